@@ -2,7 +2,7 @@
 """Headline benchmark: primary+secondary rays/s at 4096 rays x 512 samples (BASELINE.json), one
 MI355X per rank.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one pass of the hot path over one batch of 4096 synthetic rays per rank:
@@ -12,6 +12,12 @@ compositing, then for every ray with acc > 0.5 the secondary march over 8x16 = 1
 field are resident in HBM before the timed region.  With N > 1 every rank renders its own 4096 rays
 (weak scaling; rays are independent) and the per-ray output records are all-gathered over RCCL once
 per step.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the --steps steps and prints the headline line.  Everything else the line can
+carry (sustained / single-stream / exact-decoder / forced-precision / march-to-the-end passes, per-kernel attribution and
+rooflines, the eager boundary call, the CPU baseline and its parity check against the oracle, the sharp-surface scene, the
+side workloads) is measured with ``--full``.  ``--dump-outputs DIR`` writes the maps of the last timed step (rank 0's
+batch) as DIR/<name>.npy; the inputs are seeded, so two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -91,12 +97,108 @@ def parse():
                          "row tiles and interleaved tiles, and report per-shard times, max / mean and the predicted speed-up")
     ap.add_argument("--force-dist", action="store_true",
                     help="single process: create a 1-rank RCCL group anyway and run the multi-rank code path (all-gather per step)")
+    ap.add_argument("--full", action="store_true",
+                    help="batch workload: besides the headline, every secondary measurement and check (sustained / single-stream / "
+                         "exact-decoder / forced-precision / march-to-the-end passes, per-kernel rooflines, boundary call, CPU baseline "
+                         "+ parity against the oracle, sharp-surface scene, side workloads); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", type=str, default="", metavar="DIR",
+                    help="batch workload: write what the last timed step computed (rank 0's output maps) as DIR/<name>.npy (float32)")
     return ap.parse_args()
+
+
+def dump_outputs(ret, out_dir):
+    """The output maps of one step as <out_dir>/<name>.npy: floating maps in their own precision (float32 / float64), masks and
+    counts as float32.  Non-tensor entries are skipped, and so are the albedo / roughness smoothness losses: they come from the
+    device-side jitter draw, which differs from run to run (the parity checks exclude them for the same reason)."""
+    os.makedirs(out_dir, exist_ok=True)
+    names = []
+    for k, v in ret.items():
+        if not torch.is_tensor(v) or "smoothness" in k:
+            continue
+        x = v.detach().cpu()
+        x = x.numpy() if x.dtype in (torch.float32, torch.float64) else x.to(torch.float32).numpy()
+        np.save(os.path.join(out_dir, f"{k}.npy"), np.ascontiguousarray(x))
+        names.append(k)
+    return names
+
+
+def headline_fields(a, model, M, n_batches, elapsed, per_rank_ms, lanes, use_dist, world, B):
+    """The fields of the result line that describe the headline figure itself (a plain run prints these alone)."""
+    import torch.distributed as dist
+    from tensoir_amd import dist as tdist, ops
+    n_gpus = world
+    D = a.env_h * a.env_w
+    rccl = None
+    if use_dist and a.backend == "nccl":
+        try:
+            rccl = ".".join(str(x) for x in torch.cuda.nccl.version())
+        except Exception:
+            rccl = "unknown"
+    return {
+        "metric": "primary+secondary rays/sec at 4096 rays x 512 samples",
+        "value": round(n_gpus * B * a.steps / elapsed, 1), "unit": "rays/s", "n_gpus": n_gpus, "steps": a.steps, "warmup": a.warmup,
+        "ms_per_step": round(1e3 * elapsed / a.steps, 4), "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": ("f32 io and field; decoders split-bf16 x3 (hi/lo operands, 3 MFMA products), fp32 accumulate" +
+                  ("; indirect light (secondary-ray records): fp16 shadow taps + fp16 single-product decoder, fp32 accumulate"
+                   if ops.secondary_mlp_impl() == "f16" else "")) if a.decoder == "bf16x3" else "f32 (exact fp32 MFMA decoders)",
+        "data": "synthetic",
+        "config": {"workload": f"C2+C3: Renderer_TensoIR_train, {B} rays x {a.samples} samples per GPU, VM grid "
+                               f"{a.grid}^3 (16/48 comps), occupancy 128^3, 3 decoders 150-128-128, secondary "
+                               f"{D} dirs x {a.second_samples} samples on {M} surface points, SG env light",
+                   "value_is": f"whole-job rays/s over exactly --steps = {a.steps} steps (after {SETTLE_STEPS} untimed clock-settle steps "
+                               f"and --warmup = {a.warmup}): HIP-graph replay, "
+                               f"{1 if a.no_graph else lanes} batch(es) in flight per GPU, rays resident in HBM, the timed region "
+                               f"rotates through {n_batches} distinct camera poses (batch i = pose i mod {n_batches})",
+                   "rays_per_gpu": B, "samples": a.samples, "grid": a.grid, "light_dirs": D,
+                   "second_samples": a.second_samples, "surface_points": M, "ray_batches": n_batches,
+                   "sharding": f"dp{n_gpus} over rays, all-gather of {tdist.RECORD * 4} B/ray records",
+                   "launch": "eager" if a.no_graph else "hip-graph replay (one graph per step)",
+                   "in_flight": 1 if a.no_graph else lanes,
+                   "in_flight_note": "independent batches in flight per GPU: batch i replays lane (i mod in_flight)'s captured graph "
+                                     "on that lane's HIP stream; every batch is a full step" + (", lanes checked bit-identical" if a.full else ""),
+                   "march_t_stop": float(model.march_t_stop)},
+        "world_size": (dist.get_world_size() if use_dist else 1), "device_count": torch.cuda.device_count(),
+        "backend": (a.backend if use_dist else None), "rccl_version": rccl, "per_rank_ms_per_step": per_rank_ms,
+        "decoder": {"mode": a.decoder, "note": "bf16x3 = x=hi+lo bf16 split, 3 MFMA products, fp32 accumulate; parity-tested at 1e-4"
+                    if a.decoder == "bf16x3" else "exact fp32 MFMA"},
+        "library": library_info(),
+        "settle_steps": SETTLE_STEPS,
+        "precision_policy": {"indirect": model.indirect_precision(),
+                             "secondary_gather": ops.secondary_app_impl() or "fp32", "secondary_decoder": ops.secondary_mlp_impl() or a.decoder,
+                             "fused_gather_decoder": bool(ops.fused_indirect()), "limits": dict(ops.INDIRECT_PROBE),
+                             "note": "auto (default): radiance of the secondary-ray records (indirect light) from fp16 shadow planes + single-product "
+                                     "fp16 decoder, fp32 accumulation, ONLY while this field / decoder version passes the range guard and the "
+                                     "self-check probe against the full-precision kernels (`indirect.probe`; otherwise `mode` = full); every launch "
+                                     "whose output is composited directly stays fp32 / split-bf16 x3 (DESIGN 4.1, profiles/r05_precision_*.json); "
+                                     "TENSOIR_INDIRECT_PRECISION=full|f16 forces either"},
+        "full": bool(a.full),
+    }
+
+
+def headline_only(a, model, last, last_b, n_batches, elapsed, per_rank_ms, lanes, use_dist, world, rank, B):
+    """A plain run: the headline line, nothing measured beyond the timed steps (the secondary figures are --full)."""
+    import torch.distributed as dist
+    if rank == 0:
+        M = int((last["acc_map"] > 0.5).sum())
+        out = headline_fields(a, model, M, n_batches, elapsed, per_rank_ms, lanes, use_dist, world, B)
+        out["config"]["surface_points_of"] = f"the last timed step's batch (pose {last_b}); --full: the canonical pose 0"
+        if a.dump_outputs:
+            out["dumped_outputs"] = {"dir": a.dump_outputs, "step": a.steps - 1, "pose": last_b, "rank": 0}
+        pp = out["precision_policy"]                    # the line stays short: the policy's verdict, not its probe statistics
+        out["precision_policy"] = {"indirect": {k: pp["indirect"].get(k) for k in ("policy", "mode", "why")},
+                                   "secondary_gather": pp["secondary_gather"], "secondary_decoder": pp["secondary_decoder"],
+                                   "fused_gather_decoder": pp["fused_gather_decoder"]}
+        print(json.dumps(out), flush=True)
+    if use_dist:
+        dist.destroy_process_group()
 
 
 def main():
     a = parse()
     check_launch(a)
+    if a.dump_outputs and a.workload != "batch":
+        raise SystemExit(f"--dump-outputs writes the batch workload's maps; not available with --workload {a.workload}")
     if a.workload == "image":
         return bench_image(a)
     if a.workload == "relight":
@@ -146,7 +248,8 @@ def main():
     # follow each other on the stream.
     if not a.no_graph:
         try:
-            for impl in dict.fromkeys([a.decoder] + (["mfma"] if a.decoder != "mfma" and not a.no_exact_pass else [])):
+            exact_graph = a.full and a.decoder != "mfma" and not a.no_exact_pass      # the exact-decoder pass is --full only
+            for impl in dict.fromkeys([a.decoder] + (["mfma"] if exact_graph else [])):
                 make_graph(impl)
         except Exception as e:                       # capture refused on this box: the eager path is the same work
             print(f"[bench] HIP-graph capture unavailable ({type(e).__name__}: {e}); using eager launches",
@@ -275,8 +378,13 @@ def main():
     ops.MLP_IMPL = a.decoder
     settle()
     state["b"] = 0
-    elapsed, _ = timed(a.warmup, a.steps)
+    elapsed, last = timed(a.warmup, a.steps)
     per_rank_ms = [round(1e3 * x, 4) for x in state["per_rank_s"]]
+    last_b = state["last_b"]
+    if a.dump_outputs and rank == 0:                     # off the clock, before any later step reuses the graph's output buffers
+        dump_outputs(last, a.dump_outputs)
+    if not a.full:
+        return headline_only(a, model, last, last_b, len(batches), elapsed, per_rank_ms, lanes, use_dist, world, rank, B)
     n_sus = max(a.sustained_steps, a.steps)
     state["b"] = 0
     el_sus, _ = timed(0, n_sus)                          # a longer region over the same rotation, reported next to the K steps
@@ -551,46 +659,14 @@ def main():
         ops.MLP_IMPL = a.decoder
 
     value = n_gpus * B * a.steps / elapsed
-    rccl = None
-    if use_dist and a.backend == "nccl":
-        try:
-            rccl = ".".join(str(x) for x in torch.cuda.nccl.version())
-        except Exception:
-            rccl = "unknown"
-    out = {
-        "metric": "primary+secondary rays/sec at 4096 rays x 512 samples",
-        "value": round(value, 1), "unit": "rays/s", "n_gpus": n_gpus, "steps": a.steps, "warmup": a.warmup,
-        "ms_per_step": round(1e3 * elapsed / a.steps, 4), "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": ("f32 io and field; decoders split-bf16 x3 (hi/lo operands, 3 MFMA products), fp32 accumulate" +
-                  ("; indirect light (secondary-ray records): fp16 shadow taps + fp16 single-product decoder, fp32 accumulate"
-                   if ops.secondary_mlp_impl() == "f16" else "")) if a.decoder == "bf16x3" else "f32 (exact fp32 MFMA decoders)",
-        "data": "synthetic",
-        "config": {"workload": f"C2+C3: Renderer_TensoIR_train, {B} rays x {a.samples} samples per GPU, VM grid "
-                               f"{a.grid}^3 (16/48 comps), occupancy 128^3, 3 decoders 150-128-128, secondary "
-                               f"{D} dirs x {a.second_samples} samples on {M} surface points, SG env light",
-                   "value_is": f"whole-job rays/s over exactly --steps = {a.steps} steps (after {SETTLE_STEPS} untimed clock-settle steps "
-                               f"and --warmup = {a.warmup}): HIP-graph replay, "
-                               f"{1 if a.no_graph else lanes} batch(es) in flight per GPU, rays resident in HBM, the timed region "
-                               f"rotates through {len(batches)} distinct camera poses (batch i = pose i mod {len(batches)}); "
-                               "`sustained` is the same over >= 200 steps, `protocol_2_1` the BASELINE.md 2.1 figure "
-                               "(eager boundary call incl. H2D, hipEvent, median of 50)",
-                   "rays_per_gpu": B, "samples": a.samples, "grid": a.grid, "light_dirs": D,
-                   "second_samples": a.second_samples, "surface_points": M, "ray_batches": len(batches),
-                   "sharding": f"dp{n_gpus} over rays, all-gather of {tdist.RECORD * 4} B/ray records",
-                   "launch": "eager" if a.no_graph else "hip-graph replay (one graph per step)",
-                   "in_flight": 1 if a.no_graph else lanes,
-                   "in_flight_note": "independent batches in flight per GPU: batch i replays lane (i mod in_flight)'s captured graph "
-                                     "on that lane's HIP stream; every batch is a full step, lanes checked bit-identical; "
-                                     "per-kernel rooflines are measured one kernel at a time (eager pass on one stream)",
-                   "march_t_stop": float(model.march_t_stop)},
+    out = headline_fields(a, model, M, len(batches), elapsed, per_rank_ms, lanes, use_dist, world, B)
+    out["config"]["value_is"] += ("; `sustained` is the same over >= 200 steps, `protocol_2_1` the BASELINE.md 2.1 figure "
+                                  "(eager boundary call incl. H2D, hipEvent, median of 50)")
+    out["config"]["in_flight_note"] += "; per-kernel rooflines are measured one kernel at a time (eager pass on one stream)"
+    out.update({
         "sustained": sustained,
         "single_stream": single,
         "protocol_2_1": boundary,
-        "world_size": (dist.get_world_size() if use_dist else 1), "device_count": torch.cuda.device_count(),
-        "backend": (a.backend if use_dist else None), "rccl_version": rccl, "per_rank_ms_per_step": per_rank_ms,
-        "decoder": {"mode": a.decoder, "note": "bf16x3 = x=hi+lo bf16 split, 3 MFMA products, fp32 accumulate; parity-tested at 1e-4"
-                    if a.decoder == "bf16x3" else "exact fp32 MFMA"},
         "exact_fp32_decoders": exact,
         "march_to_the_end": exact_march,
         "roofline": roofline,
@@ -598,17 +674,8 @@ def main():
         "roofline_app_gather": roofline_app,
         "roofline_decoder": roofline_dec,
         "pmc": pmc_meta,
-        "library": library_info(),
-        "settle_steps": SETTLE_STEPS,
-        "precision_policy": {"indirect": model.indirect_precision(), "full": forced_lines.get("full"), "hp": forced_lines.get("hp"),
-                             "trained_300": trained_300_verdict(),
-                             "secondary_gather": ops.secondary_app_impl() or "fp32", "secondary_decoder": ops.secondary_mlp_impl() or a.decoder,
-                             "fused_gather_decoder": bool(ops.fused_indirect()), "limits": dict(ops.INDIRECT_PROBE),
-                             "note": "auto (default): radiance of the secondary-ray records (indirect light) from fp16 shadow planes + single-product "
-                                     "fp16 decoder, fp32 accumulation, ONLY while this field / decoder version passes the range guard and the "
-                                     "self-check probe against the full-precision kernels (`indirect.probe`; otherwise `mode` = full); every launch "
-                                     "whose output is composited directly stays fp32 / split-bf16 x3 (DESIGN 4.1, profiles/r05_precision_*.json); "
-                                     "TENSOIR_INDIRECT_PRECISION=full|f16 forces either"},
+        "precision_policy": dict(out["precision_policy"], full=forced_lines.get("full"), hp=forced_lines.get("hp"),
+                                 trained_300=trained_300_verdict()),
         "boundary_call": boundary,
         "cpu_baseline": cpu,
         "parity": parity,
@@ -617,7 +684,7 @@ def main():
         "gpu_kernel_ms_per_step": round(gpu_ms, 4),
         "event_bracket_overhead_ms": round(ev_over, 5),
         "kernels": [{k: (round(v, 4) if isinstance(v, float) else v) for k, v in r.items()} for r in rows[:8]],
-    }
+    })
     if cpu:
         out["speedup_vs_cpu_baseline"] = round(value / cpu["value"], 1)
     if a.breakdown:

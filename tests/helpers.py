@@ -1,4 +1,6 @@
 """Shared test helpers: golden fixture -> checkpoint / oracle Scene, error metrics."""
+import io
+
 import numpy as np
 import torch
 
@@ -129,4 +131,88 @@ def depth_discontinuity_rays(O, sc, ref, rays, light_idx, candidates, n_sample, 
         spread = float((v.max(0).values - v.min(0).values).max())
         if spread > tol:
             out[i] = spread
+    return out
+
+
+# ---- recorded host-side results of the reference (tests/golden/host_reference.npz, oracle/make_golden_host.py) -------------
+def digest(t):
+    """sha256 over a tensor's shape and values (floats widened to float64, integers to int64): equal digests <=> torch.equal."""
+    import hashlib
+    x = t.detach().cpu().contiguous()
+    x = x.to(torch.float64) if x.is_floating_point() else x.to(torch.int64)
+    return hashlib.sha256(repr(tuple(x.shape)).encode() + x.numpy().tobytes()).hexdigest()
+
+
+def tv_loss(x):
+    """Total variation of a [N, C, H, W] plane as TensoRF-style models regularise it (weight 1): twice the mean squared forward
+    difference along H plus that along W (means over C x (H-1) x W and C x H x (W-1)), divided by N."""
+    n, c, h, w = x.shape
+    dh = (x[:, :, 1:, :] - x[:, :, :h - 1, :]).pow(2).sum()
+    dw = (x[:, :, :, 1:] - x[:, :, :, :w - 1]).pow(2).sum()
+    return 2 * (dh / (c * (h - 1) * w) + dw / (c * h * (w - 1))) / n
+
+
+def field_trace(m):
+    """What the upsample / shrink comparison pins of a model: every plane and line, the box and the step geometry."""
+    out = {}
+    for name in ("density_plane", "density_line", "app_plane", "app_line"):
+        for i, t in enumerate(getattr(m, name)):
+            out[f"{name}.{i}"] = digest(t)
+    for name in ("aabb", "gridSize", "units", "invaabbSize"):
+        out[name] = digest(getattr(m, name))
+    out["stepSize"] = repr(float(m.stepSize))
+    out["nSamples"] = repr(int(m.nSamples))
+    return out
+
+
+def upsample_shrink_trace(m):
+    """field_trace after loading, after upsample_volume_grid(gridSize + 5) and after shrink to a box inside the aabb; plus
+    whether the shrink took the branch for a mask grid that differs from the field's."""
+    import contextlib
+    trace = {"load": field_trace(m)}
+    target = [int(g) + 5 for g in m.gridSize]
+    with contextlib.redirect_stdout(io.StringIO()):
+        m.upsample_volume_grid(target)
+    trace["upsample"] = field_trace(m)
+    lo, hi = m.aabb[0], m.aabb[1]
+    new_aabb = torch.stack([lo + 0.21 * (hi - lo), hi - 0.17 * (hi - lo)])
+    trace["mask_grid_differs"] = repr(bool(not torch.all(m.alphaMask.gridSize == m.gridSize)))
+    with contextlib.redirect_stdout(io.StringIO()):
+        m.shrink(new_aabb.clone())
+    trace["shrink"] = field_trace(m)
+    return trace
+
+
+def regulariser_trace(m, tv):
+    """density_L1, vector_comp_diffs, TV_loss_density / _app (with the TV callable `tv`), the learning rates and parameter counts
+    of the optimizer groups."""
+    vals = {name: float(getattr(m, name)(*args).detach()) for name, args in
+            (("density_L1", ()), ("vector_comp_diffs", ()), ("TV_loss_density", (tv,)), ("TV_loss_app", (tv,)))}
+    lrs = [g["lr"] for g in m.get_optparam_groups(0.02, 0.001)]
+    counts = [sum(p.numel() for p in (g["params"] if not isinstance(g["params"], torch.Tensor) else [g["params"]]))
+              for g in m.get_optparam_groups()]
+    return {"values": vals, "lrs": lrs, "counts": counts}
+
+
+SEEDED_CASES = [("sg", "derived_plus_predicted"), ("pixel", "derived_plus_predicted"), ("sg", "residue_prediction")]
+
+
+def seeded_construction_trace(ctor, light_kind, normals_kind):
+    """A model built under torch seed 77 (`ctor(aabb, grid, device, **kw)`) and its stratified light directions under seeds
+    5 and 6: digests of every state_dict entry, the light tables and the drawn directions."""
+    import contextlib
+    aabb = torch.tensor([[-1.5, -1.4, -1.3], [1.5, 1.4, 1.3]])
+    kw = dict(density_n_comp=[16, 16, 16], appearance_n_comp=[48, 48, 48], app_dim=27, shadingMode="MLP_Fea", step_ratio=0.5,
+              normals_kind=normals_kind, light_rotation=["000", "120"], envmap_w=8, envmap_h=4,
+              light_kind=light_kind, numLgtSGs=128)
+    torch.manual_seed(77)
+    with contextlib.redirect_stdout(io.StringIO()):
+        m = ctor(aabb.clone(), [12, 14, 16], "cpu", **kw)
+    out = {"sd/" + k: digest(v) for k, v in m.state_dict().items()}
+    for name in ("light_area_weight", "fixed_viewdirs", "light_rotation_matrix"):
+        out[name] = digest(getattr(m, name))
+    torch.manual_seed(5)
+    out["dirs/stratified_sampling"] = digest(m.gen_light_incident_dirs(method="stratified_sampling"))
+    torch.manual_seed(6)
+    out["dirs/stratifed_sample_equal_areas"] = digest(m.gen_light_incident_dirs(method="stratifed_sample_equal_areas"))
     return out

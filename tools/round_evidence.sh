@@ -16,8 +16,8 @@ cp "$OUT/parity_fullsize.json" "$OUT/${TAG}_parity_fullsize.json" 2>/dev/null
 cp "$OUT/precision_policy_tests.json" "$OUT/${TAG}_precision_policy_tests.json" 2>/dev/null
 P="$OUT/prof_${TAG}"; mkdir -p "$P"
 cd /tmp && export TMPDIR=/tmp
-CMD1="python $REPO/bench.py --steps 10 --warmup 2 --no-cpu-baseline --profile-steps 1 --boundary-calls 3 --no-exact-pass --no-full-pass --no-sharp-scene --no-side-workloads --sustained-steps 10 --in-flight 1"
-CMD2="python $REPO/bench.py --steps 10 --warmup 2 --no-cpu-baseline --profile-steps 1 --boundary-calls 3 --no-exact-pass --no-full-pass --no-sharp-scene --no-side-workloads --sustained-steps 10"
+CMD1="python $REPO/bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --profile-steps 1 --boundary-calls 3 --no-exact-pass --no-full-pass --no-sharp-scene --no-side-workloads --sustained-steps 10 --in-flight 1"
+CMD2="python $REPO/bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --profile-steps 1 --boundary-calls 3 --no-exact-pass --no-full-pass --no-sharp-scene --no-side-workloads --sustained-steps 10"
 timeout -k 5 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$P/trace" -o trace -- $CMD1 > "$P/trace.log" 2>&1
 timeout -k 5 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$P/trace2" -o trace -- $CMD2 > "$P/trace2.log" 2>&1
 # the hp route (what a trained checkpoint runs): the same command with the indirect-light policy forced
@@ -45,7 +45,7 @@ prune; du -sh "$P" "$OUT"
 cd "$REPO"
 timeout -k 5 900 python tools/precision_300.py --out "$OUT/${TAG}_precision_trained_300.json" > "$OUT/${TAG}_precision.log" 2>&1; echo "precision rc=$?"
 [ -s "$OUT/${TAG}_precision_trained_300.json" ] && cp "$OUT/${TAG}_precision_trained_300.json" "$REPO/profiles/r06_precision_trained_300.json"
-timeout -k 5 900 python bench.py --breakdown "$OUT/${TAG}_breakdown.json" > "$OUT/${TAG}_bench.json" 2> "$OUT/${TAG}_bench.err"
+timeout -k 5 900 python bench.py --full --breakdown "$OUT/${TAG}_breakdown.json" > "$OUT/${TAG}_bench.json" 2> "$OUT/${TAG}_bench.err"
 echo "bench rc=$?"; tail -c 500 "$OUT/${TAG}_bench.json"; echo; tail -3 "$OUT/${TAG}_bench.err"
 timeout -k 5 500 python bench.py --workload image --simulate-ranks 8 > "$OUT/${TAG}_image_bench.json" 2> "$OUT/${TAG}_image_bench.err"; echo "image rc=$?"
 timeout -k 5 500 python bench.py --workload relight --simulate-ranks 8 > "$OUT/${TAG}_relight_bench.json" 2> "$OUT/${TAG}_relight_bench.err"; echo "relight rc=$?"
