@@ -733,6 +733,34 @@ int tir_shade_integrate_bwd(const float* maps, const float* rays, const float* d
 int tir_env_sg_bwd(const TirEnvSG* e, const float* dirs, int32_t D, const float* g_env, float* g_sgs,
                    void* stream);
 
+/* ---- Mesh export: marching cubes on a dense lattice (scripts/export_mesh.py:15-24 -> utils.py:164-226,
+ *      convert_sdf_samples_to_ply -> skimage.measure.marching_cubes; the lattice is tir_dense_alpha's output).
+ *   vol [gx][gy][gz] fp32, contiguous, z fastest; array axis 0/1/2 = x/y/z.  gx, gy, gz >= 2.
+ *   inside:    a lattice point is inside iff value > level (a value exactly at `level` is outside).
+ *   vertices:  one per lattice edge that crosses the level (one end inside, the other not), owned by the edge's lower point p
+ *              and axis; position origin + (idx(p) + t e_axis) * spacing per component, t = (level - v0) / (v1 - v0) along
+ *              the edge, every fp32 operation rounded on its own (no contraction).
+ *   normals:   -(central-difference gradient, one-sided on the lattice boundary, in index units) interpolated along the edge
+ *              and normalised: they point toward decreasing values.
+ *   faces:     int32 vertex triples from a sign-only case table (tensoir_amd/csrc/tir_mc_table.hpp, generated by
+ *              tools/make_mc_table.py): ambiguous faces separate their inside corners, so the mesh is crack-free;
+ *              every triangle's right-hand normal points from inside (high values) to outside.
+ *   order:     vertices in (point linear index, axis x < y < z) order, faces in (cell linear index, table) order; no
+ *              atomics, so two calls give bit-identical output.
+ * Use: nb = tir_mc_blocks(g); tir_mc_count -> counts [2][nb] (vertices, faces per block of lattice points) and their
+ * exclusive scans offsets [2][nb+1]; the caller reads the totals offsets[nb] and offsets[2*nb+1] back, allocates, then
+ * tir_mc_emit writes verts [V][3], normals [V][3], faces [F][3] and the workspace vbase [gx*gy*gz] (int32, first vertex of
+ * each point).  n_verts / n_faces are the totals (capacities of the outputs; nothing is written beyond them).
+ * tir_mc_blocks returns nb, or TIR_ERR_ARG (a dimension < 2) / TIR_ERR_UNSUPPORTED (more than 2^31-1 lattice points, or a
+ * lattice whose worst-case vertex or face total -- every edge crossing, every cell at the table's maximum -- overflows
+ * int32); the two calls validate the same way, and null pointers, before any device work. */
+int64_t tir_mc_blocks(int32_t gx, int32_t gy, int32_t gz);
+int tir_mc_count(const float* vol, int32_t gx, int32_t gy, int32_t gz, float level, int32_t* counts, int32_t* offsets,
+                 void* stream);
+int tir_mc_emit(const float* vol, int32_t gx, int32_t gy, int32_t gz, float level, float spacing_x, float spacing_y,
+                float spacing_z, float origin_x, float origin_y, float origin_z, const int32_t* offsets, int32_t n_verts,
+                int32_t n_faces, int32_t* vbase, float* verts, float* normals, int32_t* faces, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -149,6 +149,9 @@ SIGNATURES = {
     "tir_gemm_tn_bf16x3": (C.c_int, [P, I32, I32, P, I32, I32, I32, I64, P, I32, P, P]),
     "tir_shade_integrate_bwd": (C.c_int, [P, P, P, P, P, P, P, P, I32, I32, I32, I32, I32, F32, P, P, P, P]),
     "tir_env_sg_bwd": (C.c_int, [C.POINTER(TirEnvSG), P, I32, P, P, P]),
+    "tir_mc_blocks": (I64, [I32, I32, I32]),
+    "tir_mc_count": (C.c_int, [P, I32, I32, I32, F32, P, P, P]),
+    "tir_mc_emit": (C.c_int, [P, I32, I32, I32, F32, F32, F32, F32, F32, F32, F32, P, I32, I32, P, P, P, P, P]),
 }
 
 _lib = None

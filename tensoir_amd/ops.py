@@ -1423,3 +1423,34 @@ def env_sg_bwd(lgtSGs, rot, dirs, g_env):
     desc = TirEnvSG(sgs.data_ptr(), rot.data_ptr(), sgs.shape[0], rot.shape[0])
     _call("tir_env_sg_bwd", C.byref(desc), _ptr(dirs), dirs.shape[0], _ptr(f32(g_env, "g_env", 3)), _ptr(g), _stream())
     return g
+
+
+def marching_cubes(vol, level, spacing=(1.0, 1.0, 1.0), origin=(0.0, 0.0, 0.0)):
+    """Marching cubes of a dense lattice vol [gx, gy, gz] (tir_mc_count + tir_mc_emit; contract: include/tensoir_hip.h).
+    -> (verts [V, 3] f32, faces [F, 3] i32, normals [V, 3] f32), all on vol's device.  Vertex i of edge (p, axis) lies at
+    origin + (idx(p) + t e_axis) * spacing; faces wind so that their right-hand normal points from inside (value > level)
+    to outside.  The totals are read back once (8 bytes, one sync): the output size depends on the data.  An empty surface
+    gives zero-row tensors."""
+    vol = f32(vol, "vol")
+    if vol.dim() != 3:
+        raise ValueError(f"vol: expected [gx, gy, gz], got {tuple(vol.shape)}")
+    gx, gy, gz = vol.shape
+    sp = [float(s) for s in spacing]
+    org = [float(o) for o in origin]
+    if len(sp) != 3 or len(org) != 3:
+        raise ValueError("spacing and origin take three values each")
+    nb = int(lib().tir_mc_blocks(gx, gy, gz))
+    if nb < 0:
+        check(nb, "tir_mc_blocks")
+    dev = vol.device
+    counts = torch.empty((2, nb), dtype=torch.int32, device=dev)
+    offsets = torch.empty((2, nb + 1), dtype=torch.int32, device=dev)
+    _call("tir_mc_count", _ptr(vol), gx, gy, gz, float(level), _ptr(counts), _ptr(offsets), _stream())
+    n_verts, n_faces = [int(x) for x in offsets[:, nb].cpu()]
+    verts = torch.empty((n_verts, 3), dtype=torch.float32, device=dev)
+    normals = torch.empty((n_verts, 3), dtype=torch.float32, device=dev)
+    faces = torch.empty((n_faces, 3), dtype=torch.int32, device=dev)
+    vbase = torch.empty((gx * gy * gz,), dtype=torch.int32, device=dev) if n_verts else None
+    _call("tir_mc_emit", _ptr(vol), gx, gy, gz, float(level), *sp, *org, _ptr(offsets), n_verts, n_faces, _ptr(vbase),
+          _ptr(verts if n_verts else None), _ptr(normals if n_verts else None), _ptr(faces if n_faces else None), _stream())
+    return verts, faces, normals

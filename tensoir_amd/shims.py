@@ -4,6 +4,8 @@ tensorboard.  Product side (used by ``python -m tensoir_amd.run``): a module is 
 cannot be imported.  None of them is on the hot path -- they are image I/O, logging, metrics and CLI parsing --
 so the stand-ins either implement the few functions the training script actually calls (``configargparse``,
 ``SummaryWriter``, ``kornia.create_meshgrid``, ``imageio.imwrite`` through PIL) or raise a clear error on use.
+scripts/export_mesh.py needs ``skimage.measure.marching_cubes`` and ``plyfile``: the first runs on the HIP marching-cubes
+kernels (tir_mc_*), the second is a minimal binary PLY writer (``tensoir_amd.mesh``).
 scripts/relight_importance.py additionally writes videos, reads its own PNGs back, colour-maps depth and asks for LPIPS:
 ``imageio.mimsave`` / ``imageio.v2.imread`` go through PIL, ``cv2.applyColorMap`` is a small numpy jet ramp, and ``lpips.LPIPS``
 -- whose pretrained networks cannot exist offline -- reports NaN (the metric is then visibly unmeasured, nothing else changes).
@@ -298,6 +300,70 @@ class _Compose:
         return x
 
 
+# ----------------------------------------------------------------------------------------------- mesh export
+# scripts/export_mesh.py -> utils.py:164-226 (convert_sdf_samples_to_ply): skimage.measure.marching_cubes on the HIP path and a
+# minimal plyfile that writes through tensoir_amd.mesh's writer.
+def marching_cubes(volume, level=None, *, spacing=(1.0, 1.0, 1.0), gradient_direction="descent", step_size=1,
+                   allow_degenerate=True, method="lewiner", mask=None):
+    """skimage.measure.marching_cubes (0.18) for the call convert_sdf_samples_to_ply makes, computed by tir_mc_* on the GPU
+    (tensoir_amd.ops.marching_cubes).  Returns numpy (verts, faces, normals, values) with scikit-image's dtypes and
+    scikit-image's winding, which is the reverse of the kernel's (the reference flips it back, utils.py:191).  `values` holds
+    `level` for every vertex: each vertex is the linear-interpolation crossing of one lattice edge, where the interpolated
+    volume equals the level.  Options the reference never passes raise ValueError before any device work."""
+    import numpy as np
+    import torch
+
+    from . import ops
+    if level is None:
+        raise ValueError("marching_cubes stand-in: `level` is required")
+    if mask is not None or step_size != 1 or gradient_direction != "descent" or method != "lewiner" or not allow_degenerate:
+        raise ValueError("marching_cubes stand-in: only level, spacing and the defaults (gradient_direction='descent', "
+                         "step_size=1, allow_degenerate=True, method='lewiner', mask=None) are supported")
+    vol = np.ascontiguousarray(volume, dtype=np.float32)
+    if vol.ndim != 3:
+        raise ValueError("marching_cubes stand-in: expected a 3-D volume")
+    if len(spacing) != 3:
+        raise ValueError("`spacing` must consist of three floats.")
+    # the dtype np.r_[spacing] has for scikit-image: fp32 for the reference's 0-d float32 tensors, fp64 for Python floats
+    sp_dtype = np.result_type(*[np.asarray(s).dtype for s in spacing])
+    sp = np.array([float(s) for s in spacing], dtype=sp_dtype)
+    unit = np.array_equal(sp, (1, 1, 1))
+    verts, faces, normals = ops.marching_cubes(torch.from_numpy(vol).cuda(), float(level), [float(s) for s in sp])
+    # scikit-image scales its fp32 vertices by np.r_[spacing] (skipped for unit spacing): the product's dtype is theirs
+    vdt = np.float32 if unit else np.result_type(np.float32, sp_dtype)
+    verts = verts.cpu().numpy().astype(vdt)
+    faces = np.ascontiguousarray(faces.cpu().numpy()[:, ::-1])
+    normals = normals.cpu().numpy()
+    values = np.full(verts.shape[0], level, dtype=np.float32)
+    return verts, faces, normals, values
+
+
+class PlyElement:
+    """plyfile.PlyElement.describe(structured_array, name) -- what convert_sdf_samples_to_ply uses."""
+
+    def __init__(self, name, data):
+        self.name, self.data = name, data
+
+    @staticmethod
+    def describe(data, name, len_types=None, val_types=None, comments=None):
+        if len_types or val_types:
+            raise ValueError("PlyElement stand-in: len_types / val_types are not supported (lists are uchar-counted)")
+        return PlyElement(name, data)
+
+
+class PlyData:
+    """plyfile.PlyData([elements]).write(path): binary little-endian, through tensoir_amd.mesh.write_elements."""
+
+    def __init__(self, elements=(), text=False, byte_order="=", comments=None, obj_info=None):
+        if text or byte_order not in ("=", "<") or comments or obj_info:
+            raise ValueError("PlyData stand-in: binary little-endian files without comments only")
+        self.elements = list(elements)
+
+    def write(self, stream):
+        from .mesh import write_elements
+        write_elements(stream, [(e.name, e.data) for e in self.elements])
+
+
 # ----------------------------------------------------------------------------------------------- install
 def install():
     """Install the stand-ins for whatever is missing; returns the list of module names that were shimmed."""
@@ -326,12 +392,12 @@ def install():
         _lazy("imageio.v2", imwrite=_imwrite, imread=_imread, mimsave=_mimsave)
         done.append("imageio")
     if _missing("plyfile"):
-        _lazy("plyfile", PlyData=None, PlyElement=None)
+        _lazy("plyfile", PlyData=PlyData, PlyElement=PlyElement)
         done.append("plyfile")
     if _missing("skimage"):
         sk = _lazy("skimage")
         sk.__path__ = []
-        _lazy("skimage.measure")
+        _lazy("skimage.measure", marching_cubes=marching_cubes)
         _lazy("skimage.metrics")
         done.append("skimage")
     if _missing("lpips"):

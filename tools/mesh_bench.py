@@ -1,0 +1,94 @@
+"""Mesh export timing (not part of bench.py): dense alpha lattice (tir_dense_alpha) and marching cubes (tir_mc_*) at the final
+grid sizes of a scene, on the small golden checkpoint's field.
+
+    python tools/mesh_bench.py [--grids 300,512] [--reps 3]      # event-timed passes, counts, export_mesh wall time
+    rocprofv3 --kernel-trace --stats --output-format csv -d DIR -o mesh -- python tools/mesh_bench.py --grids 300
+    python tools/mesh_bench.py --stats DIR                       # per-kernel GPU time from that trace
+
+One JSON line per grid: dense_alpha_ms / mc_ms (CUDA events around the calls, the marching-cubes figure includes the one 8-byte
+read-back of the totals), vertices, faces, export_s (extract_mesh + write_ply, wall clock, after a warm-up export).
+"""
+import argparse
+import csv
+import glob
+import json
+import os
+import sys
+import tempfile
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def stats(d):
+    rows = []
+    for f in sorted(glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True)):
+        with open(f) as fh:
+            rows += list(csv.DictReader(fh))
+    keep = ("k_dense_alpha", "k_mc_", "k_exclusive_scan")
+    out = {}
+    for r in rows:
+        name = r["Name"].replace("(anonymous namespace)::", "").split("(")[0].replace("void ", "")
+        if any(k in name for k in keep):
+            out[name] = {"calls": int(r["Calls"]), "total_ms": float(r["TotalDurationNs"]) / 1e6,
+                         "avg_us": float(r["AverageNs"]) / 1e3}
+    mc = sum(v["total_ms"] for k, v in out.items() if "k_mc_" in k or "k_exclusive_scan" in k)
+    da = sum(v["total_ms"] for k, v in out.items() if "k_dense_alpha" in k)
+    print(json.dumps({"kernels": out, "dense_alpha_total_ms": da, "marching_cubes_total_ms": mc}, indent=1))
+
+
+def run(grids, reps):
+    import numpy as np
+    import torch
+
+    import tensoir_amd
+    from tensoir_amd import mesh, ops
+    from tests.helpers import golden_checkpoint
+    g = np.load(os.path.join(ROOT, "tests", "golden", "small_scene.npz"))
+    eh, ew = [int(x) for x in g["scene/envmap_hw"]]
+    model = tensoir_amd.model_from_checkpoint(golden_checkpoint(g), "cuda:0", envmap_h=eh, envmap_w=ew)
+    aabb = model.aabb.detach().cpu().float()
+    for n in grids:
+        grid = [n, n, n]
+        sp = mesh.reference_spacing(aabb, grid)
+        da, mc = [], []
+        for _ in range(reps):
+            e0, e1, e2 = (torch.cuda.Event(enable_timing=True) for _ in range(3))
+            e0.record()
+            alpha, _ = ops.dense_alpha(model.packed_field(), grid, float(model.stepSize))
+            e1.record()
+            v, f, nrm = ops.marching_cubes(alpha, 0.005, sp, aabb[0].tolist())
+            e2.record()
+            torch.cuda.synchronize()
+            da.append(e0.elapsed_time(e1))
+            mc.append(e1.elapsed_time(e2))
+            del alpha
+        with tempfile.TemporaryDirectory() as d:
+            path = os.path.join(d, "m.ply")
+            mesh.export_mesh(model, path, gridSize=grid)      # warm-up
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            nv, nf = mesh.export_mesh(model, path, gridSize=grid)
+            export_s = time.perf_counter() - t0
+            ply_bytes = os.path.getsize(path)
+        print(json.dumps({"grid": n, "dense_alpha_ms": min(da), "mc_ms": min(mc), "vertices": int(v.shape[0]),
+                          "faces": int(f.shape[0]), "export_s": export_s, "export_vertices": nv, "export_faces": nf,
+                          "ply_bytes": ply_bytes}), flush=True)
+        del v, f, nrm
+        torch.cuda.empty_cache()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--grids", default="300,512")
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--stats", default=None, help="summarise the rocprofv3 kernel stats under this directory and exit")
+    a = ap.parse_args()
+    if a.stats:
+        return stats(a.stats)
+    run([int(x) for x in a.grids.split(",")], a.reps)
+
+
+if __name__ == "__main__":
+    main()
