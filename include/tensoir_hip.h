@@ -162,6 +162,11 @@ int tir_filter_rays(const TirField* f, const float* rays, int64_t n, int32_t n_s
  *       models/relight_utils.py:57-107).  sigma/grad/normal may each be NULL.  n_dev: as tir_vm_app_fwd. */
 int tir_density_grad_fwd(const TirField* f, const float* xyz, float* sigma, float* grad,
                          float* normal, int64_t n, const int32_t* n_dev, void* stream);
+/* compute_densityfeature_with_xyz_grad (models/tensoRF_rotated_lights.py:113-129): feat [n] = the density feature with the
+ *      border-clamped taps of models/relight_utils.py:57-107 (clamped indices, unclamped weights; equal to
+ *      tir_vm_density_fwd's inside [-1,1]^3), grad [n][3] = d feat / d xyz -- before the activation, unlike
+ *      tir_density_grad_fwd's `grad`.  Either output may be NULL. */
+int tir_density_feat_grad_fwd(const TirField* f, const float* xyz, float* feat, float* grad, int64_t n, void* stream);
 
 /* ---- K4: compute_appfeature / compute_intrinfeature / compute_bothfeature
  *      (models/tensoRF_rotated_lights.py:132-224).  light_idx (per point, or per `idx_map` entry when
@@ -632,6 +637,27 @@ int tir_march_primary_bwd(const TirField* f, const TirFieldGrad* g, const float*
  * path of compute_derived_normals, models/tensorBase_rotated_lights.py:839-856: create_graph=True). */
 int tir_density_grad_bwd(const TirField* f, const TirFieldGrad* g, const float* xyz,
                          const float* g_normal, int64_t n, void* stream);
+
+/* ---- Per-point density backward at caller-given points (the autograd of the per-point methods, in any point order).
+ * One point per 16-lane group (one channel per lane), eight consecutive points per group summed in registers while they
+ * share a cell, line gradients summed in LDS per workgroup when they fit.  n_dcomp 4 / 8 / 16 / 32.
+ * tir_vm_density_bwd: backward of tir_vm_density_fwd's feature (compute_densityfeature, models/tensoRF_rotated_lights.py:95-110;
+ *      F.grid_sample taps: align_corners=True, zero padding).  g_feat [n] = d loss / d feature, scatter-added into
+ *      g->dplane / g->dline.
+ * tir_density_feat_bwd: backward of tir_density_feat_grad_fwd's feature (compute_densityfeature_with_xyz_grad,
+ *      models/tensoRF_rotated_lights.py:113-129, border-clamped taps of models/relight_utils.py:81-92): the parameter
+ *      scatter of g_feat [n] into g (NULL: skipped) and g_xyz_out [n][3] = g_feat * d feat / d xyz (NULL: skipped).
+ * tir_density_feat_grad_bwd: its double backward (compute_derived_normals' create_graph=True,
+ *      models/tensorBase_rotated_lights.py:839-856): for v [n][3], the VJP of sum_i v_i . d feat / d xyz (x_i) w.r.t. the
+ *      planes and lines into g (NULL: skipped) and the Hessian-vector product g_xyz_out [n][3] = (d2 feat / d xyz2) v_i
+ *      (NULL: skipped; bilinear / linear taps: mixed second derivatives only).
+ * g and g_xyz_out may not both be NULL.  Float atomics: the summation order of the parameter gradients varies from run to run. */
+int tir_vm_density_bwd(const TirField* f, const TirFieldGrad* g, const float* xyz, const float* g_feat, int64_t n,
+                       void* stream);
+int tir_density_feat_bwd(const TirField* f, const TirFieldGrad* g, const float* xyz, const float* g_feat,
+                         float* g_xyz_out, int64_t n, void* stream);
+int tir_density_feat_grad_bwd(const TirField* f, const TirFieldGrad* g, const float* xyz, const float* v,
+                              float* g_xyz_out, int64_t n, void* stream);
 
 /* Backward of tir_vm_app_fwd.  g_rad / g_int [n][stride] (either may be NULL).  Accumulates into g->aplane,
  * g->aline, g->light_line, g->light_mean; writes y_rad / y_int [n][3*n_acomp] = (plane*line) (.) light row,

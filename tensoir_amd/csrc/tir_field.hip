@@ -351,6 +351,43 @@ extern "C" int tir_density_grad_fwd(const TirField* f, const float* xyz, float* 
     return TIR_OK;
 }
 
+// compute_densityfeature_with_xyz_grad (models/tensoRF_rotated_lights.py:113-129): the density feature with the
+// border-clamped taps of models/relight_utils.py:57-107 and its gradient in normalised xyz (before the activation)
+template <int C4>
+__global__ void __launch_bounds__(256)
+k_density_feat_grad(TirField f, const float* __restrict__ xyz, float* __restrict__ feat, float* __restrict__ grad, int64_t n) {
+    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float p[3] = {xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]};
+    float g[3] = {0.f, 0.f, 0.f}, acc = 0.f;
+#pragma unroll 1
+    for (int k = 0; k < 3; ++k) {
+        const int m0 = (k == 2) ? 1 : 0, m1 = (k == 0) ? 1 : 2, vi = 2 - k;
+        float val, du, dv, dw;
+        plane_line_grad<C4>(f.dplane[k], f.dline[k], f.grid[m1], f.grid[m0], f.grid[vi], p[m0], p[m1], p[vi], val, du, dv, dw);
+        acc += val;
+        g[m0] += du; g[m1] += dv; g[vi] += dw;
+    }
+    if (feat) feat[i] = acc;
+    if (grad) { grad[3 * i] = g[0]; grad[3 * i + 1] = g[1]; grad[3 * i + 2] = g[2]; }
+}
+
+extern "C" int tir_density_feat_grad_fwd(const TirField* f, const float* xyz, float* feat, float* grad, int64_t n, void* stream) {
+    int rc = check_field(f);
+    if (rc) return rc;
+    if (n < 0 || (n > 0 && !xyz)) return TIR_ERR_ARG;
+    if (n == 0) return TIR_OK;
+    dim3 g((unsigned)((n + 255) / 256)), b(256);
+    switch (f->n_dcomp) {
+        case 16: hipLaunchKernelGGL(k_density_feat_grad<4>, g, b, 0, tir_stream(stream), *f, xyz, feat, grad, n); break;
+        case 8:  hipLaunchKernelGGL(k_density_feat_grad<2>, g, b, 0, tir_stream(stream), *f, xyz, feat, grad, n); break;
+        case 32: hipLaunchKernelGGL(k_density_feat_grad<8>, g, b, 0, tir_stream(stream), *f, xyz, feat, grad, n); break;
+        default: hipLaunchKernelGGL(k_density_feat_grad<1>, g, b, 0, tir_stream(stream), *f, xyz, feat, grad, n); break;
+    }
+    TIR_CHECK_LAUNCH();
+    return TIR_OK;
+}
+
 // ------------------------------------------------------------------------------------------------
 // K4: appearance feature gather + light modulation + basis contraction, one point per lane.
 // The 3*Ca plane*line products never leave registers; basis_mat^T rows are wave-uniform -> scalar loads.

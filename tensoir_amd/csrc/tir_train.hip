@@ -1687,3 +1687,156 @@ extern "C" int tir_gemm_tn_small_bf16x3(const float* const* As, int32_t lda, int
     TIR_CHECK_LAUNCH();
     return TIR_OK;
 }
+
+// ------------------------------------------------------------------------------------------------
+// Per-point backward of the density feature at caller-given points: the autograd of the model's public per-point methods
+// (compute_densityfeature / compute_alpha / compute_densityfeature_with_xyz_grad / compute_derived_normals,
+// tensoir_amd/pointwise.py).  Feature f(x) = sum over the VM groups of sum_ch P L (models/tensoRF_rotated_lights.py:95-129).
+// Per point the caller gives a cotangent F of f and (CLAMP only) a cotangent G of grad_x f.  The kernel
+//   * scatter-adds d(F f + G . grad f) / d(planes, lines) into g->dplane / g->dline when `scatter` is set (scatter_density:
+//     the taps of one cell row go out from min(CH, 16) adjacent lanes, RUN consecutive points of a lane group are summed in
+//     registers while they share a cell, line gradients are summed in LDS per workgroup when they fit);
+//   * writes g_xyz[i] = F grad f + H G (CLAMP only, g_xyz != NULL), H the Hessian of f in x.  Bilinear and linear taps have no
+//     pure second derivatives, so per group H has the mixed terms only: d2f/du dv = sum P_uv L, d2f/du dw = sum P_u L_w,
+//     d2f/dv dw = sum P_v L_w, with P_uv = a - b - c + d per texel^2.
+// CLAMP == false: F.grid_sample's taps (zero padding, compute_densityfeature); CLAMP == true: border-clamped indices with
+// unclamped weights (models/relight_utils.py:81-92, compute_densityfeature_with_xyz_grad).
+// ------------------------------------------------------------------------------------------------
+template <int C4, bool LL, bool CLAMP>
+__global__ void __launch_bounds__(256)
+k_point_density_bwd(TirField f, TirFieldGrad g, const float* __restrict__ xyz, const float* __restrict__ g_feat,
+                    const float* __restrict__ v, float* __restrict__ g_xyz, int64_t n, int scatter) {
+    extern __shared__ __attribute__((aligned(16))) float lds_lines[];
+    if (LL) { lines_zero<C4 * 4>(f, lds_lines); __syncthreads(); }
+    constexpr int CH = C4 * 4, LPS = CH < 16 ? CH : 16;
+    constexpr int RUN = 8;                 // consecutive points per lane group (run-length combining, see VmRun)
+  const int64_t n_grp = (n + RUN - 1) / RUN;
+  const int64_t n_lanes = (n_grp * LPS + 255) / 256 * 256;     // whole blocks: the shuffles below need full lane groups
+  for (int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; tid < n_lanes; tid += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t grp = tid / LPS;
+    const int c = (int)(tid % LPS);
+    DensityRuns<C4> runs;
+    density_runs_init<C4>(runs);
+#pragma unroll 1
+   for (int step = 0; step < RUN; ++step) {
+    const int64_t i = grp * RUN + step;
+    const bool on = i < n;
+    const int64_t ic = on ? i : n - 1;
+    const float p[3] = {xyz[3 * ic], xyz[3 * ic + 1], xyz[3 * ic + 2]};
+    const float F = g_feat ? g_feat[ic] : 0.f;
+    float G[3] = {0.f, 0.f, 0.f};
+    if (CLAMP && v) { G[0] = v[3 * ic]; G[1] = v[3 * ic + 1]; G[2] = v[3 * ic + 2]; }
+    if (CLAMP && g_xyz) {
+        // this lane's partial sums over its channel(s) of grad f and H G
+        float gr[3] = {0.f, 0.f, 0.f}, hg[3] = {0.f, 0.f, 0.f};
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const int m0 = (k == 2) ? 1 : 0, m1 = (k == 0) ? 1 : 2, vi = 2 - k;
+            const int H = f.grid[m1], W = f.grid[m0], R = f.grid[vi];
+            const Tap1 tx = make_tap(p[m0], W), ty = make_tap(p[m1], H), tl = make_tap(p[vi], R);
+            const float wx0 = 1.0f - tx.t, wx1 = tx.t, wy0 = 1.0f - ty.t, wy1 = ty.t;
+            const float* pl = f.dplane[k];
+            const float* ln = f.dline[k];
+            const int r0 = (ty.i0 * W + tx.i0) * CH, r1 = (ty.i0 * W + tx.i1) * CH;
+            const int r2 = (ty.i1 * W + tx.i0) * CH, r3 = (ty.i1 * W + tx.i1) * CH;
+            const int q0 = tl.i0 * CH, q1 = tl.i1 * CH;
+            float s_du = 0.f, s_dv = 0.f, s_dw = 0.f, s_uv = 0.f, s_uw = 0.f, s_vw = 0.f;
+#pragma unroll
+            for (int ch = c; ch < CH; ch += LPS) {
+                const float av = pl[r0 + ch], bv = pl[r1 + ch], cv = pl[r2 + ch], dv = pl[r3 + ch];
+                const float ev = ln[q0 + ch], gv = ln[q1 + ch];
+                const float P = fmaf(dv, wx1 * wy1, fmaf(cv, wx0 * wy1, fmaf(bv, wx1 * wy0, av * (wx0 * wy0))));
+                const float Pu = fmaf(dv - cv, wy1, (bv - av) * wy0);
+                const float Pv = fmaf(dv - bv, wx1, (cv - av) * wx0);
+                const float Puv = (dv - cv) - (bv - av);
+                const float L = fmaf(gv, tl.t, ev * (1.0f - tl.t));
+                const float Lw = gv - ev;
+                s_du = fmaf(Pu, L, s_du); s_dv = fmaf(Pv, L, s_dv); s_dw = fmaf(P, Lw, s_dw);
+                s_uv = fmaf(Puv, L, s_uv); s_uw = fmaf(Pu, Lw, s_uw); s_vw = fmaf(Pv, Lw, s_vw);
+            }
+            const float su = 0.5f * (float)(W - 1), sv = 0.5f * (float)(H - 1), sw = 0.5f * (float)(R - 1);
+            const float huv = s_uv * (su * sv), huw = s_uw * (su * sw), hvw = s_vw * (sv * sw);
+            gr[m0] += s_du * su; gr[m1] += s_dv * sv; gr[vi] += s_dw * sw;
+            hg[m0] += fmaf(huv, G[m1], huw * G[vi]);
+            hg[m1] += fmaf(huv, G[m0], hvw * G[vi]);
+            hg[vi] += fmaf(huw, G[m0], hvw * G[m1]);
+        }
+#pragma unroll
+        for (int d = 1; d < LPS; d <<= 1) {
+#pragma unroll
+            for (int a = 0; a < 3; ++a) { gr[a] += __shfl_xor(gr[a], d, 64); hg[a] += __shfl_xor(hg[a], d, 64); }
+        }
+        if (on && c == 0) {
+#pragma unroll
+            for (int a = 0; a < 3; ++a) g_xyz[3 * i + a] = fmaf(F, gr[a], hg[a]);
+        }
+    }
+    if (!on || !scatter) continue;
+    if (F == 0.f && G[0] == 0.f && G[1] == 0.f && G[2] == 0.f) continue;
+    scatter_density<C4, CLAMP, LL>(runs, f, g, lds_lines, p[0], p[1], p[2], c, F, G[0], G[1], G[2]);
+   }
+    if (scatter) density_runs_flush<C4, LL>(runs, f, g, lds_lines, c);
+  }
+    if (LL) { __syncthreads(); lines_flush<C4 * 4>(f, g, lds_lines); }
+}
+
+// shared launcher of the three entries below: g == NULL skips the parameter scatter, g_xyz == NULL the coordinate output
+static int point_density_bwd(const TirField* f, const TirFieldGrad* g, const float* xyz, const float* g_feat, const float* v,
+                             float* g_xyz, int64_t n, bool clamp, void* stream) {
+    if (!f) return TIR_ERR_ARG;
+    TirFieldGrad probe = {};                  // g == NULL: only the field itself is validated
+    if (!g)
+        for (int i = 0; i < 3; ++i) { probe.dplane[i] = const_cast<float*>(f->dplane[i]); probe.dline[i] = const_cast<float*>(f->dline[i]); }
+    int rc = check_grad_field(f, g ? g : &probe, true, false);
+    if (rc) return rc;
+    if (!(f->n_dcomp == 4 || f->n_dcomp == 8 || f->n_dcomp == 16 || f->n_dcomp == 32)) return TIR_ERR_UNSUPPORTED;
+    if (n < 0 || (n > 0 && (!xyz || (!g && !g_xyz)))) return TIR_ERR_ARG;
+    if (n == 0) return TIR_OK;
+    hipStream_t s = tir_stream(stream);
+    const TirFieldGrad gd = g ? *g : TirFieldGrad{};
+    const int scatter = g ? 1 : 0;
+    const size_t line_bytes = (size_t)(f->grid[0] + f->grid[1] + f->grid[2]) * f->n_dcomp * sizeof(float);
+    const bool ll = scatter && line_bytes <= 96 * 1024;
+    const size_t lds = ll ? line_bytes : 0;
+    const int lps = f->n_dcomp < 16 ? f->n_dcomp : 16;       // lanes per point, 8 consecutive points per lane group
+    int64_t blocks = ((n + 7) / 8 * lps + 255) / 256;
+    if (blocks > 1024) blocks = 1024;
+    dim3 grid((unsigned)blocks), blk(256);
+#define TIR_LAUNCH_PB(C4, CL)                                                                                          \
+    do {                                                                                                               \
+        if (ll) {                                                                                                      \
+            if (int rc_ = tir_allow_dynamic_lds(reinterpret_cast<const void*>(k_point_density_bwd<C4, true, CL>), 96 * 1024)) return rc_; \
+            hipLaunchKernelGGL((k_point_density_bwd<C4, true, CL>), grid, blk, lds, s, *f, gd, xyz, g_feat, v, g_xyz, n, scatter); \
+        } else                                                                                                         \
+            hipLaunchKernelGGL((k_point_density_bwd<C4, false, CL>), grid, blk, 0, s, *f, gd, xyz, g_feat, v, g_xyz, n, scatter); \
+    } while (0)
+#define TIR_LAUNCH_PB_C(C4) do { if (clamp) TIR_LAUNCH_PB(C4, true); else TIR_LAUNCH_PB(C4, false); } while (0)
+    switch (f->n_dcomp) {
+        case 16: TIR_LAUNCH_PB_C(4); break;
+        case 8:  TIR_LAUNCH_PB_C(2); break;
+        case 32: TIR_LAUNCH_PB_C(8); break;
+        default: TIR_LAUNCH_PB_C(1); break;
+    }
+#undef TIR_LAUNCH_PB_C
+#undef TIR_LAUNCH_PB
+    TIR_CHECK_LAUNCH();
+    return TIR_OK;
+}
+
+extern "C" int tir_vm_density_bwd(const TirField* f, const TirFieldGrad* g, const float* xyz, const float* g_feat, int64_t n,
+                                  void* stream) {
+    if (!g || (n > 0 && !g_feat)) return TIR_ERR_ARG;
+    return point_density_bwd(f, g, xyz, g_feat, nullptr, nullptr, n, false, stream);
+}
+
+extern "C" int tir_density_feat_bwd(const TirField* f, const TirFieldGrad* g, const float* xyz, const float* g_feat,
+                                    float* g_xyz_out, int64_t n, void* stream) {
+    if (n > 0 && !g_feat) return TIR_ERR_ARG;
+    return point_density_bwd(f, g, xyz, g_feat, nullptr, g_xyz_out, n, true, stream);
+}
+
+extern "C" int tir_density_feat_grad_bwd(const TirField* f, const TirFieldGrad* g, const float* xyz, const float* v,
+                                         float* g_xyz_out, int64_t n, void* stream) {
+    if (n > 0 && !v) return TIR_ERR_ARG;
+    return point_density_bwd(f, g, xyz, nullptr, v, g_xyz_out, n, true, stream);
+}

@@ -66,11 +66,15 @@ def is_channel_last(p):
     return (c == 1 or sc == 1) and (w == 1 or sw == c) and (h == 1 or sh == w * c)
 
 
-def _no_grad_only(what, *tensors):
-    if torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad for t in tensors):
-        raise NotImplementedError(
-            f"{what}: backward kernels are not implemented yet (SURVEY.md section 8f-1); "
-            "call under torch.no_grad() -- tensoir_amd never falls back to eager PyTorch")
+def _wants_grad(what, *tensors):
+    """True when autograd needs the gradients of this per-point call (tensoir_amd/pointwise.py).  Their kernels run on the
+    GPU only: a grad-enabled call on host tensors is refused -- tensoir_amd never falls back to eager PyTorch."""
+    if not (torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad for t in tensors)):
+        return False
+    if any(torch.is_tensor(t) and not t.is_cuda for t in tensors):
+        raise NotImplementedError(f"{what}: the backward kernels run on the GPU only; move the model to the GPU or call "
+                                  "under torch.no_grad() -- tensoir_amd never falls back to eager PyTorch")
+    return True
 
 
 class _DensityL1Fn(torch.autograd.Function):
@@ -193,8 +197,17 @@ class _Decoder(nn.Module):
         return self.mlp[0].weight
 
     def run(self, feat, aux, aux_map=None):
-        _no_grad_only(type(self).__name__, feat, aux, *self.parameters())
+        if _wants_grad(type(self).__name__, feat, aux, *self.parameters()):
+            return self._autograd(feat, aux, None, aux_map)
         return ops.mlp(self.packed(), feat, aux, aux_map)
+
+    def _autograd(self, feat, aux, normal, aux_map=None):
+        """The forward as a pointwise.DecoderFn (gradients to the features, the weights and biases and a derived-normal input)."""
+        from . import pointwise
+        if aux.requires_grad or aux_map is not None:
+            raise NotImplementedError(f"{type(self).__name__}: no kernel computes the gradient of the positional-encoding input "
+                                      "(pts / viewdirs); detach it")
+        return pointwise.DecoderFn.apply(self, feat, aux, normal, *pointwise.decoder_params(self))
 
 
 class MLPRender_Fea(_Decoder):
@@ -267,7 +280,8 @@ class MLPNormal_normal_and_PExyz(_Decoder):
         return ops.mlp_rows_table(self.packed(), features, self.layer1_table(pts, normal), n_dev, save_hidden)
 
     def forward(self, pts, normal, features):
-        _no_grad_only(type(self).__name__, pts, normal, features, *self.parameters())
+        if _wants_grad(type(self).__name__, pts, normal, features, *self.parameters()):
+            return self._autograd(features, pts, normal)
         return self.rows(pts, normal, features)
 
 
@@ -672,45 +686,71 @@ class TensorVMSplit(nn.Module):
         return {"policy": pol, "mode": st.get("verdict") if pol == "auto" else pol, "why": st.get("why"), "probe": st.get("stats"),
                 "probes_run": st.get("probes", 0), "fallbacks": st.get("fallbacks", 0)}
 
-    # ---- per-point field functions (reference signatures) ---------------------------------------------
+    # ---- per-point field functions (reference signatures); differentiable through tensoir_amd/pointwise.py ----------
     def compute_densityfeature(self, xyz_sampled):
-        """models/tensoRF_rotated_lights.py:95-110 -> tir_vm_density_fwd."""
-        _no_grad_only("compute_densityfeature", *self._field_params())
-        return ops.vm_density(self.packed_field(), xyz_sampled.reshape(-1, 3))[0]
+        """models/tensoRF_rotated_lights.py:95-110 -> tir_vm_density_fwd (backward tir_vm_density_bwd; the coordinates are
+        detached, as in the reference)."""
+        xyz = xyz_sampled.reshape(-1, 3)
+        if _wants_grad("compute_densityfeature", xyz, *self._field_params()):
+            from . import pointwise
+            return pointwise.DensityFeatureFn.apply(self, xyz.detach(), *pointwise.density_params(self))
+        return ops.vm_density(self.packed_field(), xyz)[0]
+
+    def compute_densityfeature_with_xyz_grad(self, xyz_sampled):
+        """models/tensoRF_rotated_lights.py:113-129 -> tir_density_feat_grad_fwd: the border-clamped taps of the reference's
+        second-order grid_sample (models/relight_utils.py:57-107); differentiable in the parameters and in xyz, twice."""
+        xyz = xyz_sampled.reshape(-1, 3)
+        if _wants_grad("compute_densityfeature_with_xyz_grad", xyz, *self._field_params()):
+            from . import pointwise
+            return pointwise.DensityFeatXyzFn.apply(self, xyz, *pointwise.density_params(self))
+        return ops.density_feat_grad(self.packed_field(), xyz, True, False)[0]
 
     def feature2density(self, density_features):
         if self.fea2denseAct == "softplus":
             return F.softplus(density_features + self.density_shift)
         return F.relu(density_features)
 
+    def _app_features(self, what, xyz_sampled, light_idx, want_rad, want_int):
+        xyz = xyz_sampled.reshape(-1, 3)
+        li = light_idx.reshape(-1).to(xyz.device, torch.int32) if want_rad else None
+        if _wants_grad(what, xyz, *self._field_params()):
+            from . import pointwise
+            return pointwise.AppFeatureFn.apply(self, xyz.detach(), li, want_rad, want_int, *pointwise.app_params(self))
+        rad, intr = ops.vm_app(self.packed_field(), xyz, li, None, want_rad, want_int, ops.APP_IMPL)
+        return tuple(t[:, :self.app_dim].contiguous() for t in (rad, intr) if t is not None)
+
     def compute_appfeature(self, xyz_sampled, light_idx):
-        """models/tensoRF_rotated_lights.py:197-224 -> tir_vm_app_fwd."""
-        _no_grad_only("compute_appfeature", *self._field_params())
-        li = light_idx.reshape(-1).to(xyz_sampled.device, torch.int32)
-        return ops.vm_app(self.packed_field(), xyz_sampled.reshape(-1, 3), li, None, True, False, ops.APP_IMPL)[0][:, :self.app_dim].contiguous()
+        """models/tensoRF_rotated_lights.py:197-224 -> tir_vm_app_fwd (backward tir_vm_app_bwd + tir_gemm_tn)."""
+        return self._app_features("compute_appfeature", xyz_sampled, light_idx, True, False)[0]
 
     def compute_bothfeature(self, xyz_sampled, light_idx):
         """models/tensoRF_rotated_lights.py:132-165."""
-        _no_grad_only("compute_bothfeature", *self._field_params())
-        li = light_idx.reshape(-1).to(xyz_sampled.device, torch.int32)
-        r, i = ops.vm_app(self.packed_field(), xyz_sampled.reshape(-1, 3), li, None, True, True, ops.APP_IMPL)
-        return r[:, :self.app_dim].contiguous(), i[:, :self.app_dim].contiguous()
+        return self._app_features("compute_bothfeature", xyz_sampled, light_idx, True, True)
 
     def compute_intrinfeature(self, xyz_sampled):
         """models/tensoRF_rotated_lights.py:167-195."""
-        _no_grad_only("compute_intrinfeature", *self._field_params())
-        return ops.vm_app(self.packed_field(), xyz_sampled.reshape(-1, 3), None, None, False, True, ops.APP_IMPL)[1][:, :self.app_dim].contiguous()
+        return self._app_features("compute_intrinfeature", xyz_sampled, None, False, True)[0]
 
     def compute_derived_normals(self, xyz_locs):
-        """models/tensorBase_rotated_lights.py:839-856 -> tir_density_grad_fwd (closed form)."""
-        _no_grad_only("compute_derived_normals", *self._field_params())
-        return ops.density_grad(self.packed_field(), xyz_locs.reshape(-1, 3))[2]
+        """models/tensorBase_rotated_lights.py:839-856 -> tir_density_grad_fwd (closed form).  With gradients on, xyz_locs is
+        made to require grad as the reference does (:841), and the normals are differentiable in the parameters and in it."""
+        xyz = xyz_locs.reshape(-1, 3)
+        if _wants_grad("compute_derived_normals", xyz_locs, *self._field_params()):
+            from . import pointwise
+            xyz_locs.requires_grad_(True)
+            return pointwise.DerivedNormalFn.apply(self, xyz_locs.reshape(-1, 3), *pointwise.density_params(self))
+        return ops.density_grad(self.packed_field(), xyz)[2]
 
     def compute_alpha(self, xyz_locs, length=1):
-        """models/tensorBase_rotated_lights.py:819-837 (occupancy cull + density on the GPU)."""
+        """models/tensorBase_rotated_lights.py:819-837 (occupancy cull + density on the GPU; differentiable in the density
+        parameters through feature2density and exp, culled points get no gradient)."""
         f = self.packed_field()
         xyz = xyz_locs.reshape(-1, 3).to(torch.float32)
-        sigma = ops.vm_density(f, self.normalize_coord(xyz), False, True)[1]
+        if _wants_grad("compute_alpha", xyz, *self._field_params()):
+            from . import pointwise
+            sigma = pointwise.DensitySigmaFn.apply(self, self.normalize_coord(xyz).detach(), *pointwise.density_params(self))
+        else:
+            sigma = ops.vm_density(f, self.normalize_coord(xyz), False, True)[1]
         if self.alphaMask is not None:
             sigma = sigma * ops.occupancy_query(f, xyz).to(sigma.dtype)
         return (1 - torch.exp(-sigma * length)).view(xyz_locs.shape[:-1])

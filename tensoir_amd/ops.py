@@ -1209,6 +1209,46 @@ def density_grad_bwd(field: TirField, grad: TirFieldGrad, xyz, g_normal):
     _call("tir_density_grad_bwd", C.byref(field), C.byref(grad), _ptr(xyz), _ptr(g_normal), xyz.shape[0], _stream())
 
 
+def density_feat_grad(field: TirField, xyz, want_feat=True, want_grad=True):
+    """compute_densityfeature_with_xyz_grad's feature [n] (border-clamped taps) and its gradient in xyz [n, 3]
+    (tir_density_feat_grad_fwd)."""
+    xyz = f32(xyz, "xyz", 3).view(-1, 3)
+    n = xyz.shape[0]
+    feat = torch.empty((n,), dtype=torch.float32, device=xyz.device) if want_feat else None
+    grad = torch.empty((n, 3), dtype=torch.float32, device=xyz.device) if want_grad else None
+    _call("tir_density_feat_grad_fwd", C.byref(field), _ptr(xyz), _ptr(feat), _ptr(grad), n, _stream())
+    return feat, grad
+
+
+def vm_density_bwd(field: TirField, grad: TirFieldGrad, xyz, g_feat):
+    """Scatter d loss / d density feature [n] at the points xyz into the density planes / lines (tir_vm_density_bwd)."""
+    xyz = f32(xyz, "xyz", 3).view(-1, 3)
+    g_feat = f32(g_feat, "g_feat").view(-1)
+    _call("tir_vm_density_bwd", C.byref(field), C.byref(grad), _ptr(xyz), _ptr(g_feat), xyz.shape[0], _stream())
+
+
+def density_feat_bwd(field: TirField, grad, xyz, g_feat, want_xyz=True):
+    """Backward of density_feat_grad's feature: parameter scatter into `grad` (None: skipped) and, when want_xyz, the
+    coordinate gradient g_feat * d feat / d xyz [n, 3] (tir_density_feat_bwd)."""
+    xyz = f32(xyz, "xyz", 3).view(-1, 3)
+    g_feat = f32(g_feat, "g_feat").view(-1)
+    g_xyz = torch.empty_like(xyz) if want_xyz else None
+    _call("tir_density_feat_bwd", C.byref(field), None if grad is None else C.byref(grad), _ptr(xyz), _ptr(g_feat),
+          _ptr(g_xyz), xyz.shape[0], _stream())
+    return g_xyz
+
+
+def density_feat_grad_bwd(field: TirField, grad, xyz, v, want_xyz=True):
+    """Double backward of density_feat_grad: for cotangents v [n, 3] of d feat / d xyz, the parameter VJP into `grad` (None:
+    skipped) and, when want_xyz, the Hessian-vector product [n, 3] (tir_density_feat_grad_bwd)."""
+    xyz = f32(xyz, "xyz", 3).view(-1, 3)
+    v = f32(v, "v", 3).view(-1, 3)
+    g_xyz = torch.empty_like(xyz) if want_xyz else None
+    _call("tir_density_feat_grad_bwd", C.byref(field), None if grad is None else C.byref(grad), _ptr(xyz), _ptr(v),
+          _ptr(g_xyz), xyz.shape[0], _stream())
+    return g_xyz
+
+
 def vm_app_bwd(field: TirField, grad: TirFieldGrad, xyz, light_idx, idx_map, g_rad, g_int):
     """Scatter d feat into the appearance planes/lines + light rows; returns (y_rad, y_int) [n, 3*Ca]."""
     xyz = f32(xyz, "xyz", 3).view(-1, 3)
