@@ -727,7 +727,8 @@ int tir_mlp_wgrad_multi(const float* const* dz1s, const float* const* dz2s, cons
                         void* stream);
 
 /* C[M][ldc] += A^T B (+ column N = A^T 1 when ones_col != 0: the bias gradient); A [n][lda] (first M columns),
- * B [n][ldb] (first N columns); M <= 128, N + ones_col <= 160.  fp32 MFMA, split over n.  bias_out (may be NULL):
+ * B [n][ldb] (first N columns); M <= 128; N + ones_col <= 160 is one launch, a wider product runs as column blocks of
+ * 128.  fp32 MFMA, split over n.  bias_out (may be NULL):
  * A^T 1 is added to bias_out[M] instead of column N of C, so that C can be the exact [M][N] weight gradient. */
 int tir_gemm_tn(const float* A, int32_t lda, int32_t M, const float* B, int32_t ldb, int32_t N,
                 int32_t ones_col, int64_t n, float* C, int32_t ldc, float* bias_out, void* stream);

@@ -108,6 +108,7 @@ def scene_from_state_dict(sd, kwargs, alpha_volume=None, alpha_aabb=None,
         light_rgbs_raw=sd.get("_light_rgbs"),         # light_kind == 'pixel': the [envmap_h * envmap_w, 3] map parameters
         light_rotation=[int(r) for r in kwargs["light_rotation"]],
         density_shift=float(kwargs["density_shift"]),
+        fea2denseAct=str(kwargs.get("fea2denseAct", "softplus")),
         distance_scale=float(kwargs["distance_scale"]),
         weight_thres=float(kwargs["rayMarch_weight_thres"]),
         near_far=[float(x) for x in kwargs["near_far"]],
@@ -246,8 +247,19 @@ def density_feature(sc, xyz, backend="aten"):
     return f
 
 
+def density_act(sc):
+    """'softplus' or 'relu' (a Scene built without the field, as by older callers, is softplus)."""
+    act = getattr(sc, "fea2denseAct", "softplus")
+    if act not in ("softplus", "relu"):
+        raise ValueError(f"fea2denseAct {act!r}: the reference knows softplus and relu")
+    return act
+
+
 def feature2density(sc, f):
-    """models/tensorBase_rotated_lights.py:813-817 (softplus branch, threshold 20)."""
+    """models/tensorBase_rotated_lights.py:813-817: softplus(f + density_shift) (threshold 20), or relu(f) -- the relu
+    branch does not add the shift."""
+    if density_act(sc) == "relu":
+        return F.relu(f)
     return F.softplus(f + sc.density_shift)
 
 
@@ -271,11 +283,14 @@ def density_grad(sc, xyz):
         g[:, m0] = g[:, m0] + torch.sum(dpu * l, dim=0)
         g[:, m1] = g[:, m1] + torch.sum(dpv * l, dim=0)
         g[:, vi] = g[:, vi] + torch.sum(p * dl, dim=0)
-    x = f + sc.density_shift
-    dsig = torch.where(x > 20, torch.ones_like(x), torch.sigmoid(x))  # softplus'
+    if density_act(sc) == "relu":
+        dsig = (f > 0).to(f.dtype)                                     # relu' (0 at 0, as torch's)
+    else:
+        x = f + sc.density_shift
+        dsig = torch.where(x > 20, torch.ones_like(x), torch.sigmoid(x))  # softplus'
     grad = dsig[:, None] * g
     normal = -grad / torch.clamp(torch.linalg.norm(grad, dim=-1, keepdim=True), min=1e-6)
-    return F.softplus(x), grad, normal
+    return feature2density(sc, f), grad, normal
 
 
 def app_planeline(sc, xyz, backend="aten"):

@@ -1515,7 +1515,19 @@ static int gemm_tn_launch(bool bf16, const float* A, int32_t lda, int32_t M, con
                           int32_t ones_col, int64_t n, float* C, int32_t ldc, float* bias_out, void* stream) {
     if (!A || !B || !C || M <= 0 || N <= 0 || n < 0) return TIR_ERR_ARG;
     ones_col = (ones_col || bias_out) ? 1 : 0;
-    if (M > 128 || N + ones_col > 160) return TIR_ERR_UNSUPPORTED;
+    if (M > 128) return TIR_ERR_UNSUPPORTED;
+    if (N + ones_col > 160) {
+        // wider than one launch's tiles (d basis_mat of 96 appearance components per plane: N = 288): column blocks of 128
+        // (a multiple of 4, so every block starts 16-byte aligned), the ones column / bias with the last block
+        if ((ldb & 3) || ldb < ((N + 3) & ~3) || ldc < N + (bias_out ? 0 : ones_col)) return TIR_ERR_ARG;
+        for (int32_t j0 = 0; j0 < N; j0 += 128) {
+            const int32_t nb = N - j0 < 128 ? N - j0 : 128;
+            const bool last = j0 + nb >= N;
+            if (int rc = gemm_tn_launch(bf16, A, lda, M, B + j0, ldb, nb, last ? ones_col : 0, n, C + j0, ldc,
+                                        last ? bias_out : nullptr, stream)) return rc;
+        }
+        return TIR_OK;
+    }
     if ((lda & 3) || (ldb & 3) || lda < ((M + 3) & ~3) || ldb < ((N + 3) & ~3) || ldc < N + (bias_out ? 0 : ones_col)) return TIR_ERR_ARG;
     if (n == 0) return TIR_OK;
     int64_t chunk = (n + 511) / 512;

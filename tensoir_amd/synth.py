@@ -39,8 +39,10 @@ def _fibonacci_sphere(n):
 def make_checkpoint(grid=(128, 128, 128), seed=20211202, light_rotation=("000",),
                     aabb=((-1.5, -1.5, -1.5), (1.5, 1.5, 1.5)), density_n_comp=(16, 16, 16),
                     app_n_comp=(48, 48, 48), app_dim=27, feature_c=128, pe=2, num_sgs=128,
-                    step_ratio=0.5, blob_sigma=0.35, blob_gain=20.0):
-    """Random-init VM field with a separable Gaussian blob in density component 0."""
+                    step_ratio=0.5, blob_sigma=0.35, blob_gain=20.0, fea2dense_act="softplus"):
+    """Random-init VM field with a separable Gaussian blob in density component 0.  fea2dense_act: the density activation
+    written into the kwargs ('softplus' or 'relu', the reference's --fea2denseAct)."""
+    assert fea2dense_act in ("softplus", "relu"), fea2dense_act
     gen = torch.Generator().manual_seed(seed)
     grid = [int(g) for g in grid]
     sd = {}
@@ -80,7 +82,7 @@ def make_checkpoint(grid=(128, 128, 128), seed=20211202, light_rotation=("000",)
         "aabb": torch.tensor(aabb, dtype=torch.float32), "gridSize": grid,
         "density_n_comp": list(density_n_comp), "appearance_n_comp": list(app_n_comp),
         "app_dim": app_dim, "density_shift": -10, "alphaMask_thres": 0.001,
-        "distance_scale": 25, "rayMarch_weight_thres": 0.0001, "fea2denseAct": "softplus",
+        "distance_scale": 25, "rayMarch_weight_thres": 0.0001, "fea2denseAct": fea2dense_act,
         "near_far": [2.0, 6.0], "step_ratio": step_ratio, "shadingMode": "MLP_Fea",
         "pos_pe": pe, "view_pe": pe, "fea_pe": pe, "featureC": feature_c,
         "normals_kind": "derived_plus_predicted", "light_num": L, "light_kind": "sg",

@@ -173,3 +173,121 @@ def test_hot_kernels_keep_their_register_budget(lib):
     allowed = ("k_mlp_valu", "k_mlp_bwd_bf16", "k_mlp_bf16_auxt<false, true>", "k_mlp_bf16_auxt<true, true>", "k_vm_app_bwd<")
     bad = [k for k in ks.values() if k["scratch"] and not k["name"].startswith(allowed)]
     assert not bad, bad
+
+
+# ---- the configuration matrix (tests/config_scenes.py): what needs no GPU -----------------------------------------------------
+def _host_packing(monkeypatch):
+    """packed_field() fills the descriptor's scalars on the host; its derived tables (basis_mat^T, mean light row) are device
+    kernels, replaced here by host stand-ins that are never read."""
+    from tensoir_amd import ops
+    monkeypatch.setattr(ops, "pack_basis", lambda w: w.detach().t().contiguous())
+    monkeypatch.setattr(ops, "light_mean", lambda ll: ll.mean(0))
+
+
+def _matrix_rows():
+    from tests import config_scenes as CS
+    return [r.name for r in CS.ROWS]
+
+
+@pytest.mark.parametrize("name", _matrix_rows())
+def test_packed_field_scalars_per_configuration(monkeypatch, name):
+    import tensoir_amd
+    from tests import config_scenes as CS
+    row = CS.ROW[name]
+    m = tensoir_amd.model_from_checkpoint(CS.checkpoint(row), "cpu", envmap_h=CS.ENVMAP_HW[0], envmap_w=CS.ENVMAP_HW[1])
+    _host_packing(monkeypatch)
+    f = m.packed_field()
+    assert (int(f.n_dcomp), int(f.n_acomp), int(f.n_lights), int(f.app_dim)) == (row.n_dcomp, row.n_acomp, row.n_lights, 27)
+    assert int(f.act) == {"softplus": 0, "relu": 1}[row.act]
+    assert [int(g) for g in f.grid] == CS.GRID
+    assert float(f.density_shift) == -10.0 and float(f.distance_scale) == 25.0
+    assert all(int(f.dplane[i]) and int(f.dline[i]) and int(f.aplane[i]) and int(f.aline[i]) for i in range(3))
+    for i in range(3):                      # the planes are gathered in place, channel-last: component stride 1
+        assert m.density_plane[i].shape[1] == row.n_dcomp and m.density_plane[i].stride(1) == 1
+        assert m.app_plane[i].shape[1] == row.n_acomp and m.app_plane[i].stride(1) == 1
+        assert int(f.dplane[i]) == m.density_plane[i].data_ptr() and int(f.aplane[i]) == m.app_plane[i].data_ptr()
+
+
+@pytest.mark.parametrize("which", ["density", "appearance"])
+def test_packed_field_refuses_unequal_per_plane_counts(monkeypatch, which):
+    import torch
+    import tensoir_amd
+    from tensoir_amd._lib import TensoirHipError
+    from tests import config_scenes as CS
+    kw = dict(density_n_comp=[16, 16, 16], appearance_n_comp=[48, 48, 48], shadingMode="MLP_Fea")
+    kw["density_n_comp" if which == "density" else "appearance_n_comp"] = [16, 8, 16] if which == "density" else [48, 24, 48]
+    m = tensoir_amd.TensorVMSplit(torch.tensor(CS.AABB), CS.GRID, "cpu", **kw)
+    _host_packing(monkeypatch)
+    with pytest.raises(TensoirHipError, match="per-plane component counts"):
+        m.packed_field()
+
+
+def test_constructor_default_configuration_round_trips():
+    """TensorVMSplit's own defaults are 8 density / 24 appearance components per plane: the model builds on the host, and its
+    kwargs + state_dict rebuild the same model."""
+    import torch
+    import tensoir_amd
+    from tests import config_scenes as CS
+    torch.manual_seed(5)
+    m = tensoir_amd.TensorVMSplit(torch.tensor(CS.AABB), CS.GRID, "cpu", shadingMode="MLP_Fea")
+    assert list(m.density_n_comp) == [8, 8, 8] and list(m.app_n_comp) == [24, 24, 24] and m.fea2denseAct == "softplus"
+    kw = m.get_kwargs()
+    assert list(kw["density_n_comp"]) == [8, 8, 8] and list(kw["appearance_n_comp"]) == [24, 24, 24]
+    m2 = tensoir_amd.model_from_checkpoint({"kwargs": kw, "state_dict": m.state_dict()}, "cpu")
+    assert m2.get_kwargs().keys() == kw.keys()
+    for k, v in kw.items():
+        w = m2.get_kwargs()[k]
+        assert (torch.equal(torch.as_tensor(v), torch.as_tensor(w)) if not isinstance(v, str) else v == w), k
+    sd, sd2 = m.state_dict(), m2.state_dict()
+    assert sd.keys() == sd2.keys() and all(torch.equal(sd[k], sd2[k]) for k in sd)
+    assert sd["density_plane.0"].shape[1] == 8 and sd["app_plane.0"].shape[1] == 24 and sd["basis_mat.weight"].shape == (27, 72)
+
+
+def test_launchers_refuse_unlisted_component_counts(lib):
+    """No entry runs another width's kernel for a count it has no instantiation for: the density entries refuse anything but
+    4 / 8 / 16 / 32, the appearance gathers anything but their own list (96 has only the fp32 gather), the merged / fp16 / fused
+    entries anything but 48 -- all on the host, before any device work."""
+    import torch
+    from tensoir_amd import _lib
+    # The pointers are HOST addresses and n > 0 (n = 0 returns OK before the checks): every call below must be refused on the host.
+    # Only counts the launchers REFUSE belong in these loops -- an accepted count would launch a kernel on host memory where a GPU
+    # is present.
+    keep = torch.zeros(64, dtype=torch.float32)
+    ptr = keep.data_ptr()
+
+    def field(n_dcomp, n_acomp):
+        f = _lib.TirField()
+        f.grid[:] = (20, 24, 28)
+        f.n_dcomp, f.n_acomp, f.app_dim, f.n_lights = n_dcomp, n_acomp, 27, 3
+        f.basis_t = f.light_line = f.light_mean = ptr
+        for i in range(3):
+            f.dplane[i] = f.dline[i] = f.aplane[i] = f.aline[i] = ptr
+        return f
+    g = _lib.TirFieldGrad()
+    for i in range(3):
+        g.dplane[i] = g.dline[i] = g.aplane[i] = g.aline[i] = ptr
+    for nd in (1, 2, 12, 24, 64):
+        f = field(nd, 48)
+        assert lib.tir_vm_density_fwd(C.byref(f), ptr, ptr, ptr, 8, None) == -1002, nd
+        assert lib.tir_density_grad_fwd(C.byref(f), ptr, ptr, ptr, ptr, 8, None, None) == -1002, nd
+        assert lib.tir_density_feat_grad_fwd(C.byref(f), ptr, ptr, ptr, 8, None) == -1002, nd
+        assert lib.tir_density_grad_bwd(C.byref(f), C.byref(g), ptr, ptr, 8, None) == -1002, nd
+        assert lib.tir_vm_density_bwd(C.byref(f), C.byref(g), ptr, ptr, 8, None) == -1002, nd
+    accepted = {"tir_vm_app_fwd": (16, 24, 48, 96), "tir_vm_app_fwd_valu": (16, 24, 48, 96), "tir_vm_app_fwd_bf16x3": (16, 24, 48),
+                "tir_vm_app_fwd_x3": (16, 24, 48)}
+    for entry, ok in accepted.items():
+        for na in (8, 12, 32, 64, 96, 192):
+            if na in ok:
+                continue
+            f = field(16, na)
+            assert getattr(lib, entry)(C.byref(f), ptr, ptr, None, ptr, ptr, 32, 0, 8, None, None) == -1002, (entry, na)
+    fh = _lib.TirFieldHalf()
+    for i in range(3):
+        fh.aplane[i] = fh.aline[i] = ptr
+    mlp = _lib.TirMlp(ptr, 27, 2, 128, 3, 0, 0)
+    for na in (16, 24, 96):
+        f = field(16, na)
+        assert lib.tir_vm_app_fwd_h16(C.byref(f), C.byref(fh), ptr, ptr, None, ptr, 32, 0, 8, None, None) == -1002, na
+        assert lib.tir_indirect_fused_fwd(C.byref(f), C.byref(fh), C.byref(mlp), ptr, ptr, None, 1, 1, ptr, ptr, 8, None, None) == -1002, na
+        assert lib.tir_vm_app_primary_fwd(C.byref(f), ptr, ptr, None, ptr, ptr, 32, 8, None, 0.01, 0, 0, None, ptr, ptr, None) == -1002, na
+        assert lib.tir_vm_app_primary_x3_fwd(C.byref(f), ptr, ptr, None, ptr, ptr, 32, 8, None, 0.01, 0, 0, None, ptr, ptr, None) == -1002, na

@@ -12,14 +12,10 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+from tests.train_check import GTOL, gerr
+from tests.train_check import check_training_step as _check_training_step
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GTOL = 2e-3
-
-
-def gerr(a, b):
-    a, b = torch.as_tensor(a).detach().double().cpu(), torch.as_tensor(b).detach().double().cpu()
-    assert a.shape == b.shape, (a.shape, b.shape)
-    return float((a - b).abs().max() / b.abs().max().clamp(min=1e-20))
 
 
 @pytest.fixture(scope="module")
@@ -53,7 +49,8 @@ def test_gemm_tn(env, impl, tol):
     gen = torch.Generator().manual_seed(3)
     for n, M, N, lda, ldb, ones in ((1000, 128, 150, 128, 160, True), (777, 27, 144, 32, 144, False),
                                     (5, 4, 128, 4, 128, True), (70000, 128, 128, 128, 128, True),
-                                    (33, 100, 7, 100, 8, True), (4097, 128, 150, 132, 152, False)):
+                                    (33, 100, 7, 100, 8, True), (4097, 128, 150, 132, 152, False),
+                                    (1000, 27, 288, 32, 288, True), (777, 27, 290, 32, 296, False)):      # wider than one launch
         A = torch.randn(n, lda, generator=gen)
         B = torch.randn(n, ldb, generator=gen)
         A[:, M:] = float("nan")                 # row padding must never leak into C
@@ -125,7 +122,9 @@ def test_small_gemm_tn(env, n):
     against fp64; padded A rows carry NaN beyond column M, ragged row counts, 1-3 operand pairs, other shapes."""
     from tensoir_amd import ops
     gen = torch.Generator().manual_seed(200 + n)
-    for M, N, lda, ldb, k in ((27, 144, 32, 144, 3), (27, 144, 32, 144, 1), (4, 30, 4, 40, 2), (32, 160, 32, 160, 2)):
+    # N = 48 / 72: the basis-matrix gradient of 16 / 24 appearance components per plane (k_gemm_tn_small<2> / <3>)
+    for M, N, lda, ldb, k in ((27, 144, 32, 144, 3), (27, 144, 32, 144, 1), (4, 30, 4, 40, 2), (32, 160, 32, 160, 2),
+                              (27, 48, 32, 48, 3), (27, 72, 32, 72, 3), (27, 72, 32, 72, 1)):
         ref = torch.zeros(M, N, dtype=torch.float64)
         pairs = []
         for _ in range(k):
@@ -386,67 +385,6 @@ def test_normals_kinds_vs_reference(env, kind):
             got = m.renderModule_normal(pts.cuda(), nrm.cuda(), feat.cuda()).cpu()
         want = env.O.render_normal_residue(sc, pts, nrm, feat)
         assert float((got - want).abs().max()) < 1e-5
-
-
-def _check_training_step(env, m, sc, relight, t_stop, min_checked, normal_gt=None):
-    from tensoir_amd import Renderer_TensoIR_train
-    O, g, tg = env.O, env.g, env.tg
-    rays, lidx = T(g, "rays/rays"), T(g, "rays/light_idx")
-    S = int(tg["train/n_samples"][0])
-    gt = T(tg, "train/rgb_gt")
-    B = rays.shape[0]
-    gen = torch.Generator().manual_seed(21)
-    jitter = torch.rand(B, 1, generator=gen)
-    noise = torch.randn(B, S, 3, generator=gen)
-    loss_ref, grads_ref, ret_ref = O.train_step_grads(sc, rays, lidx, gt, is_relight=relight, n_samples=S,
-                                                      ray_jitter=jitter, brdf_jitter=noise, second_n_sample=24,
-                                                      normal_gt=normal_gt)
-    m.zero_grad(set_to_none=True)
-    m.march_t_stop = t_stop          # 1e-6 = the product default: rays stop marching once T < 1e-6 (gradients there are < 1e-6)
-    # feed the same draws: forward() takes the ray jitter from torch.rand(B,1) on the CPU generator
-    state = torch.get_rng_state()
-    torch.manual_seed(0)
-    orig_rand = torch.rand
-
-    def fake_rand(*a, **k):
-        if tuple(a) == (B, 1) or (len(a) == 1 and tuple(a[0]) == (B, 1)):
-            return jitter.clone()
-        return orig_rand(*a, **k)
-    torch.rand = fake_rand
-    try:
-        orig_fwd = type(m).forward
-
-        def fwd(self, r, l, **k):
-            return orig_fwd(self, r, l, _brdf_jitter_dense=noise, **k)
-        type(m).forward = fwd
-        try:
-            ret = Renderer_TensoIR_train(rays, normal_gt, lidx, m, N_samples=S, white_bg=True, is_train=True,
-                                         is_relight=relight, sample_method="fixed_envirmap", device="cuda",
-                                         args=env.args)
-        finally:
-            type(m).forward = orig_fwd
-    finally:
-        torch.rand = orig_rand
-        torch.set_rng_state(state)
-    loss = O.training_loss(ret, gt.cuda(), relight)
-    assert abs(float(loss.detach()) - float(loss_ref.detach())) < 1e-5
-    for k in ("rgb_map", "acc_map", "depth_map") + (("rgb_with_brdf_map", "normal_map", "albedo_map", "normals_diff_map",
-                                                     "normals_orientation_loss_map") if relight else ()):
-        assert float((ret[k].detach().cpu() - ret_ref[k]).abs().max()) < 1e-4, k
-    loss.backward()
-    worst = {}
-    for name, p in m.named_parameters():
-        ref = grads_ref[name]
-        if float(ref.abs().max()) == 0.0:
-            assert p.grad is None or float(p.grad.abs().max()) == 0.0, name
-            continue
-        assert p.grad is not None, name
-        worst[name] = gerr(p.grad, ref)
-    bad = {k: round(v, 5) for k, v in worst.items() if v > GTOL}
-    assert not bad, (bad, {k: round(v, 6) for k, v in worst.items() if k.startswith("density") or k.startswith("app")})
-    assert len(worst) >= min_checked
-    m.zero_grad(set_to_none=True)
-    m.march_t_stop = 0.0
 
 
 def test_training_step_with_no_hits(env):
