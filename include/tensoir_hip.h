@@ -788,6 +788,37 @@ int tir_mc_emit(const float* vol, int32_t gx, int32_t gy, int32_t gz, float leve
                 float spacing_z, float origin_x, float origin_y, float origin_z, const int32_t* offsets, int32_t n_verts,
                 int32_t n_faces, int32_t* vbase, float* verts, float* normals, int32_t* faces, void* stream);
 
+/* ---- per-point bake of materials and direct lighting (tensoir_amd/bake.py).  Point p is marched inward from
+ * origins[p] along dirs[p] by tir_march_secondary_fwd with records; the caller decodes every record (BRDF decoder output
+ * rec_brdf [A][4] = albedo rgb + raw roughness, shading normal rec_normal [A][3]).
+ *
+ * tir_bake_composite reduces point p's record segment ray_rec_off[p] .. + ray_rec_cnt[p] (contiguous, in sample order; the
+ * segments themselves in any order; entries reaching beyond n_rec -- the number of record rows that exist -- are clipped):
+ *   acc = sum w,  A = sum w albedo,  R = sum w (0.9 raw + 0.09),  Nv = sum w normal,  depth = sum w z
+ * with z = dot(world(rec_xyz) - origin, dir): the march records a sample's normalised position, world = aabb_min +
+ * (rec_xyz + 1) (aabb_max - aabb_min) / 2.  aabb: SIX HOST floats {min xyz, max xyz}.  Output rows [n_points][TIR_BAKE_ROW]:
+ *   [0..2] clamp(A / max(acc, 1e-6), 0, 1)   [3] clamp(R / max(acc, 1e-6), 0, 1)
+ *   [4..6] Nv / max(|Nv|, 1e-6), or fallback_normal[p] when acc <= 0.5 or |Nv| <= 1e-6     [7] min(acc, 1) (coverage)
+ *   [8..10] origin + dir * depth / max(acc, 1e-6) (surface)   [11] depth   [12..15] 0
+ * No white background is mixed in.  A group of 8 lanes walks a segment and combines by shuffles in a fixed order: no atomics,
+ * two calls give bit-identical rows.  rows and rec_brdf must be 16-byte aligned (16-byte vector accesses). */
+#define TIR_BAKE_ROW 16
+int tir_bake_composite(const int32_t* ray_rec_off, const int32_t* ray_rec_cnt, const float* rec_w, const float* rec_xyz,
+                       const float* rec_brdf, const float* rec_normal, const float* origins, const float* dirs,
+                       const float* fallback_normal, const float* aabb, int64_t n_points, int64_t n_rec, float* rows,
+                       void* stream);
+
+/* Direct light and ambient occlusion of baked points: rows [M][TIR_BAKE_ROW] of tir_bake_composite (normal, coverage are read),
+ * dirs [D][3] unit light directions, vis [M][D] transmittance toward them (0 where the pair was not marched), env
+ * [n_lights][D][3] radiance, weight_d [D] solid angles, light_idx [M] (clamped to the table).  With cos = dot(dirs[d], normal),
+ * each product and sum rounded on its own (the caller's pair mask forms it the same way), over the d with cos > 1e-6:
+ *   out[m] = { sum vis cos w / sum cos w  (1 when that denominator is 0),  sum vis env[light_idx[m]][d][c] cos w  (c = r, g, b) }
+ * and {1, 0, 0, 0} for points with coverage <= 0.5.  One wave64 per point walks its vis row (16-byte loads when D % 4 == 0 and
+ * vis is 16-byte aligned) and reduces by shuffles in a fixed order: no atomics, bit-reproducible.  Any D > 0; M = 0 is a no-op.
+ * rows and out [M][4] must be 16-byte aligned. */
+int tir_irradiance_integrate(const float* rows, const float* dirs, const float* vis, const float* env, const float* weight_d,
+                             const int32_t* light_idx, int64_t M, int32_t D, int32_t n_lights, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,182 @@
+"""Per-point bake of what the field has recovered: albedo, roughness, shading normal, coverage and (optionally) ambient
+occlusion and direct irradiance under one of the model's lights, evaluated at surface points -- the vertices of the exported mesh
+(mesh.export_mesh(..., attributes=True)) or any other point set.
+
+    out = bake_points(model, points, outward)          # device tensors, one row per point
+    python -m tensoir_amd.bake CKPT OUT.ply [--grid N] [--level L] [--color albedo|diffuse] [--light K]
+
+Per point p with unit outward direction n and s = model.stepSize:
+  1. inward march: origin o = p + n_outside * s * n, direction d = -n, n_sample samples at z_k = k * s -- the reference's short
+     equispaced march (models/relight_utils.py:707-722 + cull + density + raw2alpha) with near = 0, far = (n_sample - 1) * s.  The
+     spacing is the primary march's, so the weights are those of a camera ray arriving along -n, but the march starts a few voxels
+     above the point and cannot be occluded by other geometry in a concavity.
+  2. decode at the samples with w > rayMarch_weight_thres: intrinsic feature -> BRDF decoder (albedo, roughness = 0.9 raw + 0.09)
+     and the shading normal the renderer composites for the model's normals_kind.
+  3. composite over those samples (tir_bake_composite): coverage = min(sum w, 1); albedo, roughness = weighted means clamped to [0, 1]; normal = the
+     normalised weighted sum, `n` where coverage <= 0.5; surface = o + d * (sum w z) / coverage.  No white background.
+  4. lighting (tir_irradiance_integrate): from `surface` along model.fixed_viewdirs, for the pairs with cos > 1e-6 on covered
+     points, visibility = T_end of the reference's visibility march; ao = sum vis cos w / sum cos w, irradiance = sum vis env cos w.
+     Direct light only (the decoded indirect radiance belongs to the training illumination and a view direction).
+All per-sample work runs in libtensoir_hip.so; there is no CPU path."""
+from __future__ import annotations
+
+import torch
+
+from . import ops, relight
+
+MAX_SAMPLES = 256      # the secondary march's limit
+
+
+def _shading_normals(model, f, xyz, intr):
+    """The per-sample normal forward() composites (field_model.py, models/tensorBase_rotated_lights.py:946-968)."""
+    kind = model.normals_kind
+    if kind in ("purely_predicted", "derived_plus_predicted"):
+        return model.renderModule_normal.run(intr, xyz)
+    if kind == "purely_derived":
+        return ops.density_grad(f, xyz)[2]
+    if kind == "residue_prediction":
+        return model.renderModule_normal.rows(xyz, ops.density_grad(f, xyz)[2], intr)
+    raise NotImplementedError(f"bake_points: normals_kind={kind!r} has no per-sample normal in the field")
+
+
+def _march_records(model, f, origins, dirs, z):
+    """The inward march with its w > thres samples recorded; the record buffers are sized from the previous call's count and
+    the march is repeated with room when they overflow (the count is read back: one host synchronisation per chunk)."""
+    n = origins.shape[0]
+    hints = model.__dict__.setdefault("_bake_cap_hints", {})
+    cap = hints.get(n) or relight._rec_capacity(n)
+    while True:
+        _, _, rec = ops.march_secondary(f, origins, dirs, z, n, None, None, None, model.march_t_stop, True, cap, False, 0)
+        total = int(rec["counter"][0].item())
+        if total <= cap:
+            break
+        cap = int(total * 1.25) + 1024
+    if len(hints) > 32:
+        hints.clear()
+    hints[n] = max(int(total * 1.5) + 4096, 1 << 14)
+    return rec, total
+
+
+def _bake_chunk(model, f, pts, nrm, li, n_sample, n_outside, lighting, vis_z, light_tables):
+    step = model.stepSize.to(pts.device, torch.float32)
+    origins = (pts + nrm * (step * float(n_outside))).contiguous()
+    dirs = (-nrm).contiguous()
+    z = relight._z_table(n_sample, 0.0, float(step) * (n_sample - 1), pts.device)
+    rec, total = _march_records(model, f, origins, dirs, z)
+    rec_w, rec_xyz = rec["w"][:total], rec["xyz"][:total]
+    if total > 0:
+        intr = model.compute_intrinfeature(rec_xyz)
+        brdf = model.renderModule_brdf.run(intr, rec_xyz)
+        normal = _shading_normals(model, f, rec_xyz, intr)
+    else:
+        brdf = torch.empty((0, 4), dtype=torch.float32, device=pts.device)
+        normal = torch.empty((0, 3), dtype=torch.float32, device=pts.device)
+    rows = ops.bake_composite(rec["off"], rec["cnt"], rec_w, rec_xyz, brdf, normal, origins, dirs, nrm, model.aabb)
+    if not lighting:
+        return rows, None
+    ldirs, area, env = light_tables
+    M, D = rows.shape[0], ldirs.shape[0]
+    n, cov = rows[:, 4:7], rows[:, 7]
+    # the cosine test of the reference's shading stage (models/relight_utils.py:436-441), formed as the integration kernel
+    # forms it (products and sums rounded one by one), so that both take the same pairs
+    cos = (n[:, 0:1] * ldirs[None, :, 0] + n[:, 1:2] * ldirs[None, :, 1]) + n[:, 2:3] * ldirs[None, :, 2]
+    active = (cos > 1e-6) & (cov > 0.5)[:, None]
+    surf = rows[:, 8:11].contiguous()
+    # only the pairs that pass get a ray: the march walks their compacted id list (as the shading stage's does) and addresses
+    # vis by pair id; the others keep the zero they are created with.  One host synchronisation: the length of the list.
+    ids = torch.nonzero(active.view(-1)).view(-1).to(torch.int32)
+    vis = torch.zeros((M * D,), dtype=torch.float32, device=pts.device)
+    if ids.numel():
+        n_ids = torch.full((1,), ids.numel(), dtype=torch.int32, device=pts.device)
+        ops.march_secondary(f, surf, ldirs, vis_z, ids.numel(), None, None, None, model.march_t_stop, False, 0, False, D,
+                            ray_ids=ids, n_ids_dev=n_ids, vis=vis)
+    return rows, ops.irradiance_integrate(rows, ldirs, vis.view(M, D), env, area, li)
+
+
+@torch.no_grad()
+def bake_points(model, points, outward, light_idx=0, n_sample=96, n_outside=16, lighting=True, vis_n_sample=96, vis_near=0.05,
+                vis_far=1.5, chunk=16384):
+    """points [N, 3] world positions, outward [N, 3] unit outward directions (device float32) -> dict of device tensors
+    albedo [N, 3], roughness [N], normal [N, 3], coverage [N], surface [N, 3], and with lighting ao [N], irradiance [N, 3] under
+    light `light_idx` (an int, or one int per point).  Points are processed `chunk` at a time, so no [chunk, D] buffer grows with
+    the point set; the results do not depend on `chunk` (every point is reduced on its own, in a fixed order)."""
+    pts = ops.f32(points, "points", 3).view(-1, 3)
+    nrm = ops.f32(outward, "outward", 3).view(-1, 3)
+    if nrm.shape[0] != pts.shape[0] or nrm.device != pts.device:
+        raise ValueError("points and outward take one row per point, on one device")
+    if not 1 <= int(n_sample) <= MAX_SAMPLES or not 1 <= int(vis_n_sample) <= MAX_SAMPLES:
+        raise ValueError(f"n_sample and vis_n_sample must lie in 1 .. {MAX_SAMPLES} (the secondary march's limit)")
+    if int(chunk) < 1:
+        raise ValueError("chunk must be positive")
+    dev, N = pts.device, pts.shape[0]
+    f = model.packed_field()
+    li = light_idx if torch.is_tensor(light_idx) else torch.full((N,), int(light_idx), dtype=torch.int32)
+    li = ops.to_device(li.reshape(-1), dev, torch.int32).contiguous()
+    if li.numel() != N:
+        raise ValueError("light_idx: an int or one entry per point")
+    tables = vis_z = None
+    if lighting:
+        ldirs = relight._on_device(model, "fixed_viewdirs", model.fixed_viewdirs, dev)
+        area = relight._on_device(model, "light_area_weight", model.light_area_weight, dev)
+        env = model.get_light_rgbs(ldirs, device=dev).detach().contiguous()
+        if N and not (0 <= int(li.min()) and int(li.max()) < env.shape[0]):
+            raise ValueError(f"light_idx outside 0 .. {env.shape[0] - 1}")
+        if min(int(chunk), N) * ldirs.shape[0] >= 1 << 31:
+            raise ValueError("chunk x light directions must stay below 2^31 pairs")
+        tables = (ldirs, area, env)
+        vis_z = relight._z_table(int(vis_n_sample), vis_near, vis_far, dev)
+    rows = torch.empty((N, ops.BAKE_ROW), dtype=torch.float32, device=dev)
+    light = torch.empty((N, 4), dtype=torch.float32, device=dev) if lighting else None
+    for a in range(0, N, int(chunk)):
+        b = min(N, a + int(chunk))
+        r, l = _bake_chunk(model, f, pts[a:b], nrm[a:b], li[a:b], int(n_sample), n_outside, lighting, vis_z, tables)
+        rows[a:b] = r
+        if lighting:
+            light[a:b] = l
+    out = {"albedo": rows[:, 0:3].contiguous(), "roughness": rows[:, 3].contiguous(), "normal": rows[:, 4:7].contiguous(),
+           "coverage": rows[:, 7].contiguous(), "surface": rows[:, 8:11].contiguous()}
+    if lighting:
+        out["ao"] = light[:, 0].contiguous()
+        out["irradiance"] = light[:, 1:4].contiguous()
+    return out
+
+
+def load_model(path, device="cuda", **extra):
+    """A checkpoint file in the reference's layout (TensorVMSplit.save) -> model, as model_from_checkpoint builds it; a
+    checkpoint of the general multi-light variant (it carries light_name_list) gets that class."""
+    import tensoir_amd
+    from .run import _allow_numpy_in_checkpoints
+    _allow_numpy_in_checkpoints()
+    ckpt = torch.load(path, map_location=device)
+    if "light_name_list" in ckpt["kwargs"]:
+        from .general_multi_lights import TensorVMSplit
+        kwargs = {**ckpt["kwargs"], "device": device, **extra}
+        kwargs.pop("light_num", None)
+        model = TensorVMSplit(**kwargs)
+        model.load(ckpt)
+        return model
+    return tensoir_amd.model_from_checkpoint(ckpt, device, **extra)
+
+
+def main(argv=None):
+    import argparse
+    from . import mesh
+    ap = argparse.ArgumentParser(prog="python -m tensoir_amd.bake", description="Export a checkpoint's surface as a binary PLY with "
+                                 "per-vertex normals, colour, roughness, ambient occlusion, coverage, albedo and direct irradiance.")
+    ap.add_argument("ckpt")
+    ap.add_argument("out")
+    ap.add_argument("--grid", type=int, default=None, help="lattice points per axis (default: the model's gridSize)")
+    ap.add_argument("--level", type=float, default=0.005)
+    ap.add_argument("--color", choices=("albedo", "diffuse"), default="albedo")
+    ap.add_argument("--light", type=int, default=0)
+    ap.add_argument("--envmap", type=int, nargs=2, metavar=("H", "W"), default=None, help="light direction grid (default 16 32)")
+    a = ap.parse_args(argv)
+    extra = {} if a.envmap is None else {"envmap_h": a.envmap[0], "envmap_w": a.envmap[1]}
+    model = load_model(a.ckpt, "cuda", **extra)
+    grid = None if a.grid is None else [a.grid] * 3
+    nv, nf = mesh.export_mesh(model, a.out, a.level, grid, attributes=True, color=a.color, light_idx=a.light)
+    print(f"{a.out}: {nv} vertices, {nf} faces")
+
+
+if __name__ == "__main__":
+    main()

@@ -7,6 +7,11 @@
 //   k_mc_verts   block-local scan of the per-point crossing counts: vertices + normals in (point, axis) order, vbase[p]
 //   k_mc_faces   block-local scan of the per-cell triangle counts: faces in (cell, table) order; a corner's vertex on the
 //                edge along `axis` is vbase[corner] + the number of its crossing edges along lower axes
+//
+// Per-vertex bake of the exported mesh (tensoir_amd/bake.py; contract: include/tensoir_hip.h, tir_bake_composite and
+// tir_irradiance_integrate): two reductions without atomics, every point summed in a fixed order.
+//   k_bake_composite        BAKE_LANES lanes per point walk its contiguous record segment of the short inward march
+//   k_irradiance_integrate  one wave64 per point walks its contiguous visibility row
 #define TIR_MC_CONSTANT __constant__
 #include "tir_common.hpp"
 #include "tir_mc_table.hpp"
@@ -251,7 +256,185 @@ int64_t mc_validate(int32_t gx, int32_t gy, int32_t gz) {
     return (n + MC_BLOCK_POINTS - 1) / MC_BLOCK_POINTS;
 }
 
+// ---- per-vertex bake -------------------------------------------------------------------------------------------------------
+constexpr int BAKE_LANES = 8;          // a trained surface leaves 5-30 records per ray: 1-4 strides of the segment per lane
+constexpr int BAKE_THREADS = 256;
+constexpr int BAKE_ROW = 16;           // floats per output row (TIR_BAKE_ROW)
+
+struct BakeBox {
+    float mn[3];
+    float half[3];                     // (aabb_max - aabb_min) / 2: world = mn + (normalised + 1) * half
+};
+
+__global__ void __launch_bounds__(BAKE_THREADS)
+k_bake_composite(const int32_t* __restrict__ off, const int32_t* __restrict__ cnt, const float* __restrict__ rec_w,
+                 const float* __restrict__ rec_xyz, const float* __restrict__ rec_brdf, const float* __restrict__ rec_normal,
+                 const float* __restrict__ origins, const float* __restrict__ dirs, const float* __restrict__ fallback,
+                 BakeBox box, int64_t n_points, int64_t n_rec, float* __restrict__ rows) {
+    const int64_t p = ((int64_t)blockIdx.x * BAKE_THREADS + threadIdx.x) / BAKE_LANES;
+    const int gl = threadIdx.x & (BAKE_LANES - 1);
+    // a whole lane group leaves together (BAKE_LANES divides the wave), so the shuffles below never meet a retired lane
+    if (p >= n_points) return;
+    float o[3], d[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) { o[a] = origins[3 * p + a]; d[a] = dirs[3 * p + a]; }
+    // the segment, clipped to the rows that exist (a dropped ray has cnt 0; nothing outside [0, n_rec) is ever read)
+    const int c = cnt[p];
+    int64_t b = off[p], e = b + c;
+    if (c <= 0 || b < 0) { b = 0; e = 0; }
+    if (e > n_rec) e = n_rec;
+    float acc = 0.f, alb[3] = {0.f, 0.f, 0.f}, rough = 0.f, nv[3] = {0.f, 0.f, 0.f}, depth = 0.f;
+    for (int64_t i = b + gl; i < e; i += BAKE_LANES) {
+        const float w = rec_w[i];
+        const float4 br = *reinterpret_cast<const float4*>(rec_brdf + 4 * i);
+        float z = 0.f;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            const float world = fmaf(rec_xyz[3 * i + a] + 1.0f, box.half[a], box.mn[a]);
+            z = fmaf(world - o[a], d[a], z);
+            nv[a] = fmaf(w, rec_normal[3 * i + a], nv[a]);
+        }
+        acc += w;
+        alb[0] = fmaf(w, br.x, alb[0]);
+        alb[1] = fmaf(w, br.y, alb[1]);
+        alb[2] = fmaf(w, br.z, alb[2]);
+        rough = fmaf(w, fmaf(br.w, 0.9f, 0.09f), rough);
+        depth = fmaf(w, z, depth);
+    }
+    // butterfly inside the lane group: every lane ends with the same sums, added in the same order on every call
+#pragma unroll
+    for (int s = BAKE_LANES / 2; s > 0; s >>= 1) {
+        acc += __shfl_xor(acc, s, BAKE_LANES);
+        rough += __shfl_xor(rough, s, BAKE_LANES);
+        depth += __shfl_xor(depth, s, BAKE_LANES);
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            alb[a] += __shfl_xor(alb[a], s, BAKE_LANES);
+            nv[a] += __shfl_xor(nv[a], s, BAKE_LANES);
+        }
+    }
+    if (gl >= 4) return;
+    const float den = fmaxf(acc, 1e-6f);
+    float4 out;
+    if (gl == 0) {
+        out = make_float4(fminf(fmaxf(alb[0] / den, 0.f), 1.f), fminf(fmaxf(alb[1] / den, 0.f), 1.f),
+                          fminf(fmaxf(alb[2] / den, 0.f), 1.f), fminf(fmaxf(rough / den, 0.f), 1.f));
+    } else if (gl == 1) {
+        const float len = sqrtf(nv[0] * nv[0] + nv[1] * nv[1] + nv[2] * nv[2]);
+        if (acc <= 0.5f || !(len > 1e-6f)) {
+            out = make_float4(fallback[3 * p], fallback[3 * p + 1], fallback[3 * p + 2], fminf(acc, 1.0f));
+        } else {
+            // (the fp32 sum of an opaque ray's weights can end one ulp above 1: the coverage is reported within [0, 1])
+            out = make_float4(nv[0] / len, nv[1] / len, nv[2] / len, fminf(acc, 1.0f));
+        }
+    } else if (gl == 2) {
+        const float t = depth / den;
+        out = make_float4(fmaf(d[0], t, o[0]), fmaf(d[1], t, o[1]), fmaf(d[2], t, o[2]), depth);
+    } else {
+        out = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    *reinterpret_cast<float4*>(rows + BAKE_ROW * p + 4 * gl) = out;    // 4 x 16 bytes: one 64-byte row per lane group
+}
+
+// VEC4: D % 4 == 0 and a 16-byte aligned vis -- a lane takes four neighbouring directions per 16-byte load.
+// The direction / weight / radiance tables (28 bytes per direction, 14 KB at D = 512) are read straight from global memory:
+// every wave reads the same few KB, which stay in the vector L1 / L2; staging them in LDS would cost a workgroup of four
+// points more bytes than its four visibility rows.
+template <bool VEC4>
+__global__ void __launch_bounds__(BAKE_THREADS)
+k_irradiance_integrate(const float* __restrict__ rows, const float* __restrict__ dirs, const float* __restrict__ vis,
+                       const float* __restrict__ env, const float* __restrict__ weight_d, const int32_t* __restrict__ light_idx,
+                       int64_t M, int D, int n_lights, float* __restrict__ out) {
+    const int64_t m = (int64_t)blockIdx.x * (BAKE_THREADS / 64) + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (m >= M) return;                                           // wave-uniform
+    const float4 r1 = *reinterpret_cast<const float4*>(rows + BAKE_ROW * m + 4);      // normal, coverage
+    if (!(r1.w > 0.5f)) {                                         // no surface here: unoccluded, unlit
+        if (lane == 0) *reinterpret_cast<float4*>(out + 4 * m) = make_float4(1.f, 0.f, 0.f, 0.f);
+        return;
+    }
+    int li = light_idx[m];
+    li = li < 0 ? 0 : (li >= n_lights ? n_lights - 1 : li);
+    const float* __restrict__ e = env + (size_t)li * D * 3;
+    const float* __restrict__ v = vis + (size_t)m * D;
+    float num = 0.f, den = 0.f, irr[3] = {0.f, 0.f, 0.f};
+    constexpr int PER = VEC4 ? 4 : 1;
+    for (int d0 = lane * PER; d0 < D; d0 += 64 * PER) {
+        float vv[PER];
+        if constexpr (VEC4) {
+            const float4 q = *reinterpret_cast<const float4*>(v + d0);
+            vv[0] = q.x; vv[1] = q.y; vv[2] = q.z; vv[3] = q.w;
+        } else {
+            vv[0] = v[d0];
+        }
+#pragma unroll
+        for (int j = 0; j < PER; ++j) {
+            const int d = d0 + j;
+            // the cosine exactly as the caller's activity mask forms it: three products, two sums, each rounded on its own
+            const float c = add_rn(add_rn(mul_rn(dirs[3 * d], r1.x), mul_rn(dirs[3 * d + 1], r1.y)), mul_rn(dirs[3 * d + 2], r1.z));
+            if (!(c > 1e-6f)) continue;
+            const float cw = c * weight_d[d];
+            const float vc = vv[j] * cw;
+            den += cw;
+            num += vc;
+            irr[0] = fmaf(vc, e[3 * d], irr[0]);
+            irr[1] = fmaf(vc, e[3 * d + 1], irr[1]);
+            irr[2] = fmaf(vc, e[3 * d + 2], irr[2]);
+        }
+    }
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) {
+        num += __shfl_xor(num, s, 64);
+        den += __shfl_xor(den, s, 64);
+#pragma unroll
+        for (int a = 0; a < 3; ++a) irr[a] += __shfl_xor(irr[a], s, 64);
+    }
+    if (lane == 0) *reinterpret_cast<float4*>(out + 4 * m) = make_float4(den > 0.f ? num / den : 1.f, irr[0], irr[1], irr[2]);
+}
+
 }  // namespace
+
+extern "C" int tir_bake_composite(const int32_t* ray_rec_off, const int32_t* ray_rec_cnt, const float* rec_w, const float* rec_xyz,
+                                  const float* rec_brdf, const float* rec_normal, const float* origins, const float* dirs,
+                                  const float* fallback_normal, const float* aabb, int64_t n_points, int64_t n_rec, float* rows,
+                                  void* stream) {
+    if (n_points < 0 || n_rec < 0 || !aabb) return TIR_ERR_ARG;
+    if (n_points == 0) return TIR_OK;
+    if (!ray_rec_off || !ray_rec_cnt || !origins || !dirs || !fallback_normal || !rows) return TIR_ERR_ARG;
+    if (n_rec > 0 && (!rec_w || !rec_xyz || !rec_brdf || !rec_normal)) return TIR_ERR_ARG;
+    if (((uintptr_t)rows | (uintptr_t)rec_brdf) & 15) return TIR_ERR_ARG;
+    const int64_t nblk = (n_points * BAKE_LANES + BAKE_THREADS - 1) / BAKE_THREADS;
+    if (nblk > INT32_MAX) return TIR_ERR_UNSUPPORTED;
+    BakeBox box;
+    for (int a = 0; a < 3; ++a) {
+        box.mn[a] = aabb[a];
+        box.half[a] = (aabb[3 + a] - aabb[a]) * 0.5f;
+    }
+    hipLaunchKernelGGL(k_bake_composite, dim3((unsigned)nblk), dim3(BAKE_THREADS), 0, tir_stream(stream), ray_rec_off,
+                       ray_rec_cnt, rec_w, rec_xyz, rec_brdf, rec_normal, origins, dirs, fallback_normal, box, n_points, n_rec,
+                       rows);
+    TIR_CHECK_LAUNCH();
+    return TIR_OK;
+}
+
+extern "C" int tir_irradiance_integrate(const float* rows, const float* dirs, const float* vis, const float* env,
+                                        const float* weight_d, const int32_t* light_idx, int64_t M, int32_t D, int32_t n_lights,
+                                        float* out, void* stream) {
+    if (M < 0 || D <= 0 || n_lights <= 0) return TIR_ERR_ARG;
+    if (M == 0) return TIR_OK;
+    if (!rows || !dirs || !vis || !env || !weight_d || !light_idx || !out) return TIR_ERR_ARG;
+    if (((uintptr_t)rows | (uintptr_t)out) & 15) return TIR_ERR_ARG;
+    const int64_t nblk = (M + BAKE_THREADS / 64 - 1) / (BAKE_THREADS / 64);
+    if (nblk > INT32_MAX) return TIR_ERR_UNSUPPORTED;
+    if (D % 4 == 0 && ((uintptr_t)vis & 15) == 0)
+        hipLaunchKernelGGL(k_irradiance_integrate<true>, dim3((unsigned)nblk), dim3(BAKE_THREADS), 0, tir_stream(stream), rows,
+                           dirs, vis, env, weight_d, light_idx, M, (int)D, (int)n_lights, out);
+    else
+        hipLaunchKernelGGL(k_irradiance_integrate<false>, dim3((unsigned)nblk), dim3(BAKE_THREADS), 0, tir_stream(stream), rows,
+                           dirs, vis, env, weight_d, light_idx, M, (int)D, (int)n_lights, out);
+    TIR_CHECK_LAUNCH();
+    return TIR_OK;
+}
 
 extern "C" int64_t tir_mc_blocks(int32_t gx, int32_t gy, int32_t gz) { return mc_validate(gx, gy, gz); }
 

@@ -2,6 +2,7 @@
 
     verts, faces, normals = extract_mesh(model)          # dense alpha lattice -> marching cubes (tir_dense_alpha, tir_mc_*)
     export_mesh(model, "scene.ply")                      # + binary PLY, laid out as plyfile writes the reference's mesh
+    export_mesh(model, "scene.ply", attributes=True)     # + per-vertex materials and direct lighting (tensoir_amd/bake.py)
 
 Coordinates follow the reference, quirk included (Appendix B policy: parity first): convert_sdf_samples_to_ply takes the voxel
 size as (aabb[1] - aabb[0]) / shape -- `shape`, not `shape - 1` (utils.py:186) -- although getDenseAlpha's lattice spans the
@@ -90,6 +91,90 @@ def read_ply(path):
     return v.astype(np.float32), f["i"].astype(np.int32)
 
 
+_PLY_DTYPES = {v: k for k, v in _PLY_TYPES.items()}
+_PLY_DTYPES.update({"float32": "f4", "float64": "f8", "int8": "i1", "uint8": "u1", "int16": "i2", "uint16": "u2", "int32": "i4",
+                    "uint32": "u4"})
+
+
+def read_ply_attributes(path):
+    """A binary little-endian PLY with a `vertex` element of scalar properties (x y z first) followed by a `face` element of one
+    triangle list property, as write_elements lays them out -> (verts [V, 3] f32, faces [F, 3] i32, {property: [V] array} of the
+    vertex properties other than x y z, in their file types; empty for a plain file)."""
+    data = open(path, "rb").read()
+    end = data.index(b"end_header\n") + len(b"end_header\n")
+    lines = data[:end].decode("ascii").split("\n")
+    if lines[0] != "ply" or lines[1] != "format binary_little_endian 1.0":
+        raise ValueError("read_ply_attributes: only binary little-endian PLY files are supported")
+    elements = []                                             # [name, count, [(property, dtype) or (property, count type, dtype)]]
+    for ln in lines[2:]:
+        t = ln.split()
+        if not t or t[0] in ("comment", "obj_info", "end_header"):
+            continue
+        if t[0] == "element":
+            elements.append([t[1], int(t[2]), []])
+        elif t[0] == "property" and elements:
+            if t[1] == "list":
+                elements[-1][2].append((t[4], "<" + _PLY_DTYPES[t[2]], "<" + _PLY_DTYPES[t[3]]))
+            else:
+                elements[-1][2].append((t[2], "<" + _PLY_DTYPES[t[1]]))
+        else:
+            raise ValueError(f"read_ply_attributes: unexpected header line {ln!r}")
+    if [e[0] for e in elements] != ["vertex", "face"]:
+        raise ValueError("read_ply_attributes: expected a vertex element followed by a face element")
+    (_, nv, vprops), (_, nf, fprops) = elements
+    if any(len(p) != 2 for p in vprops) or [p[0] for p in vprops[:3]] != ["x", "y", "z"]:
+        raise ValueError("read_ply_attributes: vertex properties must be scalars starting with x y z")
+    if len(fprops) != 1 or len(fprops[0]) != 3:
+        raise ValueError("read_ply_attributes: the face element takes one list property")
+    vdt = np.dtype([(n, t) for n, t in vprops])
+    v = np.frombuffer(data, dtype=vdt, count=nv, offset=end)
+    fdt = np.dtype([("n", fprops[0][1]), ("i", fprops[0][2], (3,))])
+    f = np.frombuffer(data, dtype=fdt, count=nf, offset=end + vdt.itemsize * nv)
+    if nf and not (f["n"] == 3).all():
+        raise ValueError("read_ply_attributes: only triangle faces are supported")
+    verts = np.stack([v["x"], v["y"], v["z"]], axis=1).astype(np.float32) if nv else np.zeros((0, 3), np.float32)
+    attrs = {n: np.ascontiguousarray(v[n]).astype(np.dtype(t).newbyteorder("=")) for n, t in vprops[3:]}
+    return verts, f["i"].astype(np.int32).reshape(-1, 3), attrs
+
+
+# the vertex element of export_mesh(..., attributes=True): property -> numpy type, in file order
+ATTRIBUTE_LAYOUT = ([(n, "f4") for n in ("x", "y", "z", "nx", "ny", "nz")] + [(n, "u1") for n in ("red", "green", "blue")] +
+                    [(n, "f4") for n in ("roughness", "ao", "coverage", "albedo_r", "albedo_g", "albedo_b", "irradiance_r",
+                                         "irradiance_g", "irradiance_b")])
+
+
+def field_positions(aabb, grid, verts, normals=None):
+    """Where the field must be queried for the vertices of extract_mesh / export_mesh.  The file keeps the reference's voxel-size
+    quirk (module docstring): lattice point idx is written at aabb0 + idx * (aabb1 - aabb0) / g, while the lattice the alpha
+    values were sampled on places it at aabb0 + idx * (aabb1 - aabb0) / (g - 1).  -> aabb0 + (v - aabb0) * g / (g - 1) per axis.
+    normals (marching cubes': unit, in INDEX space) -> additionally the world directions normalize(n_idx / spacing) with the true
+    lattice spacing (aabb1 - aabb0) / (g - 1): a gradient per index step is a gradient per `spacing` of world length."""
+    verts = torch.as_tensor(verts)
+    dev = verts.device
+    box = torch.as_tensor(aabb).detach().to(dev, torch.float32).reshape(2, 3)
+    g = torch.tensor([float(x) for x in grid], dtype=torch.float32, device=dev)
+    pos = box[0] + (verts.to(torch.float32) - box[0]) * (g / (g - 1))
+    if normals is None:
+        return pos
+    n = torch.as_tensor(normals).to(dev, torch.float32) / ((box[1] - box[0]) / (g - 1))
+    return pos, n / torch.linalg.norm(n, dim=-1, keepdim=True).clamp(min=1e-20)
+
+
+def vertex_colors(albedo, irradiance=None, color="albedo"):
+    """[V, 3] uint8 display colours of baked vertices: round(255 * linear2srgb(c)) with c = albedo, or the Lambertian radiance
+    clamp(albedo / pi * irradiance, 0, 1) under the baked light (color="diffuse")."""
+    from .relight import linear2srgb_torch
+    if color == "albedo":
+        c = albedo
+    elif color == "diffuse":
+        if irradiance is None:
+            raise ValueError('color="diffuse" needs the baked irradiance (lighting=True)')
+        c = (albedo / np.pi * irradiance).clamp(0, 1)
+    else:
+        raise ValueError(f"color: 'albedo' or 'diffuse', not {color!r}")
+    return torch.round(255.0 * linear2srgb_torch(c)).clamp(0, 255).to(torch.uint8)
+
+
 def reference_spacing(aabb, grid):
     """utils.py:186: (aabb[1] - aabb[0]) / shape in fp32 (the reference divides a float32 tensor by the integer shape)."""
     aabb = torch.as_tensor(aabb).detach().to("cpu", torch.float32)
@@ -107,8 +192,34 @@ def extract_mesh(model, level=0.005, gridSize=None):
 
 
 @torch.no_grad()
-def export_mesh(model, path, level=0.005, gridSize=None):
-    """extract_mesh + write_ply -> (number of vertices, number of faces)."""
-    verts, faces, _ = extract_mesh(model, level, gridSize)
-    write_ply(path, verts, faces)
-    return verts.shape[0], faces.shape[0]
+def export_mesh(model, path, level=0.005, gridSize=None, attributes=False, color="albedo", **bake_kw):
+    """extract_mesh + write_ply -> (number of vertices, number of faces).
+    attributes=True: the vertex element becomes ATTRIBUTE_LAYOUT -- positions (bit-identical to the plain export), the baked
+    shading normal, a display colour (vertex_colors), roughness, ambient occlusion, coverage, albedo and direct irradiance of
+    bake.bake_points(model, *field_positions(...), **bake_kw); the face element is unchanged."""
+    verts, faces, normals = extract_mesh(model, level, gridSize)
+    if not attributes:
+        if bake_kw or color != "albedo":
+            raise TypeError("color and the bake arguments need attributes=True")
+        write_ply(path, verts, faces)
+        return verts.shape[0], faces.shape[0]
+    from . import bake
+    grid = [int(g) for g in (model.gridSize if gridSize is None else gridSize)]
+    pos, out_dir = field_positions(model.aabb, grid, verts, normals)
+    b = bake.bake_points(model, pos.contiguous(), out_dir.contiguous(), **bake_kw)
+    rgb = vertex_colors(b["albedo"], b.get("irradiance"), color)
+    V = verts.shape[0]
+    ao = b["ao"] if "ao" in b else torch.ones((V,), dtype=torch.float32, device=verts.device)
+    irr = b["irradiance"] if "irradiance" in b else torch.zeros((V, 3), dtype=torch.float32, device=verts.device)
+    cols = torch.cat([verts, b["normal"], b["roughness"][:, None], ao[:, None], b["coverage"][:, None], b["albedo"], irr],
+                     dim=1).cpu().numpy()
+    rgb = rgb.cpu().numpy()
+    v = np.empty(V, dtype=ATTRIBUTE_LAYOUT)
+    floats = [n for n, t in ATTRIBUTE_LAYOUT if t == "f4"]
+    for k, name in enumerate(floats):
+        v[name] = cols[:, k]
+    v["red"], v["green"], v["blue"] = rgb[:, 0], rgb[:, 1], rgb[:, 2]
+    f = np.empty(faces.shape[0], dtype=[("vertex_indices", "i4", (3,))])
+    f["vertex_indices"] = faces.cpu().numpy()
+    write_elements(path, [("vertex", v), ("face", f)])
+    return V, faces.shape[0]

@@ -1494,3 +1494,48 @@ def marching_cubes(vol, level, spacing=(1.0, 1.0, 1.0), origin=(0.0, 0.0, 0.0)):
     _call("tir_mc_emit", _ptr(vol), gx, gy, gz, float(level), *sp, *org, _ptr(offsets), n_verts, n_faces, _ptr(vbase),
           _ptr(verts if n_verts else None), _ptr(normals if n_verts else None), _ptr(faces if n_faces else None), _stream())
     return verts, faces, normals
+
+
+# ---- per-point bake (tensoir_amd/bake.py) ---------------------------------------------------------
+BAKE_ROW = 16
+
+
+def bake_composite(off, cnt, rec_w, rec_xyz, rec_brdf, rec_normal, origins, dirs, fallback_normal, aabb):
+    """tir_bake_composite: the records of the inward march (march_secondary's off / cnt / w / xyz, one ray per point) and their
+    decoder outputs rec_brdf [A, 4], rec_normal [A, 3] -> rows [N, BAKE_ROW] = albedo 3, roughness, normal 3, coverage,
+    surface 3, depth, 0 x 4 (contract: include/tensoir_hip.h).  aabb: the model's [2, 3] box (host or device)."""
+    origins = f32(origins, "origins", 3).view(-1, 3)
+    n = origins.shape[0]
+    dirs = f32(dirs, "dirs", 3).view(-1, 3)
+    fallback_normal = f32(fallback_normal, "fallback_normal", 3).view(-1, 3)
+    off, cnt = i32(off, "ray_rec_off").view(-1), i32(cnt, "ray_rec_cnt").view(-1)
+    rec_w = f32(rec_w, "rec_w").view(-1)
+    a = rec_w.shape[0]
+    rec_xyz, rec_brdf, rec_normal = f32(rec_xyz, "rec_xyz", 3), f32(rec_brdf, "rec_brdf", 4), f32(rec_normal, "rec_normal", 3)
+    if not (dirs.shape[0] == fallback_normal.shape[0] == off.numel() == cnt.numel() == n):
+        raise ValueError("origins, dirs, fallback_normal, ray_rec_off and ray_rec_cnt take one row per point")
+    if not (rec_xyz.shape[0] == rec_brdf.shape[0] == rec_normal.shape[0] == a):
+        raise ValueError("rec_w, rec_xyz, rec_brdf and rec_normal take one row per record")
+    box = (C.c_float * 6)(*[float(v) for v in torch.as_tensor(aabb).detach().reshape(-1).tolist()])
+    rows = torch.empty((n, BAKE_ROW), dtype=torch.float32, device=origins.device)
+    _call("tir_bake_composite", _ptr(off), _ptr(cnt), _ptr(rec_w), _ptr(rec_xyz), _ptr(rec_brdf), _ptr(rec_normal), _ptr(origins),
+          _ptr(dirs), _ptr(fallback_normal), box, n, a, _ptr(rows), _stream())
+    return rows
+
+
+def irradiance_integrate(rows, dirs, vis, env, weight_d, light_idx):
+    """tir_irradiance_integrate: rows [M, BAKE_ROW] of bake_composite, dirs [D, 3], vis [M, D], env [L, D, 3], weight_d [D],
+    light_idx [M] int32 -> [M, 4] = ambient occlusion, direct irradiance rgb."""
+    rows = f32(rows, "rows", BAKE_ROW).view(-1, BAKE_ROW)
+    dirs = f32(dirs, "dirs", 3).view(-1, 3)
+    M, D = rows.shape[0], dirs.shape[0]
+    vis = f32(vis, "vis")
+    env = f32(env, "env", 3)
+    weight_d = f32(weight_d, "light_area_weight").view(-1)
+    light_idx = i32(light_idx, "light_idx").view(-1)
+    if D == 0 or env.dim() != 3 or env.shape[1] != D or weight_d.numel() != D or vis.numel() != M * D or light_idx.numel() != M:
+        raise ValueError(f"expected vis [{M}, {D}], env [L, {D}, 3], weight_d [{D}], light_idx [{M}]")
+    out = torch.empty((M, 4), dtype=torch.float32, device=rows.device)
+    _call("tir_irradiance_integrate", _ptr(rows), _ptr(dirs), _ptr(vis), _ptr(env), _ptr(weight_d), _ptr(light_idx), M, D,
+          env.shape[0], _ptr(out), _stream())
+    return out

@@ -1,0 +1,122 @@
+"""Timing of the per-vertex bake (not part of bench.py): export_mesh(attributes=True) on the 300^3 lattice of the field
+tools/mesh_bench.py uses (the small golden checkpoint), with the default 16 x 32 light grid (D = 512 directions).
+
+    python tools/bake_bench.py [--grid 300] [--reps 3]          # one JSON line
+    rocprofv3 --kernel-trace --stats --output-format csv -d DIR -o bake -- python tools/bake_bench.py --reps 1
+    python tools/bake_bench.py --stats DIR                      # per-kernel GPU time from that trace
+
+The JSON line: geometry_ms (extract_mesh), material_ms (bake_points(lighting=False): inward march, decoders, tir_bake_composite),
+lighting_ms (the rest of bake_points: pair mask, visibility march, tir_irradiance_integrate) -- device events around the calls,
+best of --reps; export_plain_s / export_baked_s (wall clock incl. the PLY write, after a warm-up, measured in this same run: the
+yardstick for "is the bake cheap enough"); and for the two new kernels the bytes they must move, their time (events around the
+launch, summed over the chunks) and the rate as a fraction of the 6.3 TB/s HBM ceiling."""
+import argparse
+import csv
+import glob
+import json
+import os
+import sys
+import tempfile
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+HBM_TBS = 6.3
+
+
+def stats(d):
+    rows = []
+    for f in sorted(glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True)):
+        with open(f) as fh:
+            rows += list(csv.DictReader(fh))
+    out = {}
+    for r in rows:
+        name = r["Name"].replace("(anonymous namespace)::", "").split("(")[0].replace("void ", "")
+        out[name] = {"calls": int(r["Calls"]), "total_ms": float(r["TotalDurationNs"]) / 1e6, "avg_us": float(r["AverageNs"]) / 1e3}
+    top = dict(sorted(out.items(), key=lambda kv: -kv[1]["total_ms"])[:14])
+    print(json.dumps({"kernels": top, "total_ms": sum(v["total_ms"] for v in out.values())}, indent=1))
+
+
+def run(n, reps):
+    import numpy as np
+    import torch
+
+    import tensoir_amd
+    from tensoir_amd import bake, mesh, ops, relight
+    from tests.helpers import golden_checkpoint
+    g = np.load(os.path.join(ROOT, "tests", "golden", "small_scene.npz"))
+    model = tensoir_amd.model_from_checkpoint(golden_checkpoint(g), "cuda:0")
+    grid = [n, n, n]
+    D = model.fixed_viewdirs.shape[0]
+
+    def timed(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        out = fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return out, e0.elapsed_time(e1)
+
+    geo, mat, full, kern = [], [], [], []
+    for rep in range(reps + 1):                                   # the first pass warms up (record-capacity hints, tables)
+        (verts, faces, normals), t_geo = timed(lambda: mesh.extract_mesh(model, 0.005, grid))
+        pos, outward = mesh.field_positions(model.aabb, grid, verts, normals)
+        pos, outward = pos.contiguous(), outward.contiguous()
+        _, t_mat = timed(lambda: bake.bake_points(model, pos, outward, lighting=False))
+        ops.TIMING = []
+        out, t_full = timed(lambda: bake.bake_points(model, pos, outward))
+        calls, ops.TIMING = ops.TIMING, None
+        if rep:
+            geo.append(t_geo)
+            mat.append(t_mat)
+            full.append(t_full)
+            kern.append({k: sum(e0.elapsed_time(e1) for name, e0, e1 in calls if name.startswith(k))
+                         for k in ("tir_bake_composite", "tir_irradiance_integrate", "tir_march_secondary")})
+    V = int(verts.shape[0])
+    # records of the inward march: counted once more (the bake does not return them)
+    step = float(model.stepSize)
+    z = relight._z_table(96, 0.0, step * 95, pos.device)
+    n_rec = 0
+    for a in range(0, V, 16384):
+        o = (pos[a:a + 16384] + outward[a:a + 16384] * (step * 16)).contiguous()
+        rec, total = bake._march_records(model, model.packed_field(), o, (-outward[a:a + 16384]).contiguous(), z)
+        n_rec += total
+    comp_bytes = n_rec * (4 + 12 + 16 + 12) + V * (8 + 36 + 64)          # w, xyz, brdf, normal per record; off/cnt, o/d/n, row per point
+    integ_bytes = V * D * 4 + V * (64 + 4 + 16)                            # vis; row, light index, output per point
+    k = {name: min(r[name] for r in kern) for name in kern[0]}
+    with tempfile.TemporaryDirectory() as d:
+        path = os.path.join(d, "m.ply")
+        walls = {}
+        for key, kw in (("export_plain_s", {}), ("export_baked_s", {"attributes": True})):
+            mesh.export_mesh(model, path, gridSize=grid, **kw)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            mesh.export_mesh(model, path, gridSize=grid, **kw)
+            walls[key] = time.perf_counter() - t0
+            walls[key.replace("_s", "_bytes")] = os.path.getsize(path)
+    rate = lambda b, ms: b / (ms * 1e-3) / 1e12
+    print(json.dumps({
+        "grid": n, "vertices": V, "faces": int(faces.shape[0]), "directions": D, "records": n_rec,
+        "covered": float((out["coverage"] > 0.5).float().mean()),
+        "geometry_ms": min(geo), "material_ms": min(mat), "lighting_ms": min(full) - min(mat), "bake_ms": min(full), **walls,
+        "march_secondary_ms": k["tir_march_secondary"],
+        "bake_composite": {"ms": k["tir_bake_composite"], "bytes": comp_bytes, "TB_s": rate(comp_bytes, k["tir_bake_composite"]),
+                           "of_hbm": rate(comp_bytes, k["tir_bake_composite"]) / HBM_TBS},
+        "irradiance_integrate": {"ms": k["tir_irradiance_integrate"], "bytes": integ_bytes,
+                                 "TB_s": rate(integ_bytes, k["tir_irradiance_integrate"]),
+                                 "of_hbm": rate(integ_bytes, k["tir_irradiance_integrate"]) / HBM_TBS}}), flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--grid", type=int, default=300)
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--stats", default=None, help="summarise the rocprofv3 kernel stats under this directory and exit")
+    a = ap.parse_args()
+    if a.stats:
+        return stats(a.stats)
+    run(a.grid, a.reps)
+
+
+if __name__ == "__main__":
+    main()
