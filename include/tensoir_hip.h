@@ -788,6 +788,34 @@ int tir_mc_emit(const float* vol, int32_t gx, int32_t gy, int32_t gz, float leve
                 float spacing_z, float origin_x, float origin_y, float origin_z, const int32_t* offsets, int32_t n_verts,
                 int32_t n_faces, int32_t* vbase, float* verts, float* normals, int32_t* faces, void* stream);
 
+/* ---- Connected components of a dense lattice: removing detached blobs ("floaters") from the mesh and the occupancy mask.
+ *   vol [gx][gy][gz] fp32, contiguous, z fastest (the tir_mc_* layout); every dimension >= 1; at most 2^31-1 points.
+ *   inside:    vol[p] > level in fp32, the comparison of tir_mc_count (a value at `level`, or a NaN, is outside).
+ *   links:     connectivity 6 joins inside points that differ by one step along one axis (the components whose boundaries are
+ *              the closed surfaces of tir_mc_emit, whose case table separates inside corners on ambiguous faces);
+ *              connectivity 26 also joins across edges and corners.
+ *   labels [gx][gy][gz] int32: -1 where p is outside, otherwise the SMALLEST linear index ((x * gy + y) * gz + z) of any point
+ *              of p's component.  The definition fixes the output whatever order the device worked in.
+ *   table:     component k = 0 .. K-1 in ascending order of its root (the point with labels[p] == p):
+ *              roots [K], sizes [K] (voxel count), boxes [K][6] = inclusive index bounds (x0, y0, z0, x1, y1, z1), all int32.
+ *              Counts and bounds are integer atomics: exact, and bit-identical from call to call.  No float atomics anywhere.
+ * Use: nb = tir_ccl_blocks(g) (blocks of 4096 points); tir_ccl_label writes labels and, as the caller's workspace, the number of
+ * roots per block counts [nb] and its exclusive scan offsets [nb+1]; the caller reads K = offsets[nb] back, allocates roots /
+ * sizes / boxes (the call initialises them) and runs tir_ccl_table(labels, g, offsets, K, ...).  K = 0: nothing is touched.
+ * tir_ccl_filter: out[p] = vol[p] where p is outside or keep[component of p] != 0 (keep [K] bytes), else `fill`; fill <= level
+ * is required, so a removed point is an outside point of `out` (out may not alias vol).  With K = 0, out = vol.
+ * Labelling is a union-find whose links only ever point to smaller indices: inside 4 x 8 x 32 tiles in LDS, then across tile
+ * borders with device-scope atomicMin, then a flattening pass; kernel boundaries are the only global synchronisation.
+ * Every entry validates on the host before any device work: a null pointer, a connectivity other than 6 / 26, a dimension
+ * <= 0, K < 0 or fill > level (or NaN) -> TIR_ERR_ARG; more than 2^31-1 points -> TIR_ERR_UNSUPPORTED (tir_ccl_blocks too). */
+int64_t tir_ccl_blocks(int32_t gx, int32_t gy, int32_t gz);
+int tir_ccl_label(const float* vol, int32_t gx, int32_t gy, int32_t gz, float level, int32_t connectivity, int32_t* labels,
+                  int32_t* counts, int32_t* offsets, void* stream);
+int tir_ccl_table(const int32_t* labels, int32_t gx, int32_t gy, int32_t gz, const int32_t* offsets, int32_t n_comp,
+                  int32_t* roots, int32_t* sizes, int32_t* boxes, void* stream);
+int tir_ccl_filter(const float* vol, const int32_t* labels, int32_t gx, int32_t gy, int32_t gz, float level,
+                   const int32_t* roots, const uint8_t* keep, int32_t n_comp, float fill, float* out, void* stream);
+
 /* ---- per-point bake of materials and direct lighting (tensoir_amd/bake.py).  Point p is marched inward from
  * origins[p] along dirs[p] by tir_march_secondary_fwd with records; the caller decodes every record (BRDF decoder output
  * rec_brdf [A][4] = albedo rgb + raw roughness, shading normal rec_normal [A][3]).

@@ -157,6 +157,10 @@ SIGNATURES = {
     "tir_mc_blocks": (I64, [I32, I32, I32]),
     "tir_mc_count": (C.c_int, [P, I32, I32, I32, F32, P, P, P]),
     "tir_mc_emit": (C.c_int, [P, I32, I32, I32, F32, F32, F32, F32, F32, F32, F32, P, I32, I32, P, P, P, P, P]),
+    "tir_ccl_blocks": (I64, [I32, I32, I32]),
+    "tir_ccl_label": (C.c_int, [P, I32, I32, I32, F32, I32, P, P, P, P]),
+    "tir_ccl_table": (C.c_int, [P, I32, I32, I32, P, I32, P, P, P, P]),
+    "tir_ccl_filter": (C.c_int, [P, P, I32, I32, I32, F32, P, P, I32, F32, P, P]),
     "tir_bake_composite": (C.c_int, [P, P, P, P, P, P, P, P, P, C.POINTER(C.c_float), I64, I64, P, P]),
     "tir_irradiance_integrate": (C.c_int, [P, P, P, P, P, P, I64, I32, I32, P, P]),
 }

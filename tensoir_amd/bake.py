@@ -170,11 +170,22 @@ def main(argv=None):
     ap.add_argument("--color", choices=("albedo", "diffuse"), default="albedo")
     ap.add_argument("--light", type=int, default=0)
     ap.add_argument("--envmap", type=int, nargs=2, metavar=("H", "W"), default=None, help="light direction grid (default 16 32)")
+    ap.add_argument("--keep-largest", type=int, default=None, metavar="N", help="export only the N largest connected components "
+                    "of the lattice (drops detached floaters)")
+    ap.add_argument("--min-component-voxels", type=int, default=None, metavar="N", help="drop components of fewer than N lattice "
+                    "points")
+    ap.add_argument("--connectivity", type=int, choices=(6, 26), default=6, help="what joins two lattice points into one component")
     a = ap.parse_args(argv)
     extra = {} if a.envmap is None else {"envmap_h": a.envmap[0], "envmap_w": a.envmap[1]}
     model = load_model(a.ckpt, "cuda", **extra)
     grid = None if a.grid is None else [a.grid] * 3
-    nv, nf = mesh.export_mesh(model, a.out, a.level, grid, attributes=True, color=a.color, light_idx=a.light)
+    report = {}
+    nv, nf = mesh.export_mesh(model, a.out, a.level, grid, attributes=True, color=a.color, light_idx=a.light,
+                              keep_largest=a.keep_largest, min_component_voxels=a.min_component_voxels,
+                              connectivity=a.connectivity, report=report)
+    if report:
+        sizes, kept = report["table"]["sizes"].cpu(), report["kept"].cpu()
+        print(f"components: dropped {int((~kept).sum())} of {kept.numel()} ({int(sizes[~kept].sum())} of {int(sizes.sum())} voxels)")
     print(f"{a.out}: {nv} vertices, {nf} faces")
 
 

@@ -8,6 +8,9 @@
 //   k_mc_faces   block-local scan of the per-cell triangle counts: faces in (cell, table) order; a corner's vertex on the
 //                edge along `axis` is vbase[corner] + the number of its crossing edges along lower axes
 //
+// Connected components of the same lattice (contract: include/tensoir_hip.h, tir_ccl_*): the kernels and their union-find are
+// described where they start below ("connected components of {vol > level}").
+//
 // Per-vertex bake of the exported mesh (tensoir_amd/bake.py; contract: include/tensoir_hip.h, tir_bake_composite and
 // tir_irradiance_integrate): two reductions without atomics, every point summed in a fixed order.
 //   k_bake_composite        BAKE_LANES lanes per point walk its contiguous record segment of the short inward march
@@ -256,8 +259,315 @@ int64_t mc_validate(int32_t gx, int32_t gy, int32_t gz) {
     return (n + MC_BLOCK_POINTS - 1) / MC_BLOCK_POINTS;
 }
 
+// ---- connected components of {vol > level} (contract: include/tensoir_hip.h, tir_ccl_*) ---------------------------
+// Union-find whose parent links always point to a SMALLER linear index (atomicMin on the root's own slot), so a tree's root is
+// the smallest index of its set and the flattened labels do not depend on the order the unions happened in.
+//   k_ccl_local    one workgroup per CCL_TX x CCL_TY x CCL_TZ tile: union-find in LDS over the tile's own links; labels[p] =
+//                  the tile-local root as a global index (a tile index and a global index order the tile's points alike)
+//   k_ccl_merge    the links that cross a tile face / edge / corner: device-scope atomicMin union-find on labels
+//   k_ccl_flatten  labels[p] = root of p
+//   k_ccl_roots<false/true>  count per block of MC_BLOCK_POINTS points / emit in ascending order the points with labels[p] == p
+//   k_ccl_stats    voxel count and index bounding box per component: integer atomics, one set per run of equal labels per wave
+//   k_ccl_filter   out = vol where outside or kept, else fill
+// Kernel boundaries are the only global synchronisation; no workgroup waits on another.
+constexpr int CCL_TX = 4, CCL_TY = 8, CCL_TZ = 32;
+constexpr int CCL_TILE = CCL_TX * CCL_TY * CCL_TZ;        // 1024 points = 4 KB of LDS labels; z fastest as in the lattice
+constexpr int CCL_THREADS = 256;                          // thread t owns (lx = 0..3, ly = t >> 5, lz = t & 31)
+
+struct CclGrid {
+    int32_t gx, gy, gz;
+    int32_t ntx, nty, ntz;    // tiles per axis
+    int64_t n;
+};
+
+// the 13 neighbours with a smaller linear index, faces first (x, y, z): connectivity 6 takes the first three
+__constant__ int8_t ccl_back[13][3] = {{-1, 0, 0}, {0, -1, 0}, {0, 0, -1},
+                                       {-1, -1, 0}, {-1, 1, 0}, {-1, 0, -1}, {-1, 0, 1}, {0, -1, -1}, {0, -1, 1},
+                                       {-1, -1, -1}, {-1, -1, 1}, {-1, 1, -1}, {-1, 1, 1}};
+
+__device__ __forceinline__ int ccl_lds_find(const volatile int* L, int a) {
+    int q = L[a];
+    while (q != a) { a = q; q = L[a]; }
+    return a;
+}
+
+__device__ __forceinline__ void ccl_lds_union(int* L, int a, int b) {
+    for (;;) {
+        a = ccl_lds_find(L, a);
+        b = ccl_lds_find(L, b);
+        if (a == b) return;
+        if (a < b) { const int t = a; a = b; b = t; }     // a > b: hang a below b, if a is still a root
+        const int old = atomicMin(&L[a], b);
+        if (old == a) return;
+        a = old;                                          // a had already been hung below `old`: unite that with b
+    }
+}
+
+__global__ void __launch_bounds__(CCL_THREADS)
+k_ccl_local(const float* __restrict__ vol, float level, CclGrid G, int n_back, int32_t* __restrict__ labels) {
+    __shared__ int L[CCL_TILE];
+    const uint32_t b = blockIdx.x, bz = b % (uint32_t)G.ntz, br = b / (uint32_t)G.ntz;
+    const int x0 = (int)(br / (uint32_t)G.nty) * CCL_TX, y0 = (int)(br % (uint32_t)G.nty) * CCL_TY, z0 = (int)bz * CCL_TZ;
+    const int ly = threadIdx.x >> 5, lz = threadIdx.x & 31;
+    const int y = y0 + ly, z = z0 + lz;
+    const bool col = y < G.gy && z < G.gz;
+#pragma unroll
+    for (int lx = 0; lx < CCL_TX; ++lx) {
+        const int t = lx * (CCL_TY * CCL_TZ) + threadIdx.x;
+        bool in = false;
+        if (col && x0 + lx < G.gx) in = vol[((int64_t)(x0 + lx) * G.gy + y) * G.gz + z] > level;
+        L[t] = in ? t : -1;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int lx = 0; lx < CCL_TX; ++lx) {
+        const int t = lx * (CCL_TY * CCL_TZ) + threadIdx.x;
+        if (L[t] < 0) continue;
+        for (int k = 0; k < n_back; ++k) {
+            const int qx = lx + ccl_back[k][0], qy = ly + ccl_back[k][1], qz = lz + ccl_back[k][2];
+            if (qx < 0 || qy < 0 || qy >= CCL_TY || qz < 0 || qz >= CCL_TZ) continue;
+            const int q = (qx * CCL_TY + qy) * CCL_TZ + qz;
+            if (L[q] >= 0) ccl_lds_union(L, t, q);        // (never written to or from -1: outside slots stay outside)
+        }
+    }
+    __syncthreads();
+    int root[CCL_TX];
+#pragma unroll
+    for (int lx = 0; lx < CCL_TX; ++lx) {
+        const int t = lx * (CCL_TY * CCL_TZ) + threadIdx.x;
+        root[lx] = L[t] < 0 ? -1 : ccl_lds_find(L, t);
+    }
+#pragma unroll
+    for (int lx = 0; lx < CCL_TX; ++lx) {
+        if (!(col && x0 + lx < G.gx)) continue;
+        const int r = root[lx];
+        int32_t out = -1;
+        if (r >= 0) {
+            const int rx = r / (CCL_TY * CCL_TZ), ry = (r / CCL_TZ) % CCL_TY, rz = r % CCL_TZ;
+            out = (int32_t)(((int64_t)(x0 + rx) * G.gy + (y0 + ry)) * G.gz + (z0 + rz));
+        }
+        labels[((int64_t)(x0 + lx) * G.gy + y) * G.gz + z] = out;
+    }
+}
+
+// Device-scope reads of the forest: served by L2 / memory, where the atomics of other compute units land.  (A stale parent
+// would still be an ancestor -- links only ever move to smaller members of the same set -- so this is for progress, not safety.)
+__device__ __forceinline__ int32_t ccl_load(const int32_t* p) {
+    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+__device__ __forceinline__ int32_t ccl_find(const int32_t* L, int32_t a) {
+    int32_t q = ccl_load(L + a);
+    while (q != a) { a = q; q = ccl_load(L + a); }
+    return a;
+}
+
+__device__ __forceinline__ void ccl_union(int32_t* L, int32_t a, int32_t b) {
+    for (;;) {
+        a = ccl_find(L, a);
+        b = ccl_find(L, b);
+        if (a == b) return;
+        if (a < b) { const int32_t t = a; a = b; b = t; }
+        const int32_t old = __hip_atomic_fetch_min(L + a, b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (old == a) return;
+        a = old;
+    }
+}
+
+__device__ __forceinline__ void ccl_coords(const CclGrid& G, int64_t p, int& x, int& y, int& z) {
+    const uint32_t q = (uint32_t)p, r = q / (uint32_t)G.gz;
+    z = (int)(q - r * (uint32_t)G.gz);
+    x = (int)(r / (uint32_t)G.gy);
+    y = (int)(r - (uint32_t)x * (uint32_t)G.gy);
+}
+
+__global__ void __launch_bounds__(CCL_THREADS)
+k_ccl_merge(CclGrid G, int n_back, int32_t* labels) {
+    const int64_t p = (int64_t)blockIdx.x * CCL_THREADS + threadIdx.x;
+    if (p >= G.n) return;
+    int x, y, z;
+    ccl_coords(G, p, x, y, z);
+    const int lx = x % CCL_TX, ly = y % CCL_TY, lz = z % CCL_TZ;
+    // a point away from the low faces of its tile (and, with diagonal links, from the high y / z faces) has no link that
+    // leaves the tile toward a smaller index
+    if (lx > 0 && ly > 0 && lz > 0 && (n_back == 3 || (ly < CCL_TY - 1 && lz < CCL_TZ - 1))) return;
+    if (labels[p] < 0) return;
+    for (int k = 0; k < n_back; ++k) {
+        const int dx = ccl_back[k][0], dy = ccl_back[k][1], dz = ccl_back[k][2];
+        const int qx = x + dx, qy = y + dy, qz = z + dz;
+        if (qx < 0 || qy < 0 || qy >= G.gy || qz < 0 || qz >= G.gz) continue;
+        const bool same_tile = lx + dx >= 0 && ly + dy >= 0 && ly + dy < CCL_TY && lz + dz >= 0 && lz + dz < CCL_TZ;
+        if (same_tile) continue;
+        const int64_t q = ((int64_t)qx * G.gy + qy) * G.gz + qz;
+        if (ccl_load(labels + q) >= 0) ccl_union(labels, (int32_t)p, (int32_t)q);
+    }
+}
+
+// Concurrent flattening is safe: a slot is only ever overwritten by an ancestor of its point, and roots are never written.
+__global__ void __launch_bounds__(CCL_THREADS)
+k_ccl_flatten(int64_t n, int32_t* labels) {
+    const int64_t p = (int64_t)blockIdx.x * CCL_THREADS + threadIdx.x;
+    if (p >= n) return;
+    const int32_t l = labels[p];
+    if (l < 0 || l == (int32_t)p) return;
+    const int32_t r = ccl_find(labels, l);
+    if (r != l) labels[p] = r;
+}
+
+constexpr int32_t CCL_BOX_EMPTY_LO = 0x7fffffff;
+
+template <bool EMIT>
+__global__ void __launch_bounds__(MC_THREADS)
+k_ccl_roots(const int32_t* __restrict__ labels, int64_t n, int32_t* __restrict__ counts, const int32_t* __restrict__ offsets,
+            int32_t K, int32_t* __restrict__ roots, int32_t* __restrict__ sizes, int32_t* __restrict__ boxes) {
+    __shared__ int wsum[MC_THREADS / 64];
+    const int64_t base = (int64_t)blockIdx.x * MC_BLOCK_POINTS;
+    int carry = EMIT ? offsets[blockIdx.x] : 0, nr = 0;
+    for (int it = 0; it < MC_ITERS; ++it) {
+        const int64_t p = base + it * MC_THREADS + threadIdx.x;
+        const int is_root = p < n && labels[p] == (int32_t)p;
+        if constexpr (EMIT) {
+            int tot;
+            const int o = carry + mc_block_scan(is_root, wsum, &tot);
+            carry += tot;
+            if (is_root && o < K) {
+                roots[o] = (int32_t)p;
+                sizes[o] = 0;
+#pragma unroll
+                for (int a = 0; a < 3; ++a) {
+                    boxes[(int64_t)o * 6 + a] = CCL_BOX_EMPTY_LO;
+                    boxes[(int64_t)o * 6 + 3 + a] = -1;
+                }
+            }
+        } else {
+            nr += is_root;
+        }
+    }
+    if constexpr (!EMIT) {
+        nr = mc_block_sum(nr, wsum);
+        if (threadIdx.x == 0) counts[blockIdx.x] = nr;
+    }
+}
+
+// index of `label` in the ascending roots[K], or -1
+__device__ __forceinline__ int ccl_component(const int32_t* __restrict__ roots, int32_t K, int32_t label) {
+    int lo = 0, hi = K - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (roots[mid] < label) lo = mid + 1; else hi = mid;
+    }
+    return (K > 0 && roots[lo] == label) ? lo : -1;
+}
+
+struct CclAcc {
+    int32_t label, count, lo[3], hi[3];
+};
+
+// Every lane of the wave calls this together.  Lanes with `flush` hand in their run; each distinct label among them costs the
+// wave one table look-up and seven integer atomics (size, three minima, three maxima), issued by its first seven lanes.
+__device__ __forceinline__ void ccl_wave_flush(bool flush, const CclAcc& A, const int32_t* __restrict__ roots, int32_t K,
+                                               int32_t* __restrict__ sizes, int32_t* __restrict__ boxes) {
+    const int lane = threadIdx.x & 63;
+    unsigned long long todo = __ballot(flush);
+    while (todo) {
+        const int leader = __ffsll((long long)todo) - 1;
+        const int32_t lab = __shfl(A.label, leader, 64);
+        const bool mine = flush && A.label == lab;
+        todo &= ~__ballot(mine);
+        int32_t v[7];
+        v[0] = mine ? A.count : 0;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            v[1 + a] = mine ? A.lo[a] : CCL_BOX_EMPTY_LO;
+            v[4 + a] = mine ? A.hi[a] : -1;
+        }
+#pragma unroll
+        for (int s = 32; s > 0; s >>= 1) {
+            v[0] += __shfl_xor(v[0], s, 64);
+#pragma unroll
+            for (int a = 0; a < 3; ++a) {
+                v[1 + a] = min(v[1 + a], __shfl_xor(v[1 + a], s, 64));
+                v[4 + a] = max(v[4 + a], __shfl_xor(v[4 + a], s, 64));
+            }
+        }
+        const int k = ccl_component(roots, K, lab);       // wave-uniform
+        if (k < 0) continue;
+        if (lane == 0) atomicAdd(&sizes[k], v[0]);
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            if (lane == 1 + a) atomicMin(&boxes[(int64_t)k * 6 + a], v[1 + a]);
+            if (lane == 4 + a) atomicMax(&boxes[(int64_t)k * 6 + 3 + a], v[4 + a]);
+        }
+    }
+}
+
+__global__ void __launch_bounds__(MC_THREADS)
+k_ccl_stats(const int32_t* __restrict__ labels, CclGrid G, const int32_t* __restrict__ roots, int32_t K,
+            int32_t* __restrict__ sizes, int32_t* __restrict__ boxes) {
+    // a wave walks 64 * MC_ITERS consecutive points, a lane every 64th of them, and keeps the run of equal labels it is in
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int64_t base = (int64_t)blockIdx.x * MC_BLOCK_POINTS + (int64_t)wv * (64 * MC_ITERS);
+    CclAcc A;
+    A.label = -1;
+    A.count = 0;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) { A.lo[a] = CCL_BOX_EMPTY_LO; A.hi[a] = -1; }
+    for (int it = 0; it < MC_ITERS; ++it) {
+        const int64_t p = base + it * 64 + lane;
+        const int32_t l = p < G.n ? labels[p] : -1;
+        const bool change = l >= 0 && A.label >= 0 && l != A.label;
+        if (__any(change)) {
+            ccl_wave_flush(change, A, roots, K, sizes, boxes);
+            if (change) {
+                A.label = -1;
+                A.count = 0;
+#pragma unroll
+                for (int a = 0; a < 3; ++a) { A.lo[a] = CCL_BOX_EMPTY_LO; A.hi[a] = -1; }
+            }
+        }
+        if (l >= 0) {
+            int c[3];
+            ccl_coords(G, p, c[0], c[1], c[2]);
+            A.label = l;
+            A.count += 1;
+#pragma unroll
+            for (int a = 0; a < 3; ++a) { A.lo[a] = min(A.lo[a], c[a]); A.hi[a] = max(A.hi[a], c[a]); }
+        }
+    }
+    ccl_wave_flush(A.label >= 0, A, roots, K, sizes, boxes);
+}
+
+__global__ void __launch_bounds__(CCL_THREADS)
+k_ccl_filter(const float* __restrict__ vol, const int32_t* __restrict__ labels, int64_t n, const int32_t* __restrict__ roots,
+             const uint8_t* __restrict__ keep, int32_t K, float fill, float* __restrict__ out) {
+    const int64_t p = (int64_t)blockIdx.x * CCL_THREADS + threadIdx.x;
+    if (p >= n) return;
+    const int32_t l = labels[p];
+    float v = vol[p];
+    if (l >= 0) {
+        const int k = ccl_component(roots, K, l);
+        if (k < 0 || !keep[k]) v = fill;
+    }
+    out[p] = v;
+}
+
+// host-side validation of the tir_ccl_* entries: 0, or a negative TIR_ERR_*; fills the tile grid
+int ccl_validate(int32_t gx, int32_t gy, int32_t gz, CclGrid* G) {
+    if (gx <= 0 || gy <= 0 || gz <= 0) return TIR_ERR_ARG;
+    const int64_t n = (int64_t)gx * gy * gz;
+    if (n > INT32_MAX) return TIR_ERR_UNSUPPORTED;
+    G->gx = gx; G->gy = gy; G->gz = gz;
+    G->ntx = (gx + CCL_TX - 1) / CCL_TX;
+    G->nty = (gy + CCL_TY - 1) / CCL_TY;
+    G->ntz = (gz + CCL_TZ - 1) / CCL_TZ;
+    G->n = n;
+    // one workgroup per tile in a one-dimensional grid (a 1 x N x 1 lattice has N / CCL_TY tiles: always below 2^31)
+    if ((int64_t)G->ntx * G->nty * G->ntz > INT32_MAX) return TIR_ERR_UNSUPPORTED;
+    return TIR_OK;
+}
+
 // ---- per-vertex bake -------------------------------------------------------------------------------------------------------
-constexpr int BAKE_LANES = 8;          // a trained surface leaves 5-30 records per ray: 1-4 strides of the segment per lane
+constexpr int BAKE_LANES = 8;         // a trained surface leaves 5-30 records per ray: 1-4 strides of the segment per lane
 constexpr int BAKE_THREADS = 256;
 constexpr int BAKE_ROW = 16;           // floats per output row (TIR_BAKE_ROW)
 
@@ -468,6 +778,71 @@ extern "C" int tir_mc_emit(const float* vol, int32_t gx, int32_t gy, int32_t gz,
     if (n_faces == 0) return TIR_OK;
     hipLaunchKernelGGL(k_mc_faces, dim3((unsigned)nb), dim3(MC_THREADS), 0, tir_stream(stream), L, offsets + nb + 1, n_faces,
                        vbase, faces);
+    TIR_CHECK_LAUNCH();
+    return TIR_OK;
+}
+
+extern "C" int64_t tir_ccl_blocks(int32_t gx, int32_t gy, int32_t gz) {
+    CclGrid G;
+    const int rc = ccl_validate(gx, gy, gz, &G);
+    return rc ? rc : (G.n + MC_BLOCK_POINTS - 1) / MC_BLOCK_POINTS;
+}
+
+extern "C" int tir_ccl_label(const float* vol, int32_t gx, int32_t gy, int32_t gz, float level, int32_t connectivity,
+                             int32_t* labels, int32_t* counts, int32_t* offsets, void* stream) {
+    CclGrid G;
+    if (connectivity != 6 && connectivity != 26) return TIR_ERR_ARG;
+    const int rc = ccl_validate(gx, gy, gz, &G);
+    if (rc) return rc;
+    if (!vol || !labels || !counts || !offsets) return TIR_ERR_ARG;
+    const int n_back = connectivity == 6 ? 3 : 13;
+    const unsigned tiles = (unsigned)((int64_t)G.ntx * G.nty * G.ntz);
+    const unsigned pblk = (unsigned)((G.n + CCL_THREADS - 1) / CCL_THREADS);
+    const int64_t nb = (G.n + MC_BLOCK_POINTS - 1) / MC_BLOCK_POINTS;
+    hipStream_t st = tir_stream(stream);
+    hipLaunchKernelGGL(k_ccl_local, dim3(tiles), dim3(CCL_THREADS), 0, st, vol, level, G, n_back, labels);
+    TIR_CHECK_LAUNCH();
+    if (tiles > 1) {
+        hipLaunchKernelGGL(k_ccl_merge, dim3(pblk), dim3(CCL_THREADS), 0, st, G, n_back, labels);
+        TIR_CHECK_LAUNCH();
+        hipLaunchKernelGGL(k_ccl_flatten, dim3(pblk), dim3(CCL_THREADS), 0, st, G.n, labels);
+        TIR_CHECK_LAUNCH();
+    }
+    hipLaunchKernelGGL(k_ccl_roots<false>, dim3((unsigned)nb), dim3(MC_THREADS), 0, st, (const int32_t*)labels, G.n, counts,
+                       (const int32_t*)nullptr, 0, (int32_t*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr);
+    TIR_CHECK_LAUNCH();
+    return tir_exclusive_scan(counts, offsets, (int32_t)nb, stream);
+}
+
+extern "C" int tir_ccl_table(const int32_t* labels, int32_t gx, int32_t gy, int32_t gz, const int32_t* offsets, int32_t n_comp,
+                             int32_t* roots, int32_t* sizes, int32_t* boxes, void* stream) {
+    CclGrid G;
+    const int rc = ccl_validate(gx, gy, gz, &G);
+    if (rc) return rc;
+    if (!labels || !offsets || n_comp < 0) return TIR_ERR_ARG;
+    if (n_comp == 0) return TIR_OK;
+    if (!roots || !sizes || !boxes) return TIR_ERR_ARG;
+    const int64_t nb = (G.n + MC_BLOCK_POINTS - 1) / MC_BLOCK_POINTS;
+    hipStream_t st = tir_stream(stream);
+    hipLaunchKernelGGL(k_ccl_roots<true>, dim3((unsigned)nb), dim3(MC_THREADS), 0, st, labels, G.n, (int32_t*)nullptr, offsets,
+                       n_comp, roots, sizes, boxes);
+    TIR_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_ccl_stats, dim3((unsigned)nb), dim3(MC_THREADS), 0, st, labels, G, (const int32_t*)roots, n_comp, sizes,
+                       boxes);
+    TIR_CHECK_LAUNCH();
+    return TIR_OK;
+}
+
+extern "C" int tir_ccl_filter(const float* vol, const int32_t* labels, int32_t gx, int32_t gy, int32_t gz, float level,
+                              const int32_t* roots, const uint8_t* keep, int32_t n_comp, float fill, float* out, void* stream) {
+    CclGrid G;
+    if (!(fill <= level)) return TIR_ERR_ARG;             // a removed point must become an outside point (a NaN fill is one,
+    const int rc = ccl_validate(gx, gy, gz, &G);          // but a NaN here is far more likely a mistake: refused as well)
+    if (rc) return rc;
+    if (!vol || !labels || !out || n_comp < 0) return TIR_ERR_ARG;
+    if (n_comp > 0 && (!roots || !keep)) return TIR_ERR_ARG;
+    hipLaunchKernelGGL(k_ccl_filter, dim3((unsigned)((G.n + CCL_THREADS - 1) / CCL_THREADS)), dim3(CCL_THREADS), 0,
+                       tir_stream(stream), vol, labels, G.n, roots, keep, n_comp, fill, out);
     TIR_CHECK_LAUNCH();
     return TIR_OK;
 }

@@ -789,6 +789,34 @@ class TensorVMSplit(nn.Module):
         return torch.stack((xyz_min, xyz_max))
 
     @torch.no_grad()
+    def prune_alpha_mask(self, keep_largest=None, min_voxels=None, connectivity=26):
+        """Drop detached blobs ("floaters") from the occupancy mask, so that no ray marches through them any more: the
+        connected components of alphaMask.alpha_volume > 0.5 (ops.label_components) that fail mesh.select_components(table,
+        keep_largest, min_voxels) are cleared, and self.alphaMask becomes a new AlphaGridMask of the filtered volume (same aabb,
+        dtype and shape; save() / load() round-trip it like any mask).  The default connectivity is 26: the mask is a dilated,
+        coarse volume whose lookup reports a point occupied when any of the 8 voxels around it is, so diagonal contact is contact.
+        -> the component table (of the volume as stored, [gz, gy, gx]: box columns are (z0, y0, x0, z1, y1, x1)) plus "kept"
+        [K] bool.  Never called implicitly; updateAlphaMask builds the next mask from the field as before."""
+        from . import mesh
+        if connectivity not in (6, 26):
+            raise ValueError(f"connectivity: 6 or 26, not {connectivity!r}")
+        mesh.select_components({"sizes": torch.zeros(0, dtype=torch.int32)}, keep_largest, min_voxels)    # argument errors first
+        if self.alphaMask is None:
+            raise TensoirHipError("prune_alpha_mask: the model has no alpha mask (updateAlphaMask builds one)")
+        old = self.alphaMask.alpha_volume
+        vol = old.reshape(old.shape[-3:])
+        vol32 = vol.to(torch.float32).contiguous()
+        labels, table = ops.label_components(vol32, 0.5, connectivity)
+        kept = mesh.select_components(table, keep_largest, min_voxels)
+        if not bool(kept.any()):
+            raise TensoirHipError(f"prune_alpha_mask: the selection keeps none of the mask's {kept.numel()} components")
+        new = ops.keep_components(vol32, labels, table, kept, fill=0.0, level=0.5).to(old.dtype)
+        self.alphaMask = AlphaGridMask(self.device, self.alphaMask.aabb, new)
+        self._field_key = None
+        table["kept"] = kept
+        return table
+
+    @torch.no_grad()
     def filtering_rays(self, all_rays, N_samples=256, chunk=10240 * 5, bbox_only=False):
         """models/tensorBase_rotated_lights.py:781-811 -> tir_filter_rays (one wave per ray; the [chunk, N, 3] sample
         tensor of the reference is never built).  all_rays may live on the host (as in train_tensoIR.py:228)."""

@@ -1,6 +1,7 @@
 """Mesh export of a trained field: scripts/export_mesh.py:15-24 -> utils.py:164-226 (convert_sdf_samples_to_ply), on the device.
 
     verts, faces, normals = extract_mesh(model)          # dense alpha lattice -> marching cubes (tir_dense_alpha, tir_mc_*)
+    extract_mesh(model, keep_largest=1)                  # ... without the detached blobs ("floaters"): tir_ccl_* on the lattice
     export_mesh(model, "scene.ply")                      # + binary PLY, laid out as plyfile writes the reference's mesh
     export_mesh(model, "scene.ply", attributes=True)     # + per-vertex materials and direct lighting (tensoir_amd/bake.py)
 
@@ -181,23 +182,98 @@ def reference_spacing(aabb, grid):
     return ((aabb[1] - aabb[0]) / torch.tensor([float(g) for g in grid], dtype=torch.float32)).tolist()
 
 
+def select_components(table, keep_largest=None, min_voxels=None):
+    """Which components of ops.label_components' table to keep -> [K] bool on the table's device.  A host policy on the small
+    table: keep_largest=n keeps the n largest (ties go to the smaller root, i.e. the earlier row), min_voxels=m those with at
+    least m voxels; with both, a component must pass both; with neither, all are kept."""
+    for name, v, lo in (("keep_largest", keep_largest, 0), ("min_voxels", min_voxels, 0)):
+        if v is None:
+            continue
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"{name}: expected an integer or None, not {v!r}")
+        if v < lo:
+            raise ValueError(f"{name}: must be >= {lo}, not {v}")
+    sizes = torch.as_tensor(table["sizes"])
+    if sizes.dim() != 1:
+        raise ValueError(f"table['sizes']: expected [K], got {tuple(sizes.shape)}")
+    host = sizes.detach().cpu().numpy().astype(np.int64)
+    keep = np.ones(host.shape[0], dtype=bool)
+    if min_voxels is not None:
+        keep &= host >= int(min_voxels)
+    if keep_largest is not None:
+        order = np.argsort(-host, kind="stable")              # stable: equal sizes stay in root order
+        top = np.zeros_like(keep)
+        top[order[:int(keep_largest)]] = True
+        keep &= top
+    return torch.from_numpy(keep).to(sizes.device)
+
+
+def _check_component_options(keep_largest, min_component_voxels, connectivity):
+    """-> True when a component filter was asked for.  Raises before anything touches the device."""
+    if connectivity not in (6, 26):
+        raise ValueError(f"connectivity: 6 or 26, not {connectivity!r}")
+    select_components({"sizes": torch.zeros(0, dtype=torch.int32)}, keep_largest, min_component_voxels)
+    return keep_largest is not None or min_component_voxels is not None
+
+
+def _model_grid(model, gridSize):
+    return [int(g) for g in (model.gridSize if gridSize is None else gridSize)]
+
+
 @torch.no_grad()
-def extract_mesh(model, level=0.005, gridSize=None):
+def components(model, level=0.005, gridSize=None, connectivity=6):
+    """The component table of the model's alpha lattice (getDenseAlpha at gridSize, default the model's) at `level`, for
+    inspection before choosing keep_largest / min_component_voxels: ops.label_components' table plus "boxes_world" [K, 2, 3]
+    f32, the boxes in world coordinates of the TRUE lattice (spacing (aabb1 - aabb0) / (g - 1); a one-point axis sits at
+    aabb0) -- not the reference's scaled mesh coordinates (module docstring)."""
+    _check_component_options(None, None, connectivity)
+    grid = _model_grid(model, gridSize)
+    alpha, _ = ops.dense_alpha(model.packed_field(), grid, float(model.stepSize))
+    _, table = ops.label_components(alpha, level, connectivity)
+    box = model.aabb.detach().to(alpha.device, torch.float32).reshape(2, 3)
+    g = torch.tensor([float(x) for x in grid], dtype=torch.float32, device=alpha.device)
+    spacing = (box[1] - box[0]) / (g - 1).clamp(min=1.0)
+    table["boxes_world"] = box[0] + table["boxes"].to(torch.float32).view(-1, 2, 3) * spacing
+    return table
+
+
+def _filtered_alpha(alpha, level, keep_largest, min_component_voxels, connectivity):
+    """dense alpha -> (alpha without the components the selection drops, table, kept flags)."""
+    labels, table = ops.label_components(alpha, level, connectivity)
+    kept = select_components(table, keep_largest, min_component_voxels)
+    return ops.keep_components(alpha, labels, table, kept, fill=0.0, level=level), table, kept
+
+
+@torch.no_grad()
+def extract_mesh(model, level=0.005, gridSize=None, *, keep_largest=None, min_component_voxels=None, connectivity=6,
+                 report=None):
     """getDenseAlpha(gridSize) (default: the model's gridSize) -> marching cubes at `level` in the reference's coordinates
-    (module docstring).  -> (verts [V, 3] f32, faces [F, 3] i32 outward, normals [V, 3] f32), on the model's device."""
-    grid = [int(g) for g in (model.gridSize if gridSize is None else gridSize)]
+    (module docstring).  -> (verts [V, 3] f32, faces [F, 3] i32 outward, normals [V, 3] f32), on the model's device.
+    keep_largest / min_component_voxels (select_components): the lattice's components under `connectivity` that fail the
+    selection are set to 0 before marching cubes.  With connectivity 6 that removes whole closed surfaces and leaves every kept
+    vertex bit-identical.  Needs level >= 0.  With both None no labelling kernel runs."""
+    filtering = _check_component_options(keep_largest, min_component_voxels, connectivity)
+    grid = _model_grid(model, gridSize)
     alpha, _ = ops.dense_alpha(model.packed_field(), grid, float(model.stepSize))   # getDenseAlpha's alpha, no xyz lattice
+    if filtering:
+        alpha, table, kept = _filtered_alpha(alpha, level, keep_largest, min_component_voxels, connectivity)
+        if report is not None:
+            report.update(table=table, kept=kept)
     aabb = model.aabb.detach().to("cpu", torch.float32)
     return ops.marching_cubes(alpha, level, reference_spacing(aabb, grid), aabb[0].tolist())
 
 
 @torch.no_grad()
-def export_mesh(model, path, level=0.005, gridSize=None, attributes=False, color="albedo", **bake_kw):
+def export_mesh(model, path, level=0.005, gridSize=None, attributes=False, color="albedo", *, keep_largest=None,
+                min_component_voxels=None, connectivity=6, report=None, **bake_kw):
     """extract_mesh + write_ply -> (number of vertices, number of faces).
     attributes=True: the vertex element becomes ATTRIBUTE_LAYOUT -- positions (bit-identical to the plain export), the baked
     shading normal, a display colour (vertex_colors), roughness, ambient occlusion, coverage, albedo and direct irradiance of
-    bake.bake_points(model, *field_positions(...), **bake_kw); the face element is unchanged."""
-    verts, faces, normals = extract_mesh(model, level, gridSize)
+    bake.bake_points(model, *field_positions(...), **bake_kw); the face element is unchanged.
+    keep_largest / min_component_voxels / connectivity: extract_mesh's component filter (floaters are neither written nor
+    baked)."""
+    verts, faces, normals = extract_mesh(model, level, gridSize, keep_largest=keep_largest,
+                                         min_component_voxels=min_component_voxels, connectivity=connectivity, report=report)
     if not attributes:
         if bake_kw or color != "albedo":
             raise TypeError("color and the bake arguments need attributes=True")

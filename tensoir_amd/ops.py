@@ -1496,6 +1496,64 @@ def marching_cubes(vol, level, spacing=(1.0, 1.0, 1.0), origin=(0.0, 0.0, 0.0)):
     return verts, faces, normals
 
 
+def _lattice(vol, name="vol"):
+    vol = f32(vol, name)
+    if vol.dim() != 3:
+        raise ValueError(f"{name}: expected [gx, gy, gz], got {tuple(vol.shape)}")
+    return vol
+
+
+def label_components(vol, level, connectivity=6):
+    """Connected components of {vol > level} on a dense lattice vol [gx, gy, gz] (tir_ccl_label + tir_ccl_table; contract:
+    include/tensoir_hip.h).  connectivity 6 (faces) or 26 (faces, edges, corners).
+    -> (labels [gx, gy, gz] int32: -1 outside, else the smallest linear index of the point's component,
+        table {"roots" [K] int32 ascending, "sizes" [K] int32 voxel counts, "boxes" [K, 6] int32 inclusive (x0, y0, z0, x1, y1,
+        z1)}), all on vol's device.  K is read back once (4 bytes, one sync); K = 0 gives zero-row tensors."""
+    vol = _lattice(vol)
+    if connectivity not in (6, 26):
+        raise ValueError(f"connectivity: 6 or 26, not {connectivity!r}")
+    gx, gy, gz = vol.shape
+    nb = int(lib().tir_ccl_blocks(gx, gy, gz))
+    if nb < 0:
+        check(nb, "tir_ccl_blocks")
+    dev = vol.device
+    labels = torch.empty((gx, gy, gz), dtype=torch.int32, device=dev)
+    counts = torch.empty((nb,), dtype=torch.int32, device=dev)
+    offsets = torch.empty((nb + 1,), dtype=torch.int32, device=dev)
+    _call("tir_ccl_label", _ptr(vol), gx, gy, gz, float(level), int(connectivity), _ptr(labels), _ptr(counts), _ptr(offsets),
+          _stream())
+    K = int(offsets[nb].item())
+    roots = torch.empty((K,), dtype=torch.int32, device=dev)
+    sizes = torch.empty((K,), dtype=torch.int32, device=dev)
+    boxes = torch.empty((K, 6), dtype=torch.int32, device=dev)
+    _call("tir_ccl_table", _ptr(labels), gx, gy, gz, _ptr(offsets), K, _ptr(roots if K else None), _ptr(sizes if K else None),
+          _ptr(boxes if K else None), _stream())
+    return labels, {"roots": roots, "sizes": sizes, "boxes": boxes}
+
+
+def keep_components(vol, labels, table, keep, fill=0.0, level=None):
+    """tir_ccl_filter: a new lattice equal to vol where the point is outside or its component is kept (keep [K] bool, in the
+    table's order), `fill` elsewhere.  level (optional): the level `labels` was made at -- fill must not exceed it, so that a
+    removed point is an outside point of the result; without it the call checks fill <= fill only (nothing)."""
+    vol = _lattice(vol)
+    labels = i32(labels, "labels")
+    if labels.shape != vol.shape or labels.device != vol.device:
+        raise ValueError("labels: expected the shape and device of vol")
+    roots = i32(table["roots"], "table['roots']").view(-1)
+    K = roots.shape[0]
+    keep = torch.as_tensor(keep)
+    if keep.dtype != torch.bool:
+        raise TypeError(f"keep: expected torch.bool, got {keep.dtype}")
+    keep = keep.to(vol.device).contiguous().view(-1)          # a [K] flag row: the selection is a host policy (mesh.py)
+    if keep.shape[0] != K:
+        raise ValueError(f"keep: expected [{K}] flags, got {tuple(keep.shape)}")
+    gx, gy, gz = vol.shape
+    out = torch.empty_like(vol)
+    _call("tir_ccl_filter", _ptr(vol), _ptr(labels), gx, gy, gz, float(fill if level is None else level), _ptr(roots if K else None),
+          _ptr(keep if K else None), K, float(fill), _ptr(out), _stream())
+    return out
+
+
 # ---- per-point bake (tensoir_amd/bake.py) ---------------------------------------------------------
 BAKE_ROW = 16
 
