@@ -73,6 +73,13 @@ typedef struct TirField {
      * keeps no settable state and reads no environment variable, so two embedders in one process cannot disturb each other. */
     int32_t tune_lds_lines;  /* secondary march with the density lines staged in LDS: 0 = default (on), 1 = on, 2 = off */
     int32_t tune_xcd_order;  /* contiguous per-XCD work ranges in the gathers / secondary march: 0 = default (off), 1 = on, 2 = off */
+    /* Optional dense density-feature volume (tir_dense_sigma_build): V[z][y][x] = the VM density feature at grid corner
+     * (x, y, z), fp32, x fastest, rows of dense_pitch >= grid[0] + 1 floats (the element behind a row's last corner is 0).
+     * Inside a grid cell the VM feature is multilinear, so the trilinear lookup of V equals it in real arithmetic (fp32
+     * results differ in the last bits).  The secondary march reads V instead of the 18 VM taps when it is given;
+     * NULL / 0 (a zeroed descriptor) = no volume, the VM kernels run.  The caller rebuilds V when the field changes. */
+    const float* dense_sigma;
+    int32_t dense_pitch;
 } TirField;
 
 /* fp16 shadow of the appearance planes / lines (same channel-last element order as TirField::aplane / aline; 16-byte aligned),
@@ -155,6 +162,15 @@ int tir_alpha_pool(const float* alpha, int32_t gx, int32_t gy, int32_t gz, float
                    int32_t* bbox, void* stream);
 int tir_filter_rays(const TirField* f, const float* rays, int64_t n, int32_t n_samples, int32_t bbox_only,
                     uint8_t* mask, void* stream);
+
+/* ---- dense density-feature volume (TirField::dense_sigma).
+ *      tir_dense_sigma_build: vol [grid z][grid y][pitch] (pitch >= grid x + 1, at most 4 GB) receives the VM density
+ *      feature at every grid corner: the sum over the 3 * n_dcomp plane x line products accumulated in fp64 and rounded
+ *      to fp32 once; elements [grid x, pitch) of every row are set to 0.  f->dense_sigma is not read.
+ *      tir_dense_sigma_fwd: tir_vm_density_fwd through the trilinear lookup of f->dense_sigma (the secondary march's
+ *      arithmetic; UNSUPPORTED without a volume).  Out-of-range corners carry weight 0 as in the VM gather. */
+int tir_dense_sigma_build(const TirField* f, float* vol, int32_t pitch, void* stream);
+int tir_dense_sigma_fwd(const TirField* f, const float* xyz, float* feat, float* sigma, int64_t n, void* stream);
 
 /* ---- K6: analytic d sigma/d xyz and derived normal -normalize(grad, eps=1e-6)
  *      (compute_derived_normals models/tensorBase_rotated_lights.py:839-856 ->
@@ -421,7 +437,9 @@ int tir_composite_primary_fused(const float* rays, const int32_t* offsets, const
  *      (contiguously per ray, in sample order; ray segments in arbitrary order) to rec_* (capacity rec_cap records;
  *      overflowing rays are dropped; rec_counter[0] still counts them = the capacity a re-run needs, rec_counter[1] =
  *      length of the record prefix that was actually written -- the row count consumers may process) and
- *      ray_rec_off[p] / ray_rec_cnt[p] locate ray p's segment.  stats: as tir_march_primary_fwd. */
+ *      ray_rec_off[p] / ray_rec_cnt[p] locate ray p's segment.  stats: as tir_march_primary_fwd.
+ *      With f->dense_sigma set the density feature comes from the trilinear lookup of that volume (any n_dcomp; with
+ *      records n_sample <= 96, else the VM kernels run): same results up to the fp32 rounding of the feature. */
 int tir_march_secondary_fwd(const TirField* f, const float* origins, const int32_t* org_map,
                             const float* dirs, const int32_t* dir_map, const uint8_t* active,
                             int64_t n_rays, int32_t n_dirs, int32_t n_sample, const float* z_vals,

@@ -30,6 +30,7 @@ class TirField(C.Structure):
         ("occ_dim", C.c_int32 * 3), ("occ_aabb_min", C.c_float * 3), ("occ_inv", C.c_float * 3),
         ("occ_lo", C.c_float * 3), ("occ_hi", C.c_float * 3),
         ("tune_lds_lines", C.c_int32), ("tune_xcd_order", C.c_int32),
+        ("dense_sigma", C.c_void_p), ("dense_pitch", C.c_int32),
     ]
 
 
@@ -72,6 +73,8 @@ SIGNATURES = {
     "tir_dense_alpha": (C.c_int, [C.POINTER(TirField), P, P, P, I32, I32, I32, F32, P, P]),
     "tir_alpha_pool": (C.c_int, [P, I32, I32, I32, F32, P, P, P]),
     "tir_filter_rays": (C.c_int, [C.POINTER(TirField), P, I64, I32, I32, P, P]),
+    "tir_dense_sigma_build": (C.c_int, [C.POINTER(TirField), P, I32, P]),
+    "tir_dense_sigma_fwd": (C.c_int, [C.POINTER(TirField), P, P, P, I64, P]),
     "tir_density_grad_fwd": (C.c_int, [C.POINTER(TirField), P, P, P, P, I64, P, P]),
     "tir_density_feat_grad_fwd": (C.c_int, [C.POINTER(TirField), P, P, P, I64, P]),
     "tir_vm_app_fwd": (C.c_int, [C.POINTER(TirField), P, P, P, P, P, I32, I32, I64, P, P]),

@@ -109,7 +109,7 @@ def bake_points(model, points, outward, light_idx=0, n_sample=96, n_outside=16, 
     if int(chunk) < 1:
         raise ValueError("chunk must be positive")
     dev, N = pts.device, pts.shape[0]
-    f = model.packed_field()
+    f = model.packed_field_dense()          # inference: the marches read the dense density volume where there is one
     li = light_idx if torch.is_tensor(light_idx) else torch.full((N,), int(light_idx), dtype=torch.int32)
     li = ops.to_device(li.reshape(-1), dev, torch.int32).contiguous()
     if li.numel() != N:

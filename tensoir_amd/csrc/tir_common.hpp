@@ -65,6 +65,13 @@ static inline bool tir_app_index_ok(const TirField* f) {
     return true;
 }
 
+// the dense density-feature volume is addressed with 32-bit BYTE offsets formed by 24-bit multiplies (tir::dense_feature)
+static inline bool tir_dense_sigma_ok(const TirField* f) {
+    if (!f->dense_sigma || f->dense_pitch <= f->grid[0]) return false;
+    const int64_t Y = f->grid[1], Z = f->grid[2], pb = (int64_t)f->dense_pitch * 4;
+    return f->grid[0] >= 2 && Y >= 1 && Z >= 1 && Y * Z < (1 << 24) && pb < (1 << 24) && Y * Z * pb < ((int64_t)1 << 32);
+}
+
 // matMode / vecMode of the reference (models/tensorBase_rotated_lights.py:398-399)
 __device__ __constant__ const int kMat0[3] = {0, 0, 1};
 __device__ __constant__ const int kMat1[3] = {1, 2, 2};
@@ -527,6 +534,36 @@ __device__ __forceinline__ unsigned mad_u24(unsigned a, unsigned b, unsigned c) 
     return r;
 }
 
+// ---- density feature from the dense volume (TirField::dense_sigma, built by tir_dense_sigma_build): V[z][y][x] is the VM
+// feature at grid corner (x, y, z).  Every axis of the VM gather uses ONE tap pair for its planes and its line, so inside a
+// cell the feature is multilinear in (x, y, z): the trilinear lookup of V with make_tap_q's taps (same fractions, same zero
+// weights for out-of-range corners) equals it in real arithmetic.  One lane per sample, four 8-byte loads (the x pair of
+// each (y, z) corner row; rows have one spare element, so the pair behind the last corner is loadable and carries weight 0),
+// 14 multiply / FMA.  32-bit byte offsets with the 24-bit multiplier: grid y * grid z and the row bytes are below 2^24 and
+// the volume below 4 GB (tir_dense_sigma_ok).
+typedef float tir_f2u __attribute__((ext_vector_type(2), aligned(4)));     // an x pair starts at any element
+
+__device__ __forceinline__ tir_f2 ld2b(const float* base, unsigned byte_off) {
+    const tir_f2u v = *reinterpret_cast<const tir_f2u*>(reinterpret_cast<const char*>(base) + byte_off);
+    return tir_f2{v.x, v.y};
+}
+
+__device__ __forceinline__ float dense_feature(const TirField& f, float x, float y, float z) {
+    const TapQ tx = make_tap_q(x, f.grid[0]), ty = make_tap_q(y, f.grid[1]), tz = make_tap_q(z, f.grid[2]);
+    // the pair read at the clamped i0 is (i0, i0 + 1) -- except for i0 == -1 (clamped i1 == 0), where it is (i1, i1 + 1)
+    const bool below = tx.i1 == 0u;
+    const float wx0 = below ? tx.w.y : tx.w.x, wx1 = below ? 0.0f : tx.w.y;
+    const unsigned pb = (unsigned)f.dense_pitch * 4u, xo = tx.i0 * 4u;
+    const unsigned z0 = mul_u24(tz.i0, (unsigned)f.grid[1]), z1 = mul_u24(tz.i1, (unsigned)f.grid[1]);
+    const tir_f2 v00 = ld2b(f.dense_sigma, mad_u24(z0 + ty.i0, pb, xo));
+    const tir_f2 v01 = ld2b(f.dense_sigma, mad_u24(z0 + ty.i1, pb, xo));
+    const tir_f2 v10 = ld2b(f.dense_sigma, mad_u24(z1 + ty.i0, pb, xo));
+    const tir_f2 v11 = ld2b(f.dense_sigma, mad_u24(z1 + ty.i1, pb, xo));
+    const float a = fmaf(v00.y, wx1, v00.x * wx0), b = fmaf(v01.y, wx1, v01.x * wx0);
+    const float c = fmaf(v10.y, wx1, v10.x * wx0), d = fmaf(v11.y, wx1, v11.x * wx0);
+    const float e = fmaf(b, ty.w.y, a * ty.w.x), g = fmaf(d, ty.w.y, c * ty.w.x);
+    return fmaf(g, tz.w.y, e * tz.w.x);
+}
 // 32-bit LDS addresses (device code only: the host pass of hipcc parses these bodies too and has no address space 3)
 __device__ __forceinline__ unsigned lds_addr(const float* p) {
 #if defined(__HIP_DEVICE_COMPILE__)

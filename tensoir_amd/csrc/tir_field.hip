@@ -238,6 +238,71 @@ extern "C" int tir_dense_alpha(const TirField* f, const float* lin_x, const floa
     return TIR_OK;
 }
 
+// ------------------------------------------------------------------------------------------------
+// Dense density-feature volume (TirField::dense_sigma): vol[z][y][x] = sum_i sum_c plane_i,c(corner) * line_i,c(corner),
+// the VM feature at grid corner (x, y, z).  One thread per element, x fastest (the plane taps of neighbouring threads
+// are neighbouring texels).  The 3 * n_dcomp products are exact in fp64 and are accumulated in fp64 (plane 0, 1, 2; channels
+// in order), then rounded to fp32 ONCE.  Elements [grid x, pitch) of a row are 0: the x pair behind the last corner.
+// ------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256)
+k_dense_sigma_build(TirField f, float* __restrict__ vol, int pitch) {
+    const int X = f.grid[0], Y = f.grid[1], Z = f.grid[2], C = f.n_dcomp;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (int64_t)pitch * Y * Z) return;
+    const int x = (int)(i % pitch), y = (int)((i / pitch) % Y), z = (int)(i / ((int64_t)pitch * Y));
+    double acc = 0.0;
+    if (x < X) {
+        // plane i is [grid[m1]][grid[m0]][C] with (m0, m1) = (x, y), (x, z), (y, z); line i runs along z, y, x
+        const float* const pl[3] = {f.dplane[0] + ((size_t)y * X + x) * C, f.dplane[1] + ((size_t)z * X + x) * C,
+                                    f.dplane[2] + ((size_t)z * Y + y) * C};
+        const float* const ln[3] = {f.dline[0] + (size_t)z * C, f.dline[1] + (size_t)y * C, f.dline[2] + (size_t)x * C};
+#pragma unroll
+        for (int p = 0; p < 3; ++p)
+            for (int c = 0; c < C; c += 4) {
+                const float4 a = ld4(pl[p] + c), b = ld4(ln[p] + c);
+                acc = fma((double)a.x, (double)b.x, acc);
+                acc = fma((double)a.y, (double)b.y, acc);
+                acc = fma((double)a.z, (double)b.z, acc);
+                acc = fma((double)a.w, (double)b.w, acc);
+            }
+    }
+    vol[i] = (float)acc;
+}
+
+extern "C" int tir_dense_sigma_build(const TirField* f, float* vol, int32_t pitch, void* stream) {
+    int rc = check_field(f);
+    if (rc) return rc;
+    if (!vol || pitch <= f->grid[0]) return TIR_ERR_ARG;
+    TirField g = *f;
+    g.dense_sigma = vol; g.dense_pitch = pitch;
+    if (!tir_dense_sigma_ok(&g)) return TIR_ERR_UNSUPPORTED;
+    const int64_t n = (int64_t)pitch * f->grid[1] * f->grid[2];
+    hipLaunchKernelGGL(k_dense_sigma_build, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, tir_stream(stream), *f, vol, (int)pitch);
+    TIR_CHECK_LAUNCH();
+    return TIR_OK;
+}
+
+// tir_vm_density_fwd through the volume: one point per lane, the arithmetic of the dense secondary march
+__global__ void __launch_bounds__(256)
+k_dense_sigma_fwd(TirField f, const float* __restrict__ xyz, float* __restrict__ feat, float* __restrict__ sigma, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float v = dense_feature(f, xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]);
+    if (feat) feat[i] = v;
+    if (sigma) sigma[i] = feature2density(f, v);
+}
+
+extern "C" int tir_dense_sigma_fwd(const TirField* f, const float* xyz, float* feat, float* sigma, int64_t n, void* stream) {
+    int rc = check_field(f);
+    if (rc) return rc;
+    if (n < 0 || (n > 0 && !xyz)) return TIR_ERR_ARG;
+    if (!tir_dense_sigma_ok(f)) return TIR_ERR_UNSUPPORTED;
+    if (n == 0) return TIR_OK;
+    hipLaunchKernelGGL(k_dense_sigma_fwd, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, tir_stream(stream), *f, xyz, feat, sigma, n);
+    TIR_CHECK_LAUNCH();
+    return TIR_OK;
+}
+
 extern "C" int tir_alpha_pool(const float* alpha, int32_t gx, int32_t gy, int32_t gz, float thres, float* vol,
                               int32_t* bbox, void* stream) {
     if (!alpha || !vol || gx <= 0 || gy <= 0 || gz <= 0) return TIR_ERR_ARG;

@@ -701,9 +701,14 @@ k_march_secondary(TirField f, const float* __restrict__ origins, const int32_t* 
 
 // NT = 512 (two blocks per CU while lines + scratch fit 80 KB: R <= ~370) or 1024 (one block per CU, e.g. the 400^3 field
 // of the ficus config: 76.8 KB of lines); RPB = NT / 8 rays per batch.
-template <int C4, int NSTEP, int NT, bool REC>
-__global__ void __launch_bounds__(NT, 4)
-k_march_secondary_lds(TirField f, const float* __restrict__ origins_a, const int32_t* __restrict__ org_map_a,
+//
+// DENSE: the same march with the density feature from the dense volume (TirField::dense_sigma, tir::dense_feature) instead
+// of the VM gather: the lane that holds a valid sample looks it up itself -- no staged lines, no tap records, no gather
+// passes.  Everything around the feature (cull, activation, transmittance scan, early stop, records, stats) is this one
+// body, so the two routes cannot drift apart; results agree to fp32 rounding of the feature, not bit for bit.
+template <int C4, int NSTEP, int NT, bool REC, bool DENSE>
+__device__ __forceinline__ void
+march_secondary_body(const TirField& f, const float* __restrict__ origins_a, const int32_t* __restrict__ org_map_a,
                       const float* __restrict__ dirs_a, const int32_t* __restrict__ dir_map_a,
                       const uint8_t* __restrict__ active_a, int64_t n_rays, int n_dirs, int n_sample,
                       const float* __restrict__ z_vals, float t_stop, float* __restrict__ vis_a,
@@ -713,12 +718,13 @@ k_march_secondary_lds(TirField f, const float* __restrict__ origins_a, const int
                       unsigned long long* __restrict__ stats_a, int xcd_on, const int32_t* __restrict__ ray_ids_a,
                       const int32_t* __restrict__ n_ids_dev, int line_floats) {
     constexpr int RPB = NT / 8, NHW = NT / 32;                  // rays per batch, half-waves per block
+    constexpr int SCRATCH = DENSE ? 0 : (NT / 64) * (64 * TIR_TAPREC);   // gather scratch of the VM route (floats)
     extern __shared__ __attribute__((aligned(16))) float sl_lds[];
-    float* ll = sl_lds;                                         // [line 0 | line 1 | line 2]
+    float* ll = sl_lds;                                         // [line 0 | line 1 | line 2]   (DENSE: line_floats == 0)
     const int nz = (n_sample + 3) & ~3;
     float* zt = sl_lds + line_floats;
     float* ws = zt + nz + (threadIdx.x >> 6) * (64 * TIR_TAPREC); // this wave's gather scratch: 64 tap records
-    int* s_cnt = reinterpret_cast<int*>(zt + nz + (NT / 64) * (64 * TIR_TAPREC));
+    int* s_cnt = reinterpret_cast<int*>(zt + nz + SCRATCH);
     int* s_base = s_cnt + RPB;
     int* s_pid = s_base + RPB;
     __shared__ int s_wtot[2], s_bb, s_fits;
@@ -737,12 +743,14 @@ k_march_secondary_lds(TirField f, const float* __restrict__ origins_a, const int
                                           {f.occ_lo[0], f.occ_lo[1], f.occ_lo[2]}, {f.occ_hi[0], f.occ_hi[1], f.occ_hi[2]}};
     const bool stats = stats_a != nullptr;
     {   // stage the line factors (coalesced 16-B copies; lines are [R][16] rows, contiguous)
-        int off = 0;
-        for (int i = 0; i < 3; ++i) {
-            const int nf = f.grid[2 - i] * (C4 * 4);
-            for (int e = threadIdx.x * 4; e < nf; e += NT * 4)
-                *reinterpret_cast<float4*>(ll + off + e) = *reinterpret_cast<const float4*>(f.dline[i] + e);
-            off += nf;
+        if constexpr (!DENSE) {
+            int off = 0;
+            for (int i = 0; i < 3; ++i) {
+                const int nf = f.grid[2 - i] * (C4 * 4);
+                for (int e = threadIdx.x * 4; e < nf; e += NT * 4)
+                    *reinterpret_cast<float4*>(ll + off + e) = *reinterpret_cast<const float4*>(f.dline[i] + e);
+                off += nf;
+            }
         }
         for (int i = threadIdx.x; i < n_sample; i += NT) zt[i] = z_vals[i];
     }
@@ -830,7 +838,9 @@ k_march_secondary_lds(TirField f, const float* __restrict__ origins_a, const int
                             float pz = add_rn(o[2], mul_rn(d[2], z));
                             valid = sample_valid(f, px, py, pz, x, y, zz);
                         }
-                        const float sigma = wave_sigma_lds<C4>(f, ll, valid, x, y, zz, ws);
+                        float sigma = 0.0f;
+                        if constexpr (DENSE) { if (valid) sigma = feature2density(f, dense_feature(f, x, y, zz)); }
+                        else sigma = wave_sigma_lds<C4>(f, ll, valid, x, y, zz, ws);
                         float w = 0.0f, v = 1.0f;
                         if (on) {
                             float dist = (k + 1 < n_sample) ? sub_rn(zt[k + 1], z) : 0.0f;
@@ -946,6 +956,32 @@ k_march_secondary_lds(TirField f, const float* __restrict__ origins_a, const int
     if (stats && hl == 0 && n_gather) atomicAdd(s_park.stats, (unsigned long long)n_gather);
 }
 
+#define TIR_SEC_KERNEL_PARAMS                                                                                                  \
+    TirField f, const float* __restrict__ origins, const int32_t* __restrict__ org_map, const float* __restrict__ dirs,       \
+    const int32_t* __restrict__ dir_map, const uint8_t* __restrict__ active, int64_t n_rays, int n_dirs, int n_sample,        \
+    const float* __restrict__ z_vals, float t_stop, float* __restrict__ vis, float* __restrict__ one_minus_acc,               \
+    int32_t* __restrict__ rec_counter, int64_t rec_cap, int32_t* __restrict__ rec_ray, float* __restrict__ rec_w,             \
+    float* __restrict__ rec_xyz, int32_t* __restrict__ ray_rec_off, int32_t* __restrict__ ray_rec_cnt,                        \
+    unsigned long long* __restrict__ stats, int xcd_on, const int32_t* __restrict__ ray_ids, const int32_t* __restrict__ n_ids_dev
+#define TIR_SEC_KERNEL_ARGS                                                                                                    \
+    f, origins, org_map, dirs, dir_map, active, n_rays, n_dirs, n_sample, z_vals, t_stop, vis, one_minus_acc, rec_counter,    \
+    rec_cap, rec_ray, rec_w, rec_xyz, ray_rec_off, ray_rec_cnt, stats, xcd_on, ray_ids, n_ids_dev
+
+template <int C4, int NSTEP, int NT, bool REC>
+__global__ void __launch_bounds__(NT, 4)
+k_march_secondary_lds(TIR_SEC_KERNEL_PARAMS, int line_floats) {
+    march_secondary_body<C4, NSTEP, NT, REC, false>(TIR_SEC_KERNEL_ARGS, line_floats);
+}
+
+// The dense route: 512-thread blocks as above (64 rays per batch, one record reservation each); its LDS is the z table and
+// the per-batch bookkeeping (~2.5 KB), so the registers alone set the occupancy: TIR_DENSE_WAVES waves per SIMD.
+#define TIR_DENSE_WAVES 6
+template <int NSTEP, bool REC>
+__global__ void __launch_bounds__(512, TIR_DENSE_WAVES)
+k_march_secondary_dense(TIR_SEC_KERNEL_PARAMS) {
+    march_secondary_body<1, NSTEP, 512, REC, true>(TIR_SEC_KERNEL_ARGS, 0);
+}
+
 
 extern "C" int tir_march_secondary_fwd(const TirField* f, const float* origins, const int32_t* org_map,
                                        const float* dirs, const int32_t* dir_map, const uint8_t* active,
@@ -977,6 +1013,25 @@ extern "C" int tir_march_secondary_ids_fwd(const TirField* f, const float* origi
     if (!(f->n_dcomp == 4 || f->n_dcomp == 8 || f->n_dcomp == 16 || f->n_dcomp == 32)) return TIR_ERR_UNSUPPORTED;
     if (!tir_occ_index_ok(f) || !tir_plane_index_ok(f)) return TIR_ERR_UNSUPPORTED;
     const int xcd_on = tir_xcd_mapping(f);
+    // dense density-feature volume given (inference passes of a model whose field is fixed): any component count; records up
+    // to 96 samples per ray (weights in registers), visibility-only up to TIR_SEC_MAX_SAMPLES
+    if (tir_dense_sigma_ok(f) && (n_sample <= 96 || !rec_counter)) {
+        const int64_t n_batches = (n_rays + 63) / 64;
+        unsigned nblk = (unsigned)std::min<int64_t>(n_batches, (TIR_DENSE_WAVES / 2) * 256);
+        if (xcd_on) nblk = (nblk + 7) / 8 * 8;
+        const size_t lds = ((size_t)((n_sample + 3) & ~3) + 3 * 64) * sizeof(float);
+#define TIR_LAUNCH_SEC_DENSE(NSTEP_, REC_)                                                                                  \
+        hipLaunchKernelGGL((k_march_secondary_dense<NSTEP_, REC_>), dim3(nblk), dim3(512), lds, tir_stream(stream), *f,     \
+                           origins, org_map, dirs, dir_map, active, n_rays, n_dirs, n_sample, z_vals, t_stop, vis,          \
+                           one_minus_acc, rec_counter, rec_cap, rec_ray, rec_w, rec_xyz, ray_rec_off, ray_rec_cnt, stats,   \
+                           xcd_on, ray_ids, n_ids_dev)
+        if (rec_counter) TIR_LAUNCH_SEC_DENSE(3, true);
+        else if (n_sample <= 96) TIR_LAUNCH_SEC_DENSE(3, false);
+        else TIR_LAUNCH_SEC_DENSE(8, false);
+#undef TIR_LAUNCH_SEC_DENSE
+        TIR_CHECK_LAUNCH();
+        return TIR_OK;
+    }
     // LDS-staged line factors: 16 density components, <= 96 samples per ray, lines + scratch within half a CU's LDS
     {
         const int64_t line_floats = (int64_t)(f->grid[0] + f->grid[1] + f->grid[2]) * f->n_dcomp;

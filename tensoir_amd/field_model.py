@@ -675,6 +675,58 @@ class TensorVMSplit(nn.Module):
         key walk over the parameters is not repeated)."""
         return self._field_cache.get("half_range") if self.packed_field_half(_fresh) is not None else None
 
+    def packed_field_dense(self, _fresh=False):
+        """packed_field() with the dense density-feature volume attached (TirField.dense_sigma) -- the descriptor of the
+        INFERENCE secondary marches (relight._secondary outside a training pass, the relighting visibility marches, the bake);
+        training passes keep packed_field(): the field changes every step there and a rebuild costs about what it saves.
+        The volume (4 (X+1) Y Z bytes) is built with one launch and cached with the packed field under the same key: any
+        optimizer step, upsample, shrink or load drops it.  Switched off (TENSOIR_DENSE_SIGMA=0), above the size cap
+        (TENSOIR_DENSE_SIGMA_MAX_MB), beyond the kernel's 32-bit addressing or when the allocation fails there is no volume
+        and this IS packed_field(): the choice depends on the model and the switches only, never on the call history
+        (dense_sigma_state() reports it).  _fresh: the caller has just called packed_field()."""
+        if not _fresh:
+            self.packed_field()
+        keep = self._field_cache
+        sel = (ops.TUNE["dense_sigma"], ops.TUNE["dense_sigma_max_mb"])
+        ent = keep.get("dense")
+        if ent is None or ent["sel"] != sel:
+            if torch.cuda.is_current_stream_capturing():
+                raise TensoirHipError("graph capture needs the dense density volume of the current field (run the pass eagerly first)")
+            ent = keep["dense"] = self._build_dense(keep, sel)
+        if ops.CAPTURE_KEEPALIVE is not None and ent["vol"] is not None:
+            ops.CAPTURE_KEEPALIVE.append(ent["vol"])        # a captured march bakes the volume's address
+        return ent["desc"]
+
+    @staticmethod
+    def _build_dense(keep, sel):
+        f = keep["desc"]
+        X, Y, Z = [int(g) for g in f.grid]
+        nbytes = 4 * (X + 1) * Y * Z
+        ent = {"sel": sel, "desc": f, "vol": None, "mb": nbytes / 2 ** 20, "why": None}
+        if not sel[0]:
+            ent["why"] = "switched off"
+        elif nbytes > sel[1] * 2 ** 20:
+            ent["why"] = "above the size cap"
+        elif Y * Z >= 1 << 24 or 4 * (X + 1) >= 1 << 24 or nbytes >= 1 << 32:
+            ent["why"] = "beyond 32-bit addressing"
+        else:
+            try:
+                vol, pitch = ops.dense_sigma_build(f, keep["dp0"].device)
+            except torch.cuda.OutOfMemoryError:
+                ent["why"] = "allocation failed"
+                return ent
+            g = TirField.from_buffer_copy(f)
+            g.dense_sigma, g.dense_pitch = vol.data_ptr(), pitch
+            ent["desc"], ent["vol"] = g, vol
+        return ent
+
+    def dense_sigma_state(self):
+        """Whether the inference secondary marches of this model read the dense density volume: {"on": bool, "why": reason
+        when off, "mb": its size} (builds the volume if the current field has none yet)."""
+        self.packed_field_dense()
+        ent = self._field_cache["dense"]
+        return {"on": ent["vol"] is not None, "why": ent["why"], "mb": ent["mb"]}
+
     def indirect_precision(self):
         """What the indirect-light precision policy decided for this model so far (ops.INDIRECT_GUARD, relight._indirect_mode):
         {"policy": auto|f16|full, "mode": f16|full|None, "why": ..., "probe": {...}} -- also written into checkpoints."""

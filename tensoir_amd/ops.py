@@ -28,9 +28,14 @@ TIMING = None
 #   TIR_XCD=1             contiguous per-XCD work ranges in the gathers / the march   -> TirField.tune_xcd_order = 1
 #   TENSOIR_MLP_GRID=n    persistent workgroups of a decoder launch (default 256)     -> TirMlp.tune_grid = n
 #   TIR_PAIR_ORDER=m      point-major secondary pair list (default direction-major)   -> tir_shade_setup_compact(pair_order = 2)
+#   TENSOIR_DENSE_SIGMA=0 inference secondary marches without the dense density volume -> TirField.dense_sigma = NULL
+#   TENSOIR_DENSE_SIGMA_MAX_MB=n   largest dense density volume that is built (default 1024; 300^3 needs 108 MB, 400^3 257 MB)
+# (the dense volume is the one option that is not bit-neutral: the march's density feature differs in its last fp32 bits)
 TUNE = {
     "lds_lines": 2 if os.environ.get("TENSOIR_LDS_LINES", "1") == "0" else 0,
     "xcd_order": 1 if os.environ.get("TIR_XCD", "0") == "1" else 0,
+    "dense_sigma": 0 if os.environ.get("TENSOIR_DENSE_SIGMA", "1") == "0" else 1,
+    "dense_sigma_max_mb": max(0, int(os.environ.get("TENSOIR_DENSE_SIGMA_MAX_MB", "1024") or 0)),
     "mlp_grid": max(0, int(os.environ.get("TENSOIR_MLP_GRID", "0") or 0)),
     "pair_order": 2 if os.environ.get("TIR_PAIR_ORDER", "d")[:1] == "m" else 0,
     # TENSOIR_WGRAD_BLOCKS=n: workgroups of the fused weight-gradient launch (0 = 256: each fills a CU).  It runs on the leaf
@@ -381,6 +386,25 @@ def vm_density(field: TirField, xyz, want_feat=True, want_sigma=False):
     feat = torch.empty((n,), dtype=torch.float32, device=xyz.device) if want_feat else None
     sigma = torch.empty((n,), dtype=torch.float32, device=xyz.device) if want_sigma else None
     _call("tir_vm_density_fwd", C.byref(field), _ptr(xyz), _ptr(feat), _ptr(sigma), n, _stream())
+    return feat, sigma
+
+
+def dense_sigma_build(field: TirField, device):
+    """The dense density-feature volume of `field` (tir_dense_sigma_build): fp32 [grid z][grid y][grid x + 1] and its row pitch."""
+    X, Y, Z = [int(g) for g in field.grid]
+    pitch = X + 1
+    vol = torch.empty((Z, Y, pitch), dtype=torch.float32, device=device)
+    _call("tir_dense_sigma_build", C.byref(field), _ptr(vol), pitch, _stream())
+    return vol, pitch
+
+
+def dense_sigma(field: TirField, xyz, want_feat=True, want_sigma=False):
+    """vm_density through the trilinear lookup of field.dense_sigma (the dense secondary march's arithmetic)."""
+    xyz = f32(xyz, "xyz", 3).view(-1, 3)
+    n = xyz.shape[0]
+    feat = torch.empty((n,), dtype=torch.float32, device=xyz.device) if want_feat else None
+    sigma = torch.empty((n,), dtype=torch.float32, device=xyz.device) if want_sigma else None
+    _call("tir_dense_sigma_fwd", C.byref(field), _ptr(xyz), _ptr(feat), _ptr(sigma), n, _stream())
     return feat, sigma
 
 

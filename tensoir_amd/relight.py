@@ -142,8 +142,10 @@ def _secondary(tensoIR, origins, dirs, n_rays, z, org_map, dir_map, active, ligh
 
     No host synchronisation on the record count: the record buffers are sized from the previous call's
     count (x1.5), the gather / decoder kernels read the actual count from device memory (n_dev), and the
-    count is checked once after everything has been queued; an overflow (rare) re-runs the stage."""
-    f = tensoIR.packed_field()
+    count is checked once after everything has been queued; an overflow (rare) re-runs the stage.
+
+    An inference pass marches through the dense density volume (packed_field_dense); a training pass keeps the VM kernels."""
+    f = tensoIR.packed_field() if training else tensoIR.packed_field_dense()
     dev = origins.device
     if not want_indirect:
         vis, oma, _ = ops.march_secondary(f, origins, dirs, z, n_rays, org_map, dir_map, active,
@@ -596,7 +598,7 @@ def relight_with_envmap(tensoIR, surface_xyz, normal, albedo, roughness, fresnel
             _CONST_CACHE.clear()
         _CONST_CACHE[key] = org_map
     z = _z_table(nSample, vis_near, vis_far, dev)
-    vis, _, _ = ops.march_secondary(tensoIR.packed_field(), surface_xyz.to(torch.float32).contiguous(),
+    vis, _, _ = ops.march_secondary(tensoIR.packed_field_dense(), surface_xyz.to(torch.float32).contiguous(),
                                     light_dir.view(-1, 3), z, M * Ns, org_map, None, active.view(-1),
                                     tensoIR.march_t_stop, False, 0, False)
     return ops.relight_importance(normal, albedo, roughness, fresnel, rays_d, light_dir, light_rgb,
@@ -645,7 +647,7 @@ def relight_importance_sampled(tensoIR, env, light_name, surface_xyz, normal, al
         _CONST_CACHE[key] = org_map
     z = _z_table(nSample, vis_near, vis_far, dev)
     env_dir = env.hdr_dir[light_name].view(-1, 3)
-    vis, _, _ = ops.march_secondary(tensoIR.packed_field(), surface_xyz.to(torch.float32).contiguous(), env_dir, z,
+    vis, _, _ = ops.march_secondary(tensoIR.packed_field_dense(), surface_xyz.to(torch.float32).contiguous(), env_dir, z,
                                     M * num_samples, org_map, cell.view(-1), None if active is None else active.view(-1),
                                     tensoIR.march_t_stop, False, 0, False, **listed)
     return ops.relight_importance_cells(normal, albedo, roughness, fresnel, rays_d, cell, env_dir,
