@@ -51,9 +51,7 @@ def _march_records(model, f, origins, dirs, z):
         if total <= cap:
             break
         cap = int(total * 1.25) + 1024
-    if len(hints) > 32:
-        hints.clear()
-    hints[n] = max(int(total * 1.5) + 4096, 1 << 14)
+    ops.learn_capacity(hints, n, total, 1.5, decay=0, max_entries=32)
     return rec, total
 
 

@@ -17,7 +17,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import ops
+from . import indirect, ops
 from ._lib import TensoirHipError, TirField
 
 MAT_MODE = [[0, 1], [0, 2], [1, 2]]
@@ -728,15 +728,8 @@ class TensorVMSplit(nn.Module):
         return {"on": ent["vol"] is not None, "why": ent["why"], "mb": ent["mb"]}
 
     def indirect_precision(self):
-        """What the indirect-light precision policy decided for this model so far (ops.INDIRECT_GUARD, relight._indirect_mode):
-        {"policy": auto|f16|full, "mode": f16|full|None, "why": ..., "probe": {...}} -- also written into checkpoints."""
-        st = self.__dict__.get("_indirect_state") or {}
-        if ops.secondary_app_impl() is None and ops.secondary_mlp_impl() in (None, "hp"):
-            pol = "hp" if ops.secondary_mlp_impl() == "hp" else "full"
-        else:
-            pol = "auto" if ops.INDIRECT_GUARD else "f16"
-        return {"policy": pol, "mode": st.get("verdict") if pol == "auto" else pol, "why": st.get("why"), "probe": st.get("stats"),
-                "probes_run": st.get("probes", 0), "fallbacks": st.get("fallbacks", 0)}
+        """What the indirect-light precision policy decided for this model so far (indirect.report) -- also written into checkpoints."""
+        return indirect.report(self)
 
     # ---- per-point field functions (reference signatures); differentiable through tensoir_amd/pointwise.py ----------
     def compute_densityfeature(self, xyz_sampled):
@@ -973,7 +966,7 @@ class TensorVMSplit(nn.Module):
                                            torch.from_numpy(bits.reshape(shape)).float().to(self.device))
         self.load_state_dict(ckpt["state_dict"])
         self._field_key = None
-        self.__dict__.pop("_indirect_state", None)      # new parameters in the old storage: the precision verdict must be re-established
+        indirect.reset(self)      # new parameters in the old storage: the precision verdict must be re-established
 
     # ---- the primary pass ----------------------------------------------------------------------------
     def forward(self, rays_chunk, light_idx, white_bg=True, is_train=False, ndc_ray=False, is_relight=True,
@@ -1099,9 +1092,7 @@ class TensorVMSplit(nn.Module):
         def finish():
             """True when the pass is valid; False when the record capacity overflowed (the caller re-runs)."""
             total = A if total_dev is None else (total_host.get() if total_host is not None else int(total_dev.item()))
-            if len(hints) > 64:
-                hints.clear()
-            hints[(B, S)] = min(max(int(total * 1.25) + 4096, 1 << 14, int(0.97 * hints.get((B, S), 0))), B * S)      # decays slowly (alternating light / heavy batches)
+            ops.learn_capacity(hints, (B, S), total, 1.25, ceiling=B * S, max_entries=64)
             if total_dev is not None and total > cap:
                 hints.pop((B, S), None)               # next call takes the exact (synchronising) route
                 return False

@@ -24,7 +24,7 @@ import gc
 
 import torch
 
-from . import ops, relight  # noqa: F401  (relight: imported for its caches being warmed by the eager call)
+from . import indirect, ops, relight  # noqa: F401  (relight: imported for its caches being warmed by the eager call)
 from ._lib import TensoirHipError
 from .renderer import Renderer_TensoIR_train
 
@@ -106,7 +106,7 @@ class GraphedRenderer:
         lights = m.light_parameters()
         return (m._field_key, tuple((t.data_ptr(), t._version) for t in lights), tuple(d._key for d in decs),
                 float(m.march_t_stop), ops.MLP_IMPL, ops.app_contraction(), ops.secondary_mlp_impl(), ops.secondary_app_impl(), ops.fused_indirect(),
-                ops.INDIRECT_GUARD and (m.__dict__.get("_indirect_state") or {}).get("verdict"))
+                ops.INDIRECT_GUARD and indirect.verdict(m))
 
     def _stale(self):
         return self.graph is not None and self._key() != self._model_key

@@ -183,6 +183,17 @@ class AsyncCount:
         return self.value
 
 
+def learn_capacity(hints, key, total, growth, *, ceiling=None, decay=0.97, max_entries):
+    """Record capacity for the next call of problem size `key`, learnt from this call's count `total`: growth x the count plus
+    slack, never below 16 k rows, and decaying slowly from the previous hint (a heavy batch after a light one must not
+    overflow); at most `ceiling` rows where the caller knows a bound.  `hints` is the caller's plain dict; it is emptied
+    when it holds more than `max_entries` sizes."""
+    if len(hints) > max_entries:
+        hints.clear()
+    cap = max(int(total * growth) + 4096, 1 << 14, int(decay * hints.get(key, 0)))
+    hints[key] = cap if ceiling is None else min(cap, ceiling)
+
+
 class AsyncFloats:
     """A few device floats on their way to the host (AsyncCount for float tables): copy into pinned memory + event queued NOW.
     Pinned buffers and events are recycled (a training step creates one of these per parameter version)."""
@@ -549,54 +560,15 @@ MLP_ENTRY = {"mfma": "tir_mlp_fwd", "bf16x3": "tir_mlp_fwd_bf16x3", "bf16": "tir
 MLP_IMPL = os.environ.get("TENSOIR_DECODER", "bf16x3")
 if MLP_IMPL not in MLP_ENTRY:
     raise ValueError(f"TENSOIR_DECODER={MLP_IMPL!r}: expected one of {sorted(MLP_ENTRY)}")
-# Precision policy for INDIRECT light.  The radiance of the SECONDARY-ray records (models/relight_utils.py:818-832)
-# is averaged over a ray's records and over the light directions before it reaches rgb_with_brdf_map; its gather and decoder may
-# run at another precision than the launches whose outputs are composited into the maps directly:
-#   TENSOIR_INDIRECT_PRECISION = f16: appearance taps from an fp16 shadow of the planes / lines (tir_vm_app_fwd_h16)
-#                                  and the single-product fp16 decoder (tir_mlp_fwd_auxtab_f16), fp32 accumulation everywhere;
-#                                  measured on rgb_with_brdf_map: profiles/r04_precision_policy.json
-#                              = full: the same kernels as the primary stage (fp32 taps, split-bf16 x3 decoder)
-#                              = auto (default, round 5): the f16 kernels, but only for field / decoder versions that pass (i) the
-#                                  RANGE guard -- max|plane_i| max|line_i| max|light row| and max|basis_mat| from the pack launch
-#                                  bound every fp16 product below 6e4, checked for every new parameter version without an extra
-#                                  host synchronisation -- and (ii) the SELF-CHECK probe: up to INDIRECT_PROBE["records"] of the
-#                                  pass's own records are decoded by both paths and the f16 path is kept only while the signed
-#                                  mean / rms / max difference stay inside INDIRECT_PROBE's limits; re-probed whenever parameter
-#                                  storage changes (load, upsample, shrink) and every INDIRECT_PROBE["interval"] parameter
-#                                  versions otherwise (optimizer steps).  Anything else falls back to `full` for that version
-#                                  (relight._indirect_mode; the verdict is kept with the model and written into checkpoints).
-# Applies only while MLP_IMPL is the split-bf16 default (the exact / cross-check decoder modes stay exact end to end).
-#                              = hp (round 6): the high-precision fused kernel unconditionally (tir_indirect_fused_hp_fwd: fp32 taps,
-#                                  decoder weights as fp16 + fp8 residue).  Under `auto` it is the FIRST fallback: a version whose
-#                                  self-check rejects the f16 kernels is checked the same way with the hp kernel (both against the
-#                                  full kernels) and only goes to `full` when that fails too -- a field trained to 300^3 takes
-#                                  this route (profiles/r06_precision_trained_300.json).  TENSOIR_INDIRECT_HP=0 removes the tier.
+# Knobs of the precision policy for INDIRECT light; the policy itself and its description: tensoir_amd/indirect.py.
 _IND = os.environ.get("TENSOIR_INDIRECT_PRECISION", "auto")
 if _IND not in ("auto", "f16", "hp", "full"):
     raise ValueError(f"TENSOIR_INDIRECT_PRECISION={_IND!r}: expected auto, f16, hp or full")
-SECONDARY_MLP_IMPL = {"full": None, "hp": "hp"}.get(_IND, "f16")       # None | "f16" | "hp" | "bf16" (probe only) | "bf16x3"
-SECONDARY_APP_IMPL = "h16" if _IND in ("auto", "f16") else None        # None | "h16"
-INDIRECT_GUARD = _IND == "auto"        # False: the settings above apply unconditionally (f16 / hp: the caller vouches for range and precision)
-INDIRECT_HP = os.environ.get("TENSOIR_INDIRECT_HP", "1") != "0"        # the hp tier of the auto policy
-# The self-check.  Through render_with_BRDF / Renderer_TensoIR_train (relight.shade_from_maps) it is a MEASUREMENT of the
-# quantity the tolerance is stated on: all secondary-ray records of the pass are decoded by both paths, the integration kernel
-# renders rgb_with_brdf_map from both, and the f16 kernels are kept while
-#     max over the pass's rays of |rgb_with_brdf_map(f16) - rgb_with_brdf_map(full)|  <=  map_limit  (2.5e-5)
-# -- a quarter of the 1e-4 budget; other batches of the same parameters can be worse than the probed one, measured up to 2x
-# (profiles/r05_precision_trained.json), which leaves the policy's contribution under half of the budget.
-# The bare compute_radiance / compute_secondary_shading_effects entry points have no map to measure: there
-# (relight._probe_indirect) an evenly strided subset of the records is decoded by both paths and the map error is ESTIMATED from
-# the signed mean ("bias", max over the colour channels), the rms and the max of the difference:
-#     max(w_bias * bias + w_rms * rms, w_max * max) <= limit
-# calibrated on the scaling sweep and the trained checkpoint of tests/precision_cases.py, where the measured map error was
-# 0.45 bias + 0.2 rms within 15 % on the smooth scenes and 0.2 max on the trained one (profiles/r05_precision_sweep.json: 3.3e-6 as
-# initialised, 3.0e-5 with the radiance decoder's weights doubled, 2.0e-4 with x4 -- unguarded fp16 leaves the budget there).
-# range: the largest |product| the range guard accepts (largest finite fp16 = 65504).
-# TENSOIR_INDIRECT_MAP_LIMIT overrides map_limit (a trained analytic scene measured 2.0e-5 ... 3.1e-5 on its own training rays:
-# around the default, so such a checkpoint may run either way; both are within the budget).
-# train_map_limit: what a TRAINING forward accepts (is_train renders feed the loss only, and the secondary stage is a no_grad
-# constant there, models/relight_utils.py:344): the contract's tolerance itself.  A verdict taken with it never serves an
-# inference pass (relight._indirect_mode re-probes with the strict limit).
+SECONDARY_MLP_IMPL = {"full": None, "hp": "hp"}.get(_IND, "f16")       # None | "f16" | "hp" | "bf16" (probe only) | "bf16x3"; read by indirect.mode
+SECONDARY_APP_IMPL = "h16" if _IND in ("auto", "f16") else None        # None | "h16"; read by indirect.mode
+INDIRECT_GUARD = _IND == "auto"        # False: the settings above apply unconditionally (f16 / hp: the caller vouches for range and precision); indirect.mode
+INDIRECT_HP = os.environ.get("TENSOIR_INDIRECT_HP", "1") != "0"        # the hp tier of the auto policy (indirect.establish's try_hp)
+# limits of the self-check and of the range guard (tensoir_amd/indirect.py: establish, record_estimate; HalfRange above)
 INDIRECT_PROBE = {"map_limit": float(os.environ.get("TENSOIR_INDIRECT_MAP_LIMIT", "2.5e-5")), "train_map_limit": 1.0e-4, "records": 32768, "interval": 64, "w_bias": 0.5, "w_rms": 0.25, "w_max": 0.25, "limit": 2.5e-5,
                   "range": 6.0e4}
 

@@ -2,12 +2,13 @@
 meaning and return shapes; per-sample work runs in libtensoir_hip.so."""
 from __future__ import annotations
 
+import functools
 import os
 
 import numpy as np
 import torch
 
-from . import ops
+from . import indirect, ops
 from .field_model import safe_l2_normalize  # noqa: F401  (re-exported, as the reference module does)
 
 MAP_STRIDE = ops.MAP_STRIDE
@@ -56,82 +57,44 @@ def _gather_then_decode(tensoIR, f, fh, rec_xyz, light_idx, rec_ray, light_div, 
                    n_dirs if dir_map is None else 0, n_dev)
 
 
-def _indirect_state(tensoIR):
-    return tensoIR.__dict__.setdefault("_indirect_state", {"verdict": None, "key": None, "storage": None, "age": 0, "why": None,
-                                                           "stats": None, "probes": 0, "fallbacks": 0})
+def _fusable(f, dirs, dir_map, n_dirs, n_rows):
+    """Whether the one-launch kernels (ops.indirect_fused, ops.indirect_fused_hp) take this pass's records."""
+    return dir_map is None and n_dirs > 0 and dirs.shape[0] * 8 <= max(n_rows, 1) and int(f.app_dim) == 27 and int(f.n_acomp) == 48
 
 
-def _indirect_key(tensoIR):
-    """(parameter versions, parameter storage) of everything the indirect-light kernels read: appearance field + radiance decoder."""
-    if tensoIR._field_key is None:          # (callers inside a pass have just refreshed it: the key walk over ~35 parameters
-        tensoIR.packed_field()              #  costs ~70 us of host time, and the training loop is host-bound)
-    tensoIR.renderModule.packed()
-    fk = tensoIR._field_key[0]
-    key = (fk, tensoIR.renderModule._key)
-    storage = (tuple((a, c) for a, _, c in fk), tuple(a for a, _ in tensoIR.renderModule._key))
-    return key, storage
+def _decode_records(tensoIR, f, fh, kind, rec_xyz, rec_ray, n_dev, light_idx, light_div, dirs, dir_map, n_dirs):
+    """Radiance rows of secondary-ray records from the kernels of one tier.  kind: "f16" (fp16 shadow `fh` + fp16 decoder), "hp"
+    (fp32 taps, fp16 + fp8-residue weights) or "full" (the primary-stage kernels).  light index / view direction of a record =
+    those of its ray (ray id -> point via light_div, ray id -> direction via n_dirs on the dense [point][direction] grid)."""
+    if _fusable(f, dirs, dir_map, n_dirs, rec_xyz.shape[0]):
+        if kind == "f16" and fh is not None and ops.fused_indirect() and int(f.n_lights) <= 16:
+            # gather -> basis contraction -> radiance decoder in ONE launch, the feature rows never reach HBM
+            return ops.indirect_fused(f, fh, tensoIR.renderModule.packed(), rec_xyz, light_idx, rec_ray, light_div, dirs, n_dirs, n_dev)
+        if kind == "hp" and ops.AUX_TABLE and ops.MLP_IMPL == "bf16x3" and int(f.n_lights) <= 8:
+            return ops.indirect_fused_hp(f, tensoIR.renderModule.packed(), rec_xyz, light_idx, rec_ray, light_div, dirs, n_dirs, n_dev)
+    return _gather_then_decode(tensoIR, f, fh, rec_xyz, light_idx, rec_ray, light_div, dirs, dir_map, n_dirs, n_dev, full=kind != "f16")
 
 
-def _indirect_mode(tensoIR, training=False):
-    """Which kernels decode this pass's secondary-ray records: "full" (primary-stage kernels), "f16" (the precision policy's fast
-    kernels), "hp" (the high-precision fused kernel, ops.indirect_fused_hp) or "probe" (auto policy, no valid verdict for the
-    current parameters: run f16, self-check against full, if that fails self-check hp against full, decide).
-
-    auto (ops.INDIRECT_GUARD): a verdict belongs to one parameter version.  Inference passes always use a verdict of exactly
-    the current version (so the same parameters render the same image whatever was rendered before).  TRAINING passes
-    (`training`: the forward of an optimizer step, where indirect light is a no_grad constant of the loss) carry it over to later
-    versions of the SAME storage -- an optimizer step moves a parameter by at most the learning rate -- for
-    ops.INDIRECT_PROBE["interval"] versions, then re-establish it; new storage (load, upsample, shrink) re-establishes it at
-    once.  The range guard is evaluated for EVERY version (HalfRange, no extra synchronisation) by the caller."""
-    if ops.secondary_app_impl() != "h16" and ops.secondary_mlp_impl() in (None, "hp"):
-        return "hp" if ops.secondary_mlp_impl() == "hp" else "full"
-    if not ops.INDIRECT_GUARD:
-        return "f16"
-    st = _indirect_state(tensoIR)
-    key, storage = _indirect_key(tensoIR)
-    # `key` is the version a probe MEASURED; `carried_key` the latest version a training pass carried that verdict over to.
-    # Only a training pass may ride on a carried verdict: an inference pass at a version that was never probed probes.
-    if st["verdict"] is not None and st["key"] == key and (training or not st.get("train_limit")):
-        return st["verdict"]         # (an inference pass never rides on a verdict taken with the training limit)
-    if training and st["verdict"] is not None and st["storage"] == storage:
-        if st.get("carried_key") == key:
-            return st["verdict"]     # (another pass at a version already counted)
-        if st["age"] < ops.INDIRECT_PROBE["interval"]:
-            st["age"] += 1
-            st["carried_key"] = key
-            return st["verdict"]
-    return "probe"
+def _range_failed(tensoIR, rng):
+    """The range guard (tir_pack_half_checked's contract) on the maxima of THIS version's fp16 shadow; waits for them if they have
+    not arrived.  True: an fp16 product could overflow -> the verdict is `full`, the caller decodes with the primary-stage kernels."""
+    if rng is None or rng.ok():
+        return False
+    indirect.set_verdict(tensoIR, "full", "range", {"bound": rng.bound, "maxima": rng.maxima})
+    return True
 
 
-def _set_verdict(tensoIR, verdict, why, stats=None, train_limit=False):
-    st = _indirect_state(tensoIR)
-    key, storage = _indirect_key(tensoIR)
-    if verdict != "f16" and st["verdict"] != verdict:       # (a version that left the fast kernels: to hp, or all the way to full)
-        st["fallbacks"] += 1
-    st.update(verdict=verdict, key=key, carried_key=None, storage=storage, age=0, why=why, train_limit=bool(train_limit))
-    if stats is not None:
-        st["stats"] = stats
-
-
-def _probe_indirect(tensoIR, f, rgb, n_valid, rec_xyz, light_idx, rec_ray, light_div, dirs, dir_map, n_dirs):
-    """The self-check of the auto policy: an evenly strided subset of this pass's records decoded by the primary-stage kernels
-    and compared with the f16 path's `rgb` rows.  One host synchronisation (only in passes that establish a verdict)."""
-    lim = ops.INDIRECT_PROBE
-    n_valid = min(int(n_valid), rgb.shape[0])
-    if n_valid <= 0:
-        return True, {"records": 0}
-    step = max(1, n_valid // lim["records"])
-    sel = torch.arange(0, n_valid, step, device=rgb.device)[:lim["records"]]
-    ref = _gather_then_decode(tensoIR, f, None, rec_xyz[sel].contiguous(), light_idx, rec_ray[sel].contiguous(), light_div, dirs,
-                              dir_map, n_dirs, None, full=True)
-    d = (rgb[sel] - ref).double()
-    v = torch.stack([d.mean(0).abs().max(), d.pow(2).mean().sqrt(), d.abs().max(), ref.double().pow(2).mean().sqrt()]).tolist()
-    est = max(lim["w_bias"] * v[0] + lim["w_rms"] * v[1], lim["w_max"] * v[2])     # estimated max error on rgb_with_brdf_map (ops.INDIRECT_PROBE)
-    stats = {"kind": "records", "records": int(sel.numel()), "of": n_valid, "bias": v[0], "rms": v[1], "max": v[2], "radiance_rms": v[3],
-             "estimate": est}
-    ok = est <= lim["limit"]                                   # (NaN fails)
-    _indirect_state(tensoIR)["probes"] += 1
-    return bool(ok), stats
+def _map_measure(probe_map, vis, packed, full_rows, count, n_rays, map_limit):
+    """indirect.establish's `measure` where the caller renders rgb_with_brdf_map from BOTH decodes of ALL records of this pass
+    (probe_map): the quantity the tolerance is stated on, measured -- not estimated."""
+    def measure(cand):
+        n_valid, ref = count(), full_rows()
+        d = (cand[:n_valid] - ref[:n_valid]).double()
+        delta = probe_map(vis, packed(cand), packed(ref))
+        v = (torch.stack([d.mean(0).abs().max(), d.pow(2).mean().sqrt(), d.abs().max()]).tolist() if n_valid else [0.0, 0.0, 0.0])
+        return delta <= map_limit, {"kind": "map", "map_max_abs": delta, "records": n_valid, "rays": n_rays, "bias": v[0], "rms": v[1],
+                                    "max": v[2], "limit": map_limit}                   # (NaN fails)
+    return measure
 
 
 def _secondary(tensoIR, origins, dirs, n_rays, z, org_map, dir_map, active, light_idx, light_div,
@@ -181,127 +144,81 @@ def _secondary(tensoIR, origins, dirs, n_rays, z, org_map, dir_map, active, ligh
             n_rows = total
         else:
             n_rows = cap
-        indirect = None
-        mode = "full" if force_full else _indirect_mode(tensoIR, training)
+        mode = "full" if force_full else indirect.mode(tensoIR, training)
         if mode == "probe" and capture is not None:
             raise ops._lib.TensoirHipError("graph capture needs an established indirect-light precision verdict (run the pass eagerly first)")
         rng = None
         if n_rows > 0:
             rec_ray, rec_w, rec_xyz = rec["ray"][:n_rows], rec["w"][:n_rows], rec["xyz"][:n_rows]
-            # light index / view direction of a record = those of its ray (ray id -> point via idx_div,
-            # ray id -> direction via aux_mod on the dense [point][direction] grid)
             fh = tensoIR.packed_field_half(_fresh=True) if (mode != "full" and ops.secondary_app_impl() == "h16") else None
             rng = tensoIR.half_range(_fresh=True) if (fh is not None and ops.INDIRECT_GUARD) else None
-            if rng is not None and (mode == "probe" or rng.ready()) and not rng.ok():
-                # range guard (tir_pack_half_checked's contract): an fp16 product could overflow -> the primary-stage kernels
-                _set_verdict(tensoIR, "full", "range", {"bound": rng.bound, "maxima": rng.maxima})
-                mode, fh, rng = "full", None, None
+            if rng is not None and (mode == "probe" or rng.ready()):   # a pass that waits anyway, or maxima that have arrived: now
+                if _range_failed(tensoIR, rng):
+                    mode, fh = "full", None
+                rng = None
             if capture is not None and rng is not None and not rng.ready():
                 raise ops._lib.TensoirHipError("graph capture needs a finished range check of the fp16 field shadow (run the pass eagerly first)")
+            lookup = (light_idx, light_div, dirs, dir_map, n_dirs)
 
-            fusable = dir_map is None and n_dirs > 0 and dirs.shape[0] * 8 <= max(n_rows, 1) and int(f.app_dim) == 27 and int(f.n_acomp) == 48
-
-            def decode(kind, fh=fh):
-                """kind: "f16" (fp16 shadow + fp16 decoder), "hp" (fp32 taps, fp16 + fp8-residue weights) or "full"."""
-                if kind == "f16" and fh is not None and fusable and ops.fused_indirect() and int(f.n_lights) <= 16:
-                    # gather -> basis contraction -> radiance decoder in ONE launch, the feature rows never reach HBM
-                    return ops.indirect_fused(f, fh, tensoIR.renderModule.packed(), rec_xyz, light_idx, rec_ray, light_div, dirs, n_dirs, n_dev)
-                if kind == "hp" and fusable and ops.AUX_TABLE and ops.MLP_IMPL == "bf16x3" and int(f.n_lights) <= 8:
-                    return ops.indirect_fused_hp(f, tensoIR.renderModule.packed(), rec_xyz, light_idx, rec_ray, light_div, dirs, n_dirs, n_dev)
-                return _gather_then_decode(tensoIR, f, fh, rec_xyz, light_idx, rec_ray, light_div, dirs, dir_map, n_dirs, n_dev,
-                                           full=kind != "f16")
+            def decode(kind):
+                return _decode_records(tensoIR, f, fh, kind, rec_xyz, rec_ray, n_dev, *lookup)
 
             def packed(rgb):
                 if keep_records:       # the caller's integration kernel sums the records itself (tir_shade_integrate_records)
                     return {"off": rec["off"], "cnt": rec["cnt"], "w": rec_w, "rgb": rgb}
                 return ops.accumulate_records(rec["off"], rec["cnt"], rec_w, rgb, n_rays)
 
-            rgb = decode("f16" if mode == "probe" else mode)
             if mode == "probe":        # auto policy, no verdict for these parameters yet: self-check on this pass's own records
-                n_valid = min(total if first else total_host.get(), n_rows)
-                verdict = "f16"
+                def count():           # (asked for after the f16 decode has been queued)
+                    return min(total if first else total_host.get(), n_rows)
                 if probe_map is not None:
-                    # the caller renders rgb_with_brdf_map from BOTH decodes of ALL records of this pass: the quantity the
-                    # tolerance is stated on, measured -- not estimated
-                    rgb_full = decode("full")
+                    decode = functools.lru_cache(maxsize=None)(decode)       # the full rows: measured against, and the last tier
                     # a TRAINING pass renders the map as a no_grad constant of the loss (models/relight_utils.py:344): there the
                     # policy accepts up to the contract's own tolerance; inference / export use the strict limit
-                    map_limit = ops.INDIRECT_PROBE["train_map_limit" if training else "map_limit"]
-
-                    def measure(cand):
-                        d = (cand[:n_valid] - rgb_full[:n_valid]).double()
-                        delta = probe_map(vis, packed(cand), packed(rgb_full))
-                        v = (torch.stack([d.mean(0).abs().max(), d.pow(2).mean().sqrt(), d.abs().max()]).tolist() if n_valid else [0.0, 0.0, 0.0])
-                        return delta, {"kind": "map", "map_max_abs": delta, "records": n_valid, "rays": n_rays, "bias": v[0], "rms": v[1], "max": v[2],
-                                       "limit": map_limit}
-                    delta, stats = measure(rgb)
-                    _indirect_state(tensoIR)["probes"] += 1
-                    if not delta <= map_limit:                               # (NaN fails)
-                        verdict = "full"
-                        if ops.INDIRECT_HP:                                  # first fallback: the high-precision fused kernel, checked the same way
-                            rgb_hp = decode("hp")
-                            delta_hp, stats_hp = measure(rgb_hp)
-                            stats = {**stats_hp, "f16": stats}
-                            if delta_hp <= map_limit:
-                                verdict, rgb = "hp", rgb_hp
-                        if verdict == "full":
-                            rgb = rgb_full
+                    measure = _map_measure(probe_map, vis, packed, lambda: decode("full"), count, n_rays,
+                                           ops.INDIRECT_PROBE["train_map_limit" if training else "map_limit"])
+                    try_hp = ops.INDIRECT_HP
                 else:
-                    ok, stats = _probe_indirect(tensoIR, f, rgb, n_valid, rec_xyz, light_idx, rec_ray, light_div, dirs, dir_map, n_dirs)
-                    if not ok:
-                        verdict = "full"
-                        if ops.INDIRECT_HP and fusable and ops.AUX_TABLE and ops.MLP_IMPL == "bf16x3":
-                            rgb_hp = decode("hp")
-                            ok_hp, stats_hp = _probe_indirect(tensoIR, f, rgb_hp, n_valid, rec_xyz, light_idx, rec_ray, light_div, dirs, dir_map, n_dirs)
-                            stats = {**stats_hp, "f16": stats}
-                            if ok_hp:
-                                verdict, rgb = "hp", rgb_hp
-                        if verdict == "full":
-                            rgb = decode("full")
-                _set_verdict(tensoIR, verdict, "probe", stats, train_limit=training and probe_map is not None)
-                rng = None             # (evaluated above)
-            indirect = packed(rgb)
+                    def measure(rows):
+                        return indirect.record_estimate(rows, count(), lambda sel: _decode_records(
+                            tensoIR, f, None, "full", rec_xyz[sel].contiguous(), rec_ray[sel].contiguous(), None, *lookup))
+                    try_hp = ops.INDIRECT_HP and _fusable(f, dirs, dir_map, n_dirs, n_rows) and ops.AUX_TABLE and ops.MLP_IMPL == "bf16x3"
+                _, rgb = indirect.establish(tensoIR, decode, measure, try_hp, train_limit=training and probe_map is not None)
+            else:
+                rgb = decode(mode)
+            indirect_rgb = packed(rgb)
         else:
-            indirect = torch.zeros((n_rays, 3), dtype=torch.float32, device=dev)
-
-        def range_failed(rng=rng):
-            """The range guard of a carried-over verdict, evaluated once the maxima of THIS version's shadow have arrived."""
-            if rng is None or rng.ok():
-                return False
-            _set_verdict(tensoIR, "full", "range", {"bound": rng.bound, "maxima": rng.maxima})
-            return True
+            indirect_rgb = torch.zeros((n_rays, 3), dtype=torch.float32, device=dev)
 
         if first:
-            if range_failed():
+            if _range_failed(tensoIR, rng):
                 force_full = True
                 continue
             break
         if capture is not None:                        # HIP-graph capture: the graph owner reads the counter after replay
-            if rng is not None and not rng.ok():
+            if _range_failed(tensoIR, rng):
                 raise ops._lib.TensoirHipError("graph capture: the fp16 field shadow fails the range guard")
             capture.append((n_total, cap, ("secondary", n_rays)))
-            return vis, oma, indirect
+            return vis, oma, indirect_rgb
         if defer:                                      # the caller checks after ITS remaining launches are queued too
-            def check(total_host=total_host, cap=cap, range_failed=range_failed):
+            def check():
                 total = total_host.get()
                 if total > cap:
                     hints.pop(n_rays, None)            # the re-run learns the count first
                     return False
-                hints[n_rays] = max(int(total * 1.5) + 4096, 1 << 14, int(0.97 * hints.get(n_rays, 0)))
-                return not range_failed()              # (a failed range guard: the re-run decodes with the primary-stage kernels)
+                ops.learn_capacity(hints, n_rays, total, 1.5, max_entries=32)
+                return not _range_failed(tensoIR, rng)     # (a failed range guard: the re-run decodes with the primary-stage kernels)
             tensoIR.__dict__.setdefault("_pending_checks", []).append(check)
-            return vis, oma, indirect
+            return vis, oma, indirect_rgb
         total = total_host.get()                       # waits for the march only, not for what was queued behind it
         if total <= cap:
-            if range_failed():
+            if _range_failed(tensoIR, rng):
                 force_full = True
                 continue
             break
         cap = int(total * 1.25) + 1024                 # overflow: some rays were dropped -> redo with room
-    if len(hints) > 32:
-        hints.clear()
-    hints[n_rays] = max(int(total * 1.5) + 4096, 1 << 14, int(0.97 * hints.get(n_rays, 0)))
-    return vis, oma, indirect
+    ops.learn_capacity(hints, n_rays, total, 1.5, max_entries=32)
+    return vis, oma, indirect_rgb
 
 
 @torch.no_grad()

@@ -316,10 +316,8 @@ class PrimaryRenderFn(torch.autograd.Function):
                     st.valid = False
                     return False
                 _trim_state(st, total)
-            if len(hints) > 64:
-                hints.clear()
             if noise_dense is None:
-                hints[(B, S)] = min(max(int(total * 1.25) + 4096, 1 << 14, int(0.97 * hints.get((B, S), 0))), B * S)      # decays slowly: a heavy batch after a light one must not overflow
+                ops.learn_capacity(hints, (B, S), total, 1.25, ceiling=B * S, max_entries=64)
             return True
 
         st.finish = None if total_dev is None else finish

@@ -42,12 +42,13 @@ def render(model, rays, lidx, noise, n_samples):
 
 def three_policies(model, rays, lidx, noise, n_samples):
     """rgb_with_brdf under forced f16, full and auto (+ what auto decided and measured)."""
+    from tensoir_amd import indirect
     res = {}
     with policy(False):
         out, res["f16"] = render(model, rays, lidx, noise, n_samples)
     with policy(False, None, None):
         _, res["full"] = render(model, rays, lidx, noise, n_samples)
-    model.__dict__.pop("_indirect_state", None)
+    indirect.reset(model)
     with policy(True):
         _, res["auto"] = render(model, rays, lidx, noise, n_samples)
         res["decision"] = model.indirect_precision()

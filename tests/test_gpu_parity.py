@@ -579,6 +579,44 @@ def test_record_overflow_recovers(env):
     assert rel(ind, env.g["sec/rad_indirect"]) < TOL
 
 
+@torch.no_grad()
+@pytest.mark.parametrize("tier", ["f16", "hp", "full", "auto"])
+def test_every_capacity_route_renders_the_same(env, tier):
+    """The record-capacity protocol of relight._secondary never changes the result: the synchronising first call, the hinted
+    call, the deferred check, an overflow that re-marches and a deferred overflow that makes the caller re-run all render
+    bit-identical rows, under each forced tier and under auto (whose first call also establishes the verdict)."""
+    from tensoir_amd import indirect, relight
+    from tests import precision_cases as P
+    m = env.model
+    rays, lidx = G(env, "rays/rays"), G(env, "rays/light_idx")
+    _, maps = m(rays, lidx, _return_maps=True)
+    key = maps.shape[0] * m.fixed_viewdirs.shape[0]          # M * D secondary rays
+
+    def shade(**kw):
+        return relight.shade_from_maps(m, maps, rays, lidx, "fixed_envirmap", env.args, acc_thres=0.5, **kw)
+
+    with P.policy(*{"f16": (False,), "hp": (False, "hp", None), "full": (False, None, None), "auto": (True,)}[tier]):
+        indirect.reset(m)
+        m.__dict__.pop("_rec_cap_hints", None)
+        renders = {"first": shade()}                         # no hint: reads the count back, then sizes the buffers
+        assert m._rec_cap_hints[key] > 1
+        renders["hinted"] = shade()
+        renders["deferred"] = shade(_defer_check=True)
+        assert relight.finish_pending(m) is True
+        m._rec_cap_hints[key] = 1
+        renders["overflow"] = shade()                        # far too small: re-marches with room
+        assert m._rec_cap_hints[key] > 1
+        m._rec_cap_hints[key] = 1
+        shade(_defer_check=True)                             # ... found by the deferred check: the caller re-runs
+        assert relight.finish_pending(m) is False and key not in m._rec_cap_hints
+        renders["re-run"] = shade()
+        if tier == "auto":
+            assert m.indirect_precision()["probes_run"] == 1
+    assert torch.isfinite(renders["first"]).all() and float(renders["first"].min()) < 1.0      # (some ray hit the object)
+    for name, r in renders.items():
+        assert torch.equal(r, renders["first"]), (tier, name)
+
+
 # ---------------------------------------------------------------- full size (BASELINE C2/C3) properties
 @pytest.fixture(scope="module")
 def full():

@@ -1,4 +1,4 @@
-"""The indirect-light precision policy (ops.INDIRECT_GUARD, relight._indirect_mode) on a TRAINED checkpoint and on
+"""The indirect-light precision policy (ops.INDIRECT_GUARD, tensoir_amd/indirect.py) on a TRAINED checkpoint and on
 adversarially scaled fields: the default policy keeps every map within 1e-4 of the oracle, keeps
 rgb_with_brdf_map within 2.5e-5 of the full-precision kernels, and falls back to them -- by the range guard or by the self-check
 probe -- exactly where the fp16 kernels would not.  Reference stage: models/relight_utils.py:777-834."""
@@ -113,7 +113,7 @@ def test_adversarial_scaling(cfg):
 
 @torch.no_grad()
 def test_bare_compute_radiance_uses_the_record_level_estimate():
-    """compute_radiance has no map to measure: the verdict comes from the strided record probe (relight._probe_indirect), and
+    """compute_radiance has no map to measure: the verdict comes from the strided record probe (indirect.record_estimate), and
     the returned indirect light equals the forced-policy result of that verdict (f16 on the scene as initialised; whatever the
     estimate says with the radiance decoder's weights x16)."""
     import contextlib

@@ -1,5 +1,6 @@
 """Host logic of round 5 that needs no GPU: the verdict state machine of the indirect-light precision policy
-(relight._indirect_mode / _set_verdict), the range guard's bound (ops.HalfRange.judge), the shard layout used by the image
+(indirect.mode / set_verdict), its self-check ladder and record estimate (indirect.establish / record_estimate), the
+record-capacity hint (ops.learn_capacity), the range guard's bound (ops.HalfRange.judge), the shard layout used by the image
 all-gather (dist._layout / gather_records at world 1) and the arithmetic of bench.simulate_ranks."""
 import math
 import os
@@ -51,57 +52,196 @@ def auto_policy(monkeypatch):
 
 
 def test_verdict_state_machine(auto_policy):
-    from tensoir_amd import relight
+    from tensoir_amd import indirect
     ops, m = auto_policy, _Model()
-    assert relight._indirect_mode(m) == "probe"                          # nothing known yet
-    relight._set_verdict(m, "f16", "probe", {"map_max_abs": 1e-6})
-    assert relight._indirect_mode(m) == "f16" and relight._indirect_mode(m, training=True) == "f16"
+    assert indirect.mode(m) == "probe"                          # nothing known yet
+    indirect.set_verdict(m, "f16", "probe", {"map_max_abs": 1e-6})
+    assert indirect.mode(m) == "f16" and indirect.mode(m, training=True) == "f16"
     # inference: a verdict belongs to exactly one parameter version
     m.step()
-    assert relight._indirect_mode(m) == "probe"
+    assert indirect.mode(m) == "probe"
     # training: carried over for `interval` versions of the same storage, then re-established
     for _ in range(ops.INDIRECT_PROBE["interval"]):
-        assert relight._indirect_mode(m, training=True) == "f16"
-        assert relight._indirect_mode(m, training=True) == "f16"         # (asking twice for one version does not age it twice)
+        assert indirect.mode(m, training=True) == "f16"
+        assert indirect.mode(m, training=True) == "f16"         # (asking twice for one version does not age it twice)
         m.step()
-    assert relight._indirect_mode(m, training=True) == "probe"
+    assert indirect.mode(m, training=True) == "probe"
     # ... and an inference pass never inherits a CARRIED verdict: strict verdict at v0, five training steps, inference at v5 probes
     m2 = _Model()
-    relight._set_verdict(m2, "f16", "probe", {"map_max_abs": 1e-6})
+    indirect.set_verdict(m2, "f16", "probe", {"map_max_abs": 1e-6})
     for _ in range(5):
         m2.step()
-        assert relight._indirect_mode(m2, training=True) == "f16"
-    assert relight._indirect_mode(m2) == "probe"
-    assert relight._indirect_mode(m2, training=True) == "f16"            # (the training loop still rides on it)
-    relight._set_verdict(m, "full", "probe", {"map_max_abs": 9e-5})
-    assert relight._indirect_state(m)["fallbacks"] == 1
+        assert indirect.mode(m2, training=True) == "f16"
+    assert indirect.mode(m2) == "probe"
+    assert indirect.mode(m2, training=True) == "f16"            # (the training loop still rides on it)
+    indirect.set_verdict(m, "full", "probe", {"map_max_abs": 9e-5})
+    assert indirect.state(m)["fallbacks"] == 1
     m.step()
-    assert relight._indirect_mode(m, training=True) == "full"
+    assert indirect.mode(m, training=True) == "full"
     # new storage (upsample, shrink, a model rebuilt from a checkpoint): at once
     m.realloc()
-    assert relight._indirect_mode(m, training=True) == "probe"
+    assert indirect.mode(m, training=True) == "probe"
     # a verdict taken with the TRAINING limit never serves an inference pass of the same version
-    relight._set_verdict(m, "f16", "probe", {"map_max_abs": 6e-5}, train_limit=True)
-    assert relight._indirect_mode(m, training=True) == "f16" and relight._indirect_mode(m) == "probe"
-    relight._set_verdict(m, "full", "probe", {"map_max_abs": 6e-5})
-    assert relight._indirect_mode(m) == "full"
+    indirect.set_verdict(m, "f16", "probe", {"map_max_abs": 6e-5}, train_limit=True)
+    assert indirect.mode(m, training=True) == "f16" and indirect.mode(m) == "probe"
+    indirect.set_verdict(m, "full", "probe", {"map_max_abs": 6e-5})
+    assert indirect.mode(m) == "full"
 
 
 def test_forced_policies_bypass_the_state_machine(monkeypatch):
-    from tensoir_amd import ops, relight
+    from tensoir_amd import indirect, ops
     m = _Model()
     monkeypatch.setattr(ops, "MLP_IMPL", "bf16x3")
     monkeypatch.setattr(ops, "INDIRECT_GUARD", False)
     monkeypatch.setattr(ops, "SECONDARY_MLP_IMPL", "f16")
     monkeypatch.setattr(ops, "SECONDARY_APP_IMPL", "h16")
-    assert relight._indirect_mode(m) == "f16"
+    assert indirect.mode(m) == "f16"
     monkeypatch.setattr(ops, "SECONDARY_MLP_IMPL", None)
     monkeypatch.setattr(ops, "SECONDARY_APP_IMPL", None)
-    assert relight._indirect_mode(m) == "full"
+    assert indirect.mode(m) == "full"
     monkeypatch.setattr(ops, "SECONDARY_MLP_IMPL", "f16")
     monkeypatch.setattr(ops, "SECONDARY_APP_IMPL", "h16")
     monkeypatch.setattr(ops, "MLP_IMPL", "mfma")                        # the exact decoder modes stay exact end to end
-    assert relight._indirect_mode(m) == "full"
+    assert indirect.mode(m) == "full"
+
+
+class _Ladder:
+    """decode / measure of indirect.establish on the CPU: one small distinct tensor per tier, the tiers asked for in order, and a
+    scripted measurement per candidate tier (a callable is evaluated on the spot, as the real comparisons are)."""
+
+    def __init__(self, script):
+        self.rows = {k: torch.full((4, 3), float(i)) for i, k in enumerate(("f16", "hp", "full"))}
+        self.script, self.asked = script, []
+
+    def decode(self, kind):
+        self.asked.append(kind)
+        return self.rows[kind]
+
+    def measure(self, rows):
+        tier = next(k for k, v in self.rows.items() if v is rows)
+        ok, stats = self.script[tier]
+        return (ok() if callable(ok) else ok), dict(stats)
+
+
+def test_ladder_keeps_f16_when_it_passes(auto_policy):
+    from tensoir_amd import indirect
+    m, lad = _Model(), _Ladder({"f16": (True, {"kind": "map", "map_max_abs": 1e-6})})
+    verdict, rows = indirect.establish(m, lad.decode, lad.measure, try_hp=True, train_limit=False)
+    assert verdict == "f16" and rows is lad.rows["f16"] and lad.asked == ["f16"]
+    st = indirect.state(m)
+    assert st["verdict"] == "f16" and st["why"] == "probe" and st["stats"] == {"kind": "map", "map_max_abs": 1e-6}
+    assert st["fallbacks"] == 0 and st["probes"] == 1 and st["train_limit"] is False
+    assert indirect.mode(m) == "f16" and indirect.verdict(m) == "f16"
+
+
+def test_ladder_falls_back_to_hp_then_full(auto_policy):
+    from tensoir_amd import indirect
+    f16_stats, hp_stats = {"kind": "map", "map_max_abs": 7e-5}, {"kind": "map", "map_max_abs": 8e-6}
+    m, lad = _Model(), _Ladder({"f16": (False, f16_stats), "hp": (True, hp_stats)})
+    verdict, rows = indirect.establish(m, lad.decode, lad.measure, try_hp=True, train_limit=False)
+    assert verdict == "hp" and rows is lad.rows["hp"] and lad.asked == ["f16", "hp"]
+    st = indirect.state(m)
+    assert st["stats"] == {**hp_stats, "f16": f16_stats} and st["fallbacks"] == 1 and st["probes"] == 1
+    assert indirect.mode(m) == "hp"
+    # both fail: the primary-stage kernels, and the caller gets the full rows object
+    m, lad = _Model(), _Ladder({"f16": (False, f16_stats), "hp": (False, hp_stats)})
+    verdict, rows = indirect.establish(m, lad.decode, lad.measure, try_hp=True, train_limit=False)
+    assert verdict == "full" and rows is lad.rows["full"] and lad.asked == ["f16", "hp", "full"]
+    assert indirect.state(m)["stats"] == {**hp_stats, "f16": f16_stats} and indirect.state(m)["fallbacks"] == 1
+    assert indirect.mode(m) == "full"
+    # the hp tier switched off: never decoded
+    m, lad = _Model(), _Ladder({"f16": (False, f16_stats), "hp": (True, hp_stats)})
+    verdict, rows = indirect.establish(m, lad.decode, lad.measure, try_hp=False, train_limit=False)
+    assert verdict == "full" and rows is lad.rows["full"] and lad.asked == ["f16", "full"]
+    assert indirect.state(m)["stats"] == f16_stats and indirect.state(m)["fallbacks"] == 1
+
+
+def test_ladder_rejects_a_nan_measurement(auto_policy):
+    from tensoir_amd import indirect
+    nan, limit = float("nan"), 2.5e-5
+    m, lad = _Model(), _Ladder({"f16": (lambda: nan <= limit, {"map_max_abs": nan}), "hp": (lambda: nan <= limit, {"map_max_abs": nan})})
+    verdict, rows = indirect.establish(m, lad.decode, lad.measure, try_hp=True, train_limit=False)
+    assert verdict == "full" and rows is lad.rows["full"] and lad.asked == ["f16", "hp", "full"]
+
+
+def test_ladder_training_limit_and_probe_count(auto_policy):
+    from tensoir_amd import indirect
+    m, lad = _Model(), _Ladder({"f16": (True, {"map_max_abs": 6e-5})})
+    attrs = set(m.__dict__)
+    assert indirect.verdict(m) is None and set(m.__dict__) == attrs                     # (reading creates no state)
+    indirect.establish(m, lad.decode, lad.measure, try_hp=True, train_limit=True)
+    assert indirect.state(m)["train_limit"] is True
+    assert indirect.mode(m) == "probe" and indirect.mode(m, training=True) == "f16"
+    for n in (2, 3):                                                     # one per pass that ran the self-check, hp tried or not
+        lad.script = {"f16": (False, {}), "hp": (n == 2, {})}
+        indirect.establish(m, lad.decode, lad.measure, try_hp=True, train_limit=False)
+        assert indirect.state(m)["probes"] == n and indirect.report(m)["probes_run"] == n
+    assert indirect.report(m)["mode"] == "full" and indirect.report(m)["fallbacks"] == 2
+    indirect.reset(m)
+    assert indirect.verdict(m) is None and indirect.report(m)["probes_run"] == 0
+
+
+def test_record_estimate_statistics(auto_policy, monkeypatch):
+    """10 records, at most 4 probed: stride 10 // 4 = 2 -> records 0, 2, 4, 6; the four statistics and the estimate of
+    ops.INDIRECT_PROBE's formula, computed here in fp64."""
+    from tensoir_amd import indirect
+    ops = auto_policy
+    monkeypatch.setitem(ops.INDIRECT_PROBE, "records", 4)
+    gen = torch.Generator().manual_seed(11)
+    ref_all = torch.rand(10, 3, generator=gen)
+    cand = ref_all + 1e-5 * torch.randn(10, 3, generator=gen) + torch.tensor([2e-5, 0.0, -1e-5])
+    cand = torch.cat([cand, torch.full((2, 3), 9.0)])                   # rows beyond n_valid: never read
+    asked = []
+
+    def decode_full_subset(sel):
+        asked.append(sel.tolist())
+        return ref_all[sel]
+    ok, st = indirect.record_estimate(cand, 10, decode_full_subset)
+    assert asked == [[0, 2, 4, 6]] and st["kind"] == "records" and st["records"] == 4 and st["of"] == 10
+    sel = torch.tensor([0, 2, 4, 6])
+    d = (cand[sel] - ref_all[sel]).double()
+    bias, rms, mx = float(d.mean(0).abs().max()), float(d.pow(2).mean().sqrt()), float(d.abs().max())
+    lim = ops.INDIRECT_PROBE
+    est = max(lim["w_bias"] * bias + lim["w_rms"] * rms, lim["w_max"] * mx)
+    assert st["bias"] == pytest.approx(bias, rel=1e-12) and st["rms"] == pytest.approx(rms, rel=1e-12)
+    assert st["max"] == pytest.approx(mx, rel=1e-12) and st["estimate"] == pytest.approx(est, rel=1e-12)
+    assert st["radiance_rms"] == pytest.approx(float(ref_all[sel].double().pow(2).mean().sqrt()), rel=1e-12)
+    assert ok == (est <= lim["limit"]) and ok                           # (a few 1e-5: inside the 2.5e-5 limit)
+    # outside the limit, and a NaN row: rejected
+    assert not indirect.record_estimate(cand + 1e-3, 10, decode_full_subset)[0]
+    bad = cand.clone()
+    bad[2, 1] = float("nan")
+    assert not indirect.record_estimate(bad, 10, decode_full_subset)[0]
+    # fewer valid records than rows, and none at all
+    assert indirect.record_estimate(cand, 3, decode_full_subset)[1]["records"] == 3 and asked[-1] == [0, 1, 2]
+    assert indirect.record_estimate(cand, 0, decode_full_subset) == (True, {"records": 0})
+
+
+def test_learn_capacity():
+    """The record-capacity hint of every stage (primary forward, training forward, secondary march, bake)."""
+    from tensoir_amd.ops import learn_capacity
+    h = {}
+    learn_capacity(h, "k", 1000, 1.25, max_entries=64)
+    assert h == {"k": 16384}                                             # the floor of 16 k rows
+    learn_capacity(h, "k", 100000, 1.25, max_entries=64)
+    assert h["k"] == 129096                                              # 1.25 x the count + 4096
+    learn_capacity(h, "c", 100000, 1.25, ceiling=120000, max_entries=64)
+    assert h["c"] == 120000
+    h["d"] = 1000000
+    learn_capacity(h, "d", 1000, 1.25, max_entries=64)
+    assert h["d"] == 970000                                              # decays slowly from a heavy call
+    h["d"] = 1000000
+    learn_capacity(h, "d", 1000, 1.5, decay=0, max_entries=32)
+    assert h["d"] == 16384                                               # ... unless the caller asks for no memory
+    learn_capacity(h, "s", 100000, 1.5, max_entries=32)
+    assert h["s"] == 154096
+    # a table above max_entries is emptied BEFORE the old value is read
+    h = {i: 1000000 for i in range(33)}
+    learn_capacity(h, 5, 1000, 1.5, max_entries=32)
+    assert h == {5: 16384}
+    h = {i: 1000000 for i in range(32)}
+    learn_capacity(h, 5, 1000, 1.5, max_entries=32)
+    assert len(h) == 32 and h[5] == 970000
 
 
 def test_half_range_bound():
