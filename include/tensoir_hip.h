@@ -834,6 +834,51 @@ int tir_ccl_table(const int32_t* labels, int32_t gx, int32_t gy, int32_t gz, con
 int tir_ccl_filter(const float* vol, const int32_t* labels, int32_t gx, int32_t gy, int32_t gz, float level,
                    const int32_t* roots, const uint8_t* keep, int32_t n_comp, float fill, float* out, void* stream);
 
+/* ---- Mesh simplification by quadric vertex clustering (Rossignac-Borrel clusters, Lindstrom's quadric representative):
+ *      a face budget for the exported mesh that keeps the full-resolution surface as its input.
+ *   verts [V][3] fp32, faces [F][3] int32; cell[3] > 0, origin[3] (HOST floats), dims[3] >= 1 (HOST int32), reg >= 0.
+ *   1. cell of a vertex: q = (v - origin) / cell, an fp32 subtract and an fp32 IEEE divide, each rounded on its own;
+ *      i = clamp(floor(q), 0, dims - 1) per axis (a NaN goes to 0); key = (ix * dims_y + iy) * dims_z + iz.  Everything below
+ *      takes the fp32 q as its input and works in cell units.
+ *   2. output vertices = the occupied cells in ascending key order; cell_of_vertex [V] maps input to output vertices.
+ *   3. per cell c, in its local frame u = q - (i_c + 0.5): from its vertices m = count, s = sum u; from every face corner whose
+ *      vertex lies in c (once per corner), with n = (q1 - q0) x (q2 - q0), l = |n| (l = 0 faces skipped):
+ *      A += n n^T / l,  b += n (n . (q0 - (i_c + 0.5))) / l,  N += n.
+ *   4. mu = s / m, t = trace A; x = mu when t = 0, else the solution of (A + reg t I) x = b + reg t mu (mu as well when that
+ *      solution is not finite: reg = 0 with a rank-deficient A); x is clamped to [-0.5, 0.5]^3.
+ *      out_verts = origin + (i_c + 0.5 + x) * cell; out_normals = normalize(N / cell) -- the direction of the summed area
+ *      normals in the coordinates of verts -- or (0, 0, 1) when N = 0.
+ *   5. faces are remapped through cell_of_vertex; a face with two equal corners is dropped, the others keep their input order
+ *      and winding.  Duplicates stay, so a closed oriented input keeps count(a -> b) = count(b -> a) for every directed edge.
+ * Determinism: the sums of step 3 are 64-bit integer fixed point, added with integer atomics (order-independent); the per-face
+ * terms and the 3 x 3 solve are fp64.  No float atomics: two calls give bit-identical outputs.  The fixed-point scales assume
+ *   every face edge (q1 - q0, q2 - q0) and every vertex's u within TIR_SIMPLIFY_EXTENT cell edges per axis, F <= 2^28,
+ * which bounds every sum below 2^63 whatever the mesh: s has 30 fraction bits in one word; A, N and b take two words each (the
+ * value split at 2^-28, 2^-28 and 2^-24), 60, 60 and 56 fraction bits -- a cell that a sliver of the surface crosses has a tiny
+ * trace, and its solution needs the terms to that relative precision.  The bounds are checked on the
+ * device; status[2] collects TIR_SIMPLIFY_ERR_* bits and the caller must not use the outputs when it is non-zero.
+ * Use: tir_simplify_count keys the vertices into the dense workspace slots [dims_x * dims_y * dims_z], scans it (blocks of 4096:
+ * nbs = tir_simplify_blocks(slots), nbf = tir_simplify_blocks(F); counts [nbs + nbf], offsets [nbs + 1 + nbf + 1]), fills
+ * cell_of_vertex, counts the surviving faces and writes status [4] = {V', F', error bits, 0}; the caller reads status back (one
+ * 16-byte copy), allocates, and tir_simplify_emit accumulates into acc [V'][TIR_SIMPLIFY_ACC] (int64 workspace; keys [V'] int32
+ * receives each output vertex's cell key), solves and compacts the faces.  V = 0 or F = 0 is valid.  No access leaves the
+ * buffers for any input: cell indices are clamped, a face index outside [0, V) sets TIR_SIMPLIFY_ERR_FACE_INDEX and the face is
+ * skipped everywhere.  Host validation before any device work: a null pointer, cell <= 0 (or NaN), dims < 1, reg < 0 (or NaN),
+ * a negative count -> TIR_ERR_ARG; more than 2^31-1 slots or vertices, or F > 2^28 -> TIR_ERR_UNSUPPORTED. */
+#define TIR_SIMPLIFY_EXTENT 4
+#define TIR_SIMPLIFY_ACC 28
+#define TIR_SIMPLIFY_ERR_FACE_INDEX  1   /* a face index outside [0, V)                                          */
+#define TIR_SIMPLIFY_ERR_FACE_EXTENT 2   /* a face edge longer than TIR_SIMPLIFY_EXTENT cells along an axis (or NaN)  */
+#define TIR_SIMPLIFY_ERR_VERTEX      4   /* a vertex more than TIR_SIMPLIFY_EXTENT - 0.5 cells outside the lattice (or NaN) */
+int64_t tir_simplify_blocks(int64_t n);
+int tir_simplify_count(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, const float* cell,
+                       const float* origin, const int32_t* dims, int32_t* slots, int32_t* cell_of_vertex, int32_t* counts,
+                       int32_t* offsets, int32_t* status, void* stream);
+int tir_simplify_emit(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, const float* cell,
+                      const float* origin, const int32_t* dims, double reg, const int32_t* cell_of_vertex,
+                      const int32_t* offsets, int32_t n_out_verts, int32_t n_out_faces, int64_t* acc, int32_t* keys,
+                      float* out_verts, float* out_normals, int32_t* out_faces, void* stream);
+
 /* ---- per-point bake of materials and direct lighting (tensoir_amd/bake.py).  Point p is marched inward from
  * origins[p] along dirs[p] by tir_march_secondary_fwd with records; the caller decodes every record (BRDF decoder output
  * rec_brdf [A][4] = albedo rgb + raw roughness, shading normal rec_normal [A][3]).

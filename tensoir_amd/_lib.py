@@ -164,6 +164,10 @@ SIGNATURES = {
     "tir_ccl_label": (C.c_int, [P, I32, I32, I32, F32, I32, P, P, P, P]),
     "tir_ccl_table": (C.c_int, [P, I32, I32, I32, P, I32, P, P, P, P]),
     "tir_ccl_filter": (C.c_int, [P, P, I32, I32, I32, F32, P, P, I32, F32, P, P]),
+    "tir_simplify_blocks": (I64, [I64]),
+    "tir_simplify_count": (C.c_int, [P, I64, P, I64, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(I32), P, P, P, P, P, P]),
+    "tir_simplify_emit": (C.c_int, [P, I64, P, I64, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(I32), C.c_double, P, P,
+                                    I32, I32, P, P, P, P, P, P]),
     "tir_bake_composite": (C.c_int, [P, P, P, P, P, P, P, P, P, C.POINTER(C.c_float), I64, I64, P, P]),
     "tir_irradiance_integrate": (C.c_int, [P, P, P, P, P, P, I64, I32, I32, P, P]),
 }

@@ -173,6 +173,8 @@ def main(argv=None):
     ap.add_argument("--min-component-voxels", type=int, default=None, metavar="N", help="drop components of fewer than N lattice "
                     "points")
     ap.add_argument("--connectivity", type=int, choices=(6, 26), default=6, help="what joins two lattice points into one component")
+    ap.add_argument("--simplify", type=int, default=None, metavar="K", help="reduce the mesh by quadric vertex clustering: one "
+                    "vertex per block of K x K x K lattice cells (K >= 2); the attributes are baked at the reduced vertices")
     a = ap.parse_args(argv)
     extra = {} if a.envmap is None else {"envmap_h": a.envmap[0], "envmap_w": a.envmap[1]}
     model = load_model(a.ckpt, "cuda", **extra)
@@ -180,10 +182,12 @@ def main(argv=None):
     report = {}
     nv, nf = mesh.export_mesh(model, a.out, a.level, grid, attributes=True, color=a.color, light_idx=a.light,
                               keep_largest=a.keep_largest, min_component_voxels=a.min_component_voxels,
-                              connectivity=a.connectivity, report=report)
-    if report:
+                              connectivity=a.connectivity, report=report, simplify=a.simplify)
+    if "table" in report:
         sizes, kept = report["table"]["sizes"].cpu(), report["kept"].cpu()
         print(f"components: dropped {int((~kept).sum())} of {kept.numel()} ({int(sizes[~kept].sum())} of {int(sizes.sum())} voxels)")
+    if "full" in report:
+        print(f"simplify {a.simplify}: {report['full'][0]} vertices, {report['full'][1]} faces before")
     print(f"{a.out}: {nv} vertices, {nf} faces")
 
 

@@ -566,8 +566,349 @@ int ccl_validate(int32_t gx, int32_t gy, int32_t gz, CclGrid* G) {
     return TIR_OK;
 }
 
+// ---- simplification by quadric vertex clustering (contract: include/tensoir_hip.h, tir_simplify_*) -----------------
+//   k_simplify_key            per vertex: cell key (fp32, every operation rounded on its own) -> cell_of_vertex, slots[key] = 1
+//   k_simplify_slots<false/true>  count per block of MC_BLOCK_POINTS slots / rewrite slots[key] = compact id (ascending keys), -1
+//   k_simplify_map            cell_of_vertex[v] = slots[key of v]
+//   k_simplify_faces<false/true>  per block of MC_BLOCK_POINTS faces: count the faces that survive the remap (and check indices
+//                             and extents) / write them at their scanned offsets, in input order
+//   k_simplify_status         {V', F'} next to the error word: one read-back
+//   k_simplify_accum_verts / _faces  the sums of a cell as integer fixed point, integer atomics whose value is never read back;
+//                             a face term takes two 64-bit words (the fixed-point value split at its low 32 bits), which gives
+//                             it 32 more fraction bits than one word could hold under the worst-case bound
+//   k_simplify_solve          per output vertex: the regularised 3 x 3 system in fp64, position and normal
+// The only order-dependent operations are integer additions, so the outputs do not depend on the order the device worked in.
+constexpr double SIMP_EXTENT = TIR_SIMPLIFY_EXTENT;
+constexpr int SIMP_ACC = TIR_SIMPLIFY_ACC;                 // m, s[3], then (high, low) word pairs of A[6] (00 01 02 11 12 22), b[3], N[3]
+constexpr int SIMP_A = 4, SIMP_B = 16, SIMP_N = 22;        // first word of each group
+constexpr int64_t SIMP_MAX_FACES = (int64_t)1 << 28;
+// fraction bits: |u| <= 4 over < 2^31 vertices; |n_i| <= 2 * 4^2 = 32 >= |A_ij|, |b_i| <= 32 * 8 sqrt(3) < 2^9 over < 2^30 corners
+constexpr double SIMP_S_SCALE = (double)(1 << 30), SIMP_A_SCALE = (double)(1 << 28), SIMP_B_SCALE = (double)(1 << 24),
+                 SIMP_N_SCALE = (double)(1 << 28);
+
+struct SimpGrid {
+    float cell[3], origin[3];
+    int32_t dims[3];
+};
+
+__device__ __forceinline__ void simp_q(const SimpGrid& G, const float* __restrict__ v, float q[3]) {
+#pragma unroll
+    for (int a = 0; a < 3; ++a) q[a] = __fdiv_rn(sub_rn(v[a], G.origin[a]), G.cell[a]);
+}
+
+// clamp(floor(q), 0, dim - 1); fmaxf returns its other operand for a NaN, and the comparison is made before the conversion
+__device__ __forceinline__ int simp_index(float q, int32_t dim) {
+    const float f = fmaxf(floorf(q), 0.0f);
+    return f >= (float)(dim - 1) ? dim - 1 : (int)f;
+}
+
+__device__ __forceinline__ int32_t simp_key(const SimpGrid& G, const int i[3]) {
+    return (int32_t)(((int64_t)i[0] * G.dims[1] + i[1]) * G.dims[2] + i[2]);       // < 2^31 (simp_validate)
+}
+
+__device__ __forceinline__ void simp_add(int64_t* p, double v, double scale, int mult) {
+    const long long w = __double2ll_rn(v * scale) * mult;
+    if (w) atomicAdd(reinterpret_cast<unsigned long long*>(p), (unsigned long long)w);
+}
+
+// v with 32 fraction bits more than `scale` gives one word: p[0] += floor(v scale), p[1] += round((v scale - floor) 2^32), the
+// latter in [0, 2^32] and so below 2^62 over 2^30 corners.  Every step before the rounding is exact (a power-of-two scale, the
+// difference of a value and its own floor), so the pair is the value rounded once at 2^-32 / scale.
+__device__ __forceinline__ void simp_add2(int64_t* p, double v, double scale, int mult) {
+    const double y = v * scale, h = floor(y);
+    const long long hi = (long long)h * mult;
+    const unsigned long long lo = (unsigned long long)__double2ll_rn((y - h) * 4294967296.0) * (unsigned)mult;
+    if (hi) atomicAdd(reinterpret_cast<unsigned long long*>(p), (unsigned long long)hi);
+    if (lo) atomicAdd(reinterpret_cast<unsigned long long*>(p + 1), lo);
+}
+
+// the value of a word pair: the whole part of the low word is carried into the high one first, so that sums whose terms cancel
+// come out exactly
+__device__ __forceinline__ double simp_value(const int64_t* p, double scale) {
+    const unsigned long long lo = (unsigned long long)p[1];
+    const long long hi = p[0] + (long long)(lo >> 32);
+    return ((double)hi + (double)(lo & 0xffffffffull) * (1.0 / 4294967296.0)) / scale;
+}
+
+__global__ void __launch_bounds__(MC_THREADS)
+k_simplify_key(const float* __restrict__ verts, int64_t V, SimpGrid G, int32_t* __restrict__ vkey, int32_t* __restrict__ slots,
+               int32_t* __restrict__ status) {
+    const int64_t v = (int64_t)blockIdx.x * MC_THREADS + threadIdx.x;
+    if (v >= V) return;
+    float q[3];
+    simp_q(G, verts + 3 * v, q);
+    int i[3];
+    bool ok = true;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        i[a] = simp_index(q[a], G.dims[a]);
+        ok = ok && fabs((double)q[a] - ((double)i[a] + 0.5)) <= SIMP_EXTENT;
+    }
+    const int32_t key = simp_key(G, i);
+    vkey[v] = key;
+    slots[key] = 1;                                        // (every writer of a slot writes the same value)
+    if (!ok) atomicOr(status + 2, TIR_SIMPLIFY_ERR_VERTEX);
+}
+
+template <bool EMIT>
+__global__ void __launch_bounds__(MC_THREADS)
+k_simplify_slots(int32_t* __restrict__ slots, int64_t n, int32_t* __restrict__ counts, const int32_t* __restrict__ offsets) {
+    __shared__ int wsum[MC_THREADS / 64];
+    const int64_t base = (int64_t)blockIdx.x * MC_BLOCK_POINTS;
+    int carry = EMIT ? offsets[blockIdx.x] : 0, nr = 0;
+    for (int it = 0; it < MC_ITERS; ++it) {
+        const int64_t p = base + it * MC_THREADS + threadIdx.x;
+        const int used = p < n && slots[p] != 0;
+        if constexpr (EMIT) {
+            int tot;
+            const int o = carry + mc_block_scan(used, wsum, &tot);
+            carry += tot;
+            if (p < n) slots[p] = used ? o : -1;
+        } else {
+            nr += used;
+        }
+    }
+    if constexpr (!EMIT) {
+        nr = mc_block_sum(nr, wsum);
+        if (threadIdx.x == 0) counts[blockIdx.x] = nr;
+    }
+}
+
+__global__ void __launch_bounds__(MC_THREADS)
+k_simplify_map(int32_t* __restrict__ cell_of_vertex, int64_t V, const int32_t* __restrict__ slots) {
+    const int64_t v = (int64_t)blockIdx.x * MC_THREADS + threadIdx.x;
+    if (v < V) cell_of_vertex[v] = slots[cell_of_vertex[v]];      // (holds the key, which k_simplify_key formed inside the slots)
+}
+
+// the corners of face f, or false when an index lies outside [0, V)
+__device__ __forceinline__ bool simp_face(const int32_t* __restrict__ faces, int64_t f, int64_t V, int32_t idx[3]) {
+    bool ok = true;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        idx[k] = faces[3 * f + k];
+        ok = ok && idx[k] >= 0 && idx[k] < V;
+    }
+    return ok;
+}
+
+// the edges q1 - q0 and q2 - q0 in fp64 (differences of fp32 values: exact), or false beyond the extent the scales assume
+__device__ __forceinline__ bool simp_edges(const float q[3][3], double e1[3], double e2[3]) {
+    bool ok = true;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        e1[a] = (double)q[1][a] - (double)q[0][a];
+        e2[a] = (double)q[2][a] - (double)q[0][a];
+        ok = ok && fabs(e1[a]) <= SIMP_EXTENT && fabs(e2[a]) <= SIMP_EXTENT;       // (false for a NaN)
+    }
+    return ok;
+}
+
+template <bool EMIT>
+__global__ void __launch_bounds__(MC_THREADS)
+k_simplify_faces(const float* __restrict__ verts, const int32_t* __restrict__ faces, int64_t F, int64_t V, SimpGrid G,
+                 const int32_t* __restrict__ cell_of_vertex, int32_t* __restrict__ counts, const int32_t* __restrict__ offsets,
+                 int32_t n_out_faces, int32_t* __restrict__ out_faces, int32_t* __restrict__ status) {
+    __shared__ int wsum[MC_THREADS / 64];
+    const int64_t base = (int64_t)blockIdx.x * MC_BLOCK_POINTS;
+    int carry = EMIT ? offsets[blockIdx.x] : 0, nk = 0;
+    for (int it = 0; it < MC_ITERS; ++it) {
+        const int64_t f = base + it * MC_THREADS + threadIdx.x;
+        int32_t idx[3], c[3] = {0, 0, 0};
+        int keep = 0;
+        if (f < F) {
+            if (simp_face(faces, f, V, idx)) {
+#pragma unroll
+                for (int k = 0; k < 3; ++k) c[k] = cell_of_vertex[idx[k]];
+                keep = c[0] != c[1] && c[1] != c[2] && c[0] != c[2];
+                if constexpr (!EMIT) {
+                    float q[3][3];
+                    double e1[3], e2[3];
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) simp_q(G, verts + 3 * (int64_t)idx[k], q[k]);
+                    if (!simp_edges(q, e1, e2)) atomicOr(status + 2, TIR_SIMPLIFY_ERR_FACE_EXTENT);
+                }
+            } else if constexpr (!EMIT) {
+                atomicOr(status + 2, TIR_SIMPLIFY_ERR_FACE_INDEX);
+            }
+        }
+        if constexpr (EMIT) {
+            int tot;
+            const int o = carry + mc_block_scan(keep, wsum, &tot);
+            carry += tot;
+            if (keep && o < n_out_faces) {
+#pragma unroll
+                for (int k = 0; k < 3; ++k) out_faces[(int64_t)o * 3 + k] = c[k];
+            }
+        } else {
+            nk += keep;
+        }
+    }
+    if constexpr (!EMIT) {
+        nk = mc_block_sum(nk, wsum);
+        if (threadIdx.x == 0) counts[blockIdx.x] = nk;
+    }
+}
+
+__global__ void k_simplify_status(const int32_t* __restrict__ slot_total, const int32_t* __restrict__ face_total,
+                                  int32_t* __restrict__ status) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    status[0] = *slot_total;
+    status[1] = *face_total;
+}
+
+__global__ void __launch_bounds__(MC_THREADS)
+k_simplify_accum_verts(const float* __restrict__ verts, int64_t V, SimpGrid G, const int32_t* __restrict__ cell_of_vertex,
+                       int32_t n_out, int64_t* __restrict__ acc, int32_t* __restrict__ keys) {
+    const int64_t v = (int64_t)blockIdx.x * MC_THREADS + threadIdx.x;
+    if (v >= V) return;
+    const int32_t c = cell_of_vertex[v];
+    if (c < 0 || c >= n_out) return;
+    float q[3];
+    simp_q(G, verts + 3 * v, q);
+    int i[3];
+    double u[3];
+    bool ok = true;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        i[a] = simp_index(q[a], G.dims[a]);
+        u[a] = (double)q[a] - ((double)i[a] + 0.5);
+        ok = ok && fabs(u[a]) <= SIMP_EXTENT;
+    }
+    keys[c] = simp_key(G, i);                              // (every vertex of a cell writes the same key)
+    if (!ok) return;                                       // reported by k_simplify_key; never added, so no sum can overflow
+    int64_t* A = acc + (int64_t)c * SIMP_ACC;
+    atomicAdd(reinterpret_cast<unsigned long long*>(A), 1ull);
+#pragma unroll
+    for (int a = 0; a < 3; ++a) simp_add(A + 1 + a, u[a], SIMP_S_SCALE, 1);
+}
+
+__global__ void __launch_bounds__(MC_THREADS)
+k_simplify_accum_faces(const float* __restrict__ verts, const int32_t* __restrict__ faces, int64_t F, int64_t V, SimpGrid G,
+                       const int32_t* __restrict__ cell_of_vertex, int32_t n_out, int64_t* __restrict__ acc) {
+    const int64_t f = (int64_t)blockIdx.x * MC_THREADS + threadIdx.x;
+    if (f >= F) return;
+    int32_t idx[3];
+    if (!simp_face(faces, f, V, idx)) return;
+    float q[3][3];
+    double e1[3], e2[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) simp_q(G, verts + 3 * (int64_t)idx[k], q[k]);
+    if (!simp_edges(q, e1, e2)) return;
+    const double n[3] = {e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0]};
+    const double l = sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
+    if (!(l > 0.0)) return;
+    const double inv = 1.0 / l;
+    int32_t c[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) c[k] = cell_of_vertex[idx[k]];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        // corners that share a cell share every term (the same centre): the first of them adds the integer terms for all
+        int mult = 1;
+        bool first = true;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            if (j < k && c[j] == c[k]) first = false;
+            if (j > k && c[j] == c[k]) ++mult;
+        }
+        if (!first || c[k] < 0 || c[k] >= n_out) continue;
+        double dn = 0.0;
+        bool ok = true;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            const double ctr = (double)simp_index(q[k][a], G.dims[a]) + 0.5;
+            ok = ok && fabs((double)q[k][a] - ctr) <= SIMP_EXTENT;
+            dn += n[a] * ((double)q[0][a] - ctr);
+        }
+        if (!ok) continue;
+        int64_t* A = acc + (int64_t)c[k] * SIMP_ACC;
+        simp_add2(A + SIMP_A, n[0] * n[0] * inv, SIMP_A_SCALE, mult);
+        simp_add2(A + SIMP_A + 2, n[0] * n[1] * inv, SIMP_A_SCALE, mult);
+        simp_add2(A + SIMP_A + 4, n[0] * n[2] * inv, SIMP_A_SCALE, mult);
+        simp_add2(A + SIMP_A + 6, n[1] * n[1] * inv, SIMP_A_SCALE, mult);
+        simp_add2(A + SIMP_A + 8, n[1] * n[2] * inv, SIMP_A_SCALE, mult);
+        simp_add2(A + SIMP_A + 10, n[2] * n[2] * inv, SIMP_A_SCALE, mult);
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            simp_add2(A + SIMP_B + 2 * a, n[a] * dn * inv, SIMP_B_SCALE, mult);
+            simp_add2(A + SIMP_N + 2 * a, n[a], SIMP_N_SCALE, mult);
+        }
+    }
+}
+
+__global__ void __launch_bounds__(MC_THREADS)
+k_simplify_solve(const int64_t* __restrict__ acc, const int32_t* __restrict__ keys, int32_t n_out, SimpGrid G, double reg,
+                 float* __restrict__ out_verts, float* __restrict__ out_normals) {
+    const int64_t c = (int64_t)blockIdx.x * MC_THREADS + threadIdx.x;
+    if (c >= n_out) return;
+    const int64_t* A = acc + c * SIMP_ACC;
+    const double m = (double)A[0];
+    double mu[3], b[3], N[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        mu[a] = m > 0.0 ? (double)A[1 + a] / SIMP_S_SCALE / m : 0.0;
+        b[a] = simp_value(A + SIMP_B + 2 * a, SIMP_B_SCALE);
+        N[a] = simp_value(A + SIMP_N + 2 * a, SIMP_N_SCALE);
+    }
+    const double a00 = simp_value(A + SIMP_A, SIMP_A_SCALE), a01 = simp_value(A + SIMP_A + 2, SIMP_A_SCALE),
+                 a02 = simp_value(A + SIMP_A + 4, SIMP_A_SCALE), a11 = simp_value(A + SIMP_A + 6, SIMP_A_SCALE),
+                 a12 = simp_value(A + SIMP_A + 8, SIMP_A_SCALE), a22 = simp_value(A + SIMP_A + 10, SIMP_A_SCALE);
+    const double t = a00 + a11 + a22;
+    double x[3] = {mu[0], mu[1], mu[2]};
+    if (t > 0.0) {
+        const double r = reg * t;
+        const double p = a00 + r, d = a11 + r, g = a22 + r;
+        const double r0 = b[0] + r * mu[0], r1 = b[1] + r * mu[1], r2 = b[2] + r * mu[2];
+        // symmetric positive definite with condition <= about 1 / reg: the cofactor form in fp64 is ample
+        const double c00 = d * g - a12 * a12, c01 = a02 * a12 - a01 * g, c02 = a01 * a12 - a02 * d;
+        const double c11 = p * g - a02 * a02, c12 = a01 * a02 - p * a12, c22 = p * d - a01 * a01;
+        const double idet = 1.0 / (p * c00 + a01 * c01 + a02 * c02);
+        const double s0 = (c00 * r0 + c01 * r1 + c02 * r2) * idet, s1 = (c01 * r0 + c11 * r1 + c12 * r2) * idet,
+                     s2 = (c02 * r0 + c12 * r1 + c22 * r2) * idet;
+        if (fabs(s0) < INFINITY && fabs(s1) < INFINITY && fabs(s2) < INFINITY) { x[0] = s0; x[1] = s1; x[2] = s2; }
+    }
+    // the cell's index from its key: 32-bit divisions (the key is below 2^31)
+    const uint32_t key = (uint32_t)keys[c], kr = key / (uint32_t)G.dims[2];
+    const uint32_t ix = kr / (uint32_t)G.dims[1];
+    const int i[3] = {(int)ix, (int)(kr - ix * (uint32_t)G.dims[1]), (int)(key - kr * (uint32_t)G.dims[2])};
+    double nw[3], ss = 0.0;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const double xa = fmin(fmax(x[a], -0.5), 0.5);
+        out_verts[3 * c + a] = (float)((double)G.origin[a] + ((double)i[a] + 0.5 + xa) * (double)G.cell[a]);
+        nw[a] = N[a] / (double)G.cell[a];
+        ss += nw[a] * nw[a];
+    }
+    const bool flat = N[0] == 0.0 && N[1] == 0.0 && N[2] == 0.0;         // exact: opposite terms cancel in the integer sums
+    const double inv = flat ? 0.0 : 1.0 / sqrt(ss);
+    out_normals[3 * c] = (float)(nw[0] * inv);
+    out_normals[3 * c + 1] = (float)(nw[1] * inv);
+    out_normals[3 * c + 2] = flat ? 1.0f : (float)(nw[2] * inv);
+}
+
+// host-side validation shared by the tir_simplify_* entries: 0, or a negative TIR_ERR_*; fills the grid and the slot count
+int simp_validate(int64_t V, int64_t F, const float* cell, const float* origin, const int32_t* dims, SimpGrid* G, int64_t* slots) {
+    if (!cell || !origin || !dims || V < 0 || F < 0) return TIR_ERR_ARG;
+    int64_t n = 1;
+    for (int a = 0; a < 3; ++a) {
+        if (!(cell[a] > 0.0f) || dims[a] < 1) return TIR_ERR_ARG;
+        G->cell[a] = cell[a];
+        G->origin[a] = origin[a];
+        G->dims[a] = dims[a];
+    }
+    for (int a = 0; a < 3; ++a) {
+        n *= dims[a];                                      // each factor is below 2^31 and n is checked after every one
+        if (n > INT32_MAX) return TIR_ERR_UNSUPPORTED;
+    }
+    if (V > INT32_MAX || F > SIMP_MAX_FACES) return TIR_ERR_UNSUPPORTED;
+    *slots = n;
+    return TIR_OK;
+}
+
+constexpr int64_t simp_blocks(int64_t n, int per) { return (n + per - 1) / per; }
+
 // ---- per-vertex bake -------------------------------------------------------------------------------------------------------
-constexpr int BAKE_LANES = 8;         // a trained surface leaves 5-30 records per ray: 1-4 strides of the segment per lane
+constexpr int BAKE_LANES = 8;        // a trained surface leaves 5-30 records per ray: 1-4 strides of the segment per lane
 constexpr int BAKE_THREADS = 256;
 constexpr int BAKE_ROW = 16;           // floats per output row (TIR_BAKE_ROW)
 
@@ -743,6 +1084,89 @@ extern "C" int tir_irradiance_integrate(const float* rows, const float* dirs, co
         hipLaunchKernelGGL(k_irradiance_integrate<false>, dim3((unsigned)nblk), dim3(BAKE_THREADS), 0, tir_stream(stream), rows,
                            dirs, vis, env, weight_d, light_idx, M, (int)D, (int)n_lights, out);
     TIR_CHECK_LAUNCH();
+    return TIR_OK;
+}
+
+extern "C" int64_t tir_simplify_blocks(int64_t n) { return n < 0 ? TIR_ERR_ARG : simp_blocks(n, MC_BLOCK_POINTS); }
+
+extern "C" int tir_simplify_count(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, const float* cell,
+                                  const float* origin, const int32_t* dims, int32_t* slots, int32_t* cell_of_vertex,
+                                  int32_t* counts, int32_t* offsets, int32_t* status, void* stream) {
+    SimpGrid G;
+    int64_t n_slots = 0;
+    const int rc = simp_validate(n_verts, n_faces, cell, origin, dims, &G, &n_slots);
+    if (rc) return rc;
+    if (!slots || !counts || !offsets || !status) return TIR_ERR_ARG;
+    if ((n_verts > 0 && (!verts || !cell_of_vertex)) || (n_faces > 0 && !faces)) return TIR_ERR_ARG;
+    const int64_t nbs = simp_blocks(n_slots, MC_BLOCK_POINTS), nbf = simp_blocks(n_faces, MC_BLOCK_POINTS);
+    hipStream_t st = tir_stream(stream);
+    hipError_t e = hipMemsetAsync(slots, 0, (size_t)n_slots * sizeof(int32_t), st);
+    if (e == hipSuccess) e = hipMemsetAsync(status, 0, 4 * sizeof(int32_t), st);
+    if (e != hipSuccess) return -(int)e;
+    if (n_verts > 0) {
+        hipLaunchKernelGGL(k_simplify_key, dim3((unsigned)simp_blocks(n_verts, MC_THREADS)), dim3(MC_THREADS), 0, st, verts, n_verts,
+                           G, cell_of_vertex, slots, status);
+        TIR_CHECK_LAUNCH();
+    }
+    hipLaunchKernelGGL(k_simplify_slots<false>, dim3((unsigned)nbs), dim3(MC_THREADS), 0, st, slots, n_slots, counts,
+                       (const int32_t*)nullptr);
+    TIR_CHECK_LAUNCH();
+    int src = tir_exclusive_scan(counts, offsets, (int32_t)nbs, stream);
+    if (src) return src;
+    hipLaunchKernelGGL(k_simplify_slots<true>, dim3((unsigned)nbs), dim3(MC_THREADS), 0, st, slots, n_slots, (int32_t*)nullptr,
+                       (const int32_t*)offsets);
+    TIR_CHECK_LAUNCH();
+    if (n_verts > 0) {
+        hipLaunchKernelGGL(k_simplify_map, dim3((unsigned)simp_blocks(n_verts, MC_THREADS)), dim3(MC_THREADS), 0, st,
+                           cell_of_vertex, n_verts, (const int32_t*)slots);
+        TIR_CHECK_LAUNCH();
+    }
+    if (n_faces > 0) {
+        hipLaunchKernelGGL(k_simplify_faces<false>, dim3((unsigned)nbf), dim3(MC_THREADS), 0, st, verts, faces, n_faces, n_verts, G,
+                           (const int32_t*)cell_of_vertex, counts + nbs, (const int32_t*)nullptr, 0, (int32_t*)nullptr, status);
+        TIR_CHECK_LAUNCH();
+    }
+    src = tir_exclusive_scan(counts + nbs, offsets + nbs + 1, (int32_t)nbf, stream);
+    if (src) return src;
+    hipLaunchKernelGGL(k_simplify_status, dim3(1), dim3(64), 0, st, (const int32_t*)(offsets + nbs),
+                       (const int32_t*)(offsets + nbs + 1 + nbf), status);
+    TIR_CHECK_LAUNCH();
+    return TIR_OK;
+}
+
+extern "C" int tir_simplify_emit(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, const float* cell,
+                                 const float* origin, const int32_t* dims, double reg, const int32_t* cell_of_vertex,
+                                 const int32_t* offsets, int32_t n_out_verts, int32_t n_out_faces, int64_t* acc, int32_t* keys,
+                                 float* out_verts, float* out_normals, int32_t* out_faces, void* stream) {
+    SimpGrid G;
+    int64_t n_slots = 0;
+    const int rc = simp_validate(n_verts, n_faces, cell, origin, dims, &G, &n_slots);
+    if (rc) return rc;
+    if (!(reg >= 0.0) || n_out_verts < 0 || n_out_faces < 0 || n_out_verts > n_verts || n_out_faces > n_faces) return TIR_ERR_ARG;
+    if (n_out_verts == 0) return n_out_faces == 0 ? TIR_OK : TIR_ERR_ARG;
+    if (!verts || !cell_of_vertex || !acc || !keys || !out_verts || !out_normals) return TIR_ERR_ARG;
+    if (n_faces > 0 && !faces) return TIR_ERR_ARG;
+    if (n_out_faces > 0 && (!offsets || !out_faces)) return TIR_ERR_ARG;
+    const int64_t nbs = simp_blocks(n_slots, MC_BLOCK_POINTS), nbf = simp_blocks(n_faces, MC_BLOCK_POINTS);
+    hipStream_t st = tir_stream(stream);
+    const hipError_t e = hipMemsetAsync(acc, 0, (size_t)n_out_verts * SIMP_ACC * sizeof(int64_t), st);
+    if (e != hipSuccess) return -(int)e;
+    hipLaunchKernelGGL(k_simplify_accum_verts, dim3((unsigned)simp_blocks(n_verts, MC_THREADS)), dim3(MC_THREADS), 0, st, verts,
+                       n_verts, G, cell_of_vertex, n_out_verts, acc, keys);
+    TIR_CHECK_LAUNCH();
+    if (n_faces > 0) {
+        hipLaunchKernelGGL(k_simplify_accum_faces, dim3((unsigned)simp_blocks(n_faces, MC_THREADS)), dim3(MC_THREADS), 0, st, verts,
+                           faces, n_faces, n_verts, G, cell_of_vertex, n_out_verts, acc);
+        TIR_CHECK_LAUNCH();
+    }
+    hipLaunchKernelGGL(k_simplify_solve, dim3((unsigned)simp_blocks(n_out_verts, MC_THREADS)), dim3(MC_THREADS), 0, st,
+                       (const int64_t*)acc, (const int32_t*)keys, n_out_verts, G, reg, out_verts, out_normals);
+    TIR_CHECK_LAUNCH();
+    if (n_out_faces > 0) {
+        hipLaunchKernelGGL(k_simplify_faces<true>, dim3((unsigned)nbf), dim3(MC_THREADS), 0, st, verts, faces, n_faces, n_verts, G,
+                           cell_of_vertex, (int32_t*)nullptr, offsets + nbs + 1, n_out_faces, out_faces, (int32_t*)nullptr);
+        TIR_CHECK_LAUNCH();
+    }
     return TIR_OK;
 }
 

@@ -4,6 +4,7 @@
     extract_mesh(model, keep_largest=1)                  # ... without the detached blobs ("floaters"): tir_ccl_* on the lattice
     export_mesh(model, "scene.ply")                      # + binary PLY, laid out as plyfile writes the reference's mesh
     export_mesh(model, "scene.ply", attributes=True)     # + per-vertex materials and direct lighting (tensoir_amd/bake.py)
+    export_mesh(model, "scene.ply", simplify=3)          # a face budget: one vertex per 3 x 3 x 3 block of cells (tir_simplify_*)
 
 Coordinates follow the reference, quirk included (Appendix B policy: parity first): convert_sdf_samples_to_ply takes the voxel
 size as (aabb[1] - aabb[0]) / shape -- `shape`, not `shape - 1` (utils.py:186) -- although getDenseAlpha's lattice spans the
@@ -216,6 +217,29 @@ def _check_component_options(keep_largest, min_component_voxels, connectivity):
     return keep_largest is not None or min_component_voxels is not None
 
 
+def _check_simplify(simplify):
+    """-> the cluster size k, or None.  Raises before anything touches the device."""
+    if simplify is None:
+        return None
+    if isinstance(simplify, bool) or not isinstance(simplify, (int, np.integer)):
+        raise ValueError(f"simplify: expected an integer >= 2 or None, not {simplify!r}")
+    if simplify < 2:
+        raise ValueError(f"simplify: must be >= 2, not {simplify}")
+    return int(simplify)
+
+
+def simplify_extracted(verts, faces, aabb, grid, k, reg=1e-2):
+    """ops.simplify_mesh on a mesh of extract_mesh with clusters of k x k x k marching-cubes cells: cell = k *
+    reference_spacing, origin = aabb[0], dims = (g - 1) // k + 1.  -> (verts', faces', INDEX-space unit normals, cell_of_vertex);
+    the normals are normalize(n' * reference_spacing), what field_positions expects of marching cubes' own."""
+    aabb = torch.as_tensor(aabb).detach().to("cpu", torch.float32).reshape(2, 3)
+    sp = torch.tensor(reference_spacing(aabb, grid), dtype=torch.float32)
+    cell = (sp * float(k)).tolist()
+    v, f, n, cov = ops.simplify_mesh(verts, faces, cell, aabb[0].tolist(), [(int(g) - 1) // k + 1 for g in grid], reg)
+    n = n * sp.to(n.device)
+    return v, f, n / torch.linalg.norm(n, dim=-1, keepdim=True).clamp(min=1e-20), cov
+
+
 def _model_grid(model, gridSize):
     return [int(g) for g in (model.gridSize if gridSize is None else gridSize)]
 
@@ -246,13 +270,18 @@ def _filtered_alpha(alpha, level, keep_largest, min_component_voxels, connectivi
 
 @torch.no_grad()
 def extract_mesh(model, level=0.005, gridSize=None, *, keep_largest=None, min_component_voxels=None, connectivity=6,
-                 report=None):
+                 report=None, simplify=None):
     """getDenseAlpha(gridSize) (default: the model's gridSize) -> marching cubes at `level` in the reference's coordinates
     (module docstring).  -> (verts [V, 3] f32, faces [F, 3] i32 outward, normals [V, 3] f32), on the model's device.
     keep_largest / min_component_voxels (select_components): the lattice's components under `connectivity` that fail the
     selection are set to 0 before marching cubes.  With connectivity 6 that removes whole closed surfaces and leaves every kept
-    vertex bit-identical.  Needs level >= 0.  With both None no labelling kernel runs."""
+    vertex bit-identical.  Needs level >= 0.  With both None no labelling kernel runs.
+    simplify=k (an integer >= 2): the mesh is then reduced by quadric vertex clustering over blocks of k x k x k marching-cubes
+    cells (simplify_extracted; the component filter runs first, on the lattice); the normals are the clusters' summed face
+    normals in index space.  report (a dict) receives "full" = (vertices, faces) before the reduction.  With None no
+    simplification kernel runs."""
     filtering = _check_component_options(keep_largest, min_component_voxels, connectivity)
+    k = _check_simplify(simplify)
     grid = _model_grid(model, gridSize)
     alpha, _ = ops.dense_alpha(model.packed_field(), grid, float(model.stepSize))   # getDenseAlpha's alpha, no xyz lattice
     if filtering:
@@ -260,20 +289,26 @@ def extract_mesh(model, level=0.005, gridSize=None, *, keep_largest=None, min_co
         if report is not None:
             report.update(table=table, kept=kept)
     aabb = model.aabb.detach().to("cpu", torch.float32)
-    return ops.marching_cubes(alpha, level, reference_spacing(aabb, grid), aabb[0].tolist())
+    verts, faces, normals = ops.marching_cubes(alpha, level, reference_spacing(aabb, grid), aabb[0].tolist())
+    if k is None:
+        return verts, faces, normals
+    if report is not None:
+        report["full"] = (verts.shape[0], faces.shape[0])
+    return simplify_extracted(verts, faces, aabb, grid, k)[:3]
 
 
 @torch.no_grad()
 def export_mesh(model, path, level=0.005, gridSize=None, attributes=False, color="albedo", *, keep_largest=None,
-                min_component_voxels=None, connectivity=6, report=None, **bake_kw):
+                min_component_voxels=None, connectivity=6, report=None, simplify=None, **bake_kw):
     """extract_mesh + write_ply -> (number of vertices, number of faces).
     attributes=True: the vertex element becomes ATTRIBUTE_LAYOUT -- positions (bit-identical to the plain export), the baked
     shading normal, a display colour (vertex_colors), roughness, ambient occlusion, coverage, albedo and direct irradiance of
     bake.bake_points(model, *field_positions(...), **bake_kw); the face element is unchanged.
     keep_largest / min_component_voxels / connectivity: extract_mesh's component filter (floaters are neither written nor
-    baked)."""
+    baked).  simplify=k: extract_mesh's face budget; the attributes are then baked at the simplified vertices."""
     verts, faces, normals = extract_mesh(model, level, gridSize, keep_largest=keep_largest,
-                                         min_component_voxels=min_component_voxels, connectivity=connectivity, report=report)
+                                         min_component_voxels=min_component_voxels, connectivity=connectivity, report=report,
+                                         simplify=simplify)
     if not attributes:
         if bake_kw or color != "albedo":
             raise TypeError("color and the bake arguments need attributes=True")

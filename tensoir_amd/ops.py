@@ -1550,6 +1550,71 @@ def keep_components(vol, labels, table, keep, fill=0.0, level=None):
     return out
 
 
+SIMPLIFY_ACC = 28
+_SIMPLIFY_ERRORS = ((1, "a face index lies outside [0, V)"),
+                    (2, "a face edge is longer than 4 cells along an axis (or not finite)"),
+                    (4, "a vertex lies more than 3.5 cells outside the lattice of cells (or is not finite)"))
+
+
+def simplify_mesh(verts, faces, cell, origin=(0.0, 0.0, 0.0), dims=None, reg=1e-2):
+    """Quadric vertex clustering (tir_simplify_count + tir_simplify_emit; the definition: include/tensoir_hip.h).  verts [V, 3]
+    f32 and faces [F, 3] i32 on the GPU; cell: the cluster's edge (one value or three), origin: the corner of cell (0, 0, 0),
+    dims: cells per axis -- None takes floor(max((v - origin) / cell)) + 1 per axis, one extra reduction and read-back.
+    -> (verts' [V', 3] f32, faces' [F', 3] i32, normals' [V', 3] f32, cell_of_vertex [V] i32), all on verts' device: one vertex
+    per occupied cell in ascending cell order, placed where the summed plane quadrics of the cell's faces are smallest
+    (regularised toward the mean of its vertices by `reg`, clamped to the cell); faces that collapse are dropped, the others
+    keep order and winding.  Two calls give identical bits.  The two totals and an error word are read back once (16 bytes,
+    one sync); a face index outside [0, V), or a face / vertex beyond the extent the fixed-point sums are scaled for, raises."""
+    verts = f32(verts, "verts", 3).view(-1, 3)
+    faces = i32(faces, "faces").view(-1, 3)
+    dev = verts.device
+    if faces.device != dev:
+        raise ValueError("faces: expected the device of verts")
+    V, F = verts.shape[0], faces.shape[0]
+    cl = [float(cell)] * 3 if isinstance(cell, (int, float)) else [float(c) for c in cell]
+    org = [float(o) for o in origin]
+    if len(cl) != 3 or len(org) != 3:
+        raise ValueError("cell takes one or three values, origin three")
+    if dims is None:
+        if V and all(c > 0 for c in cl):
+            q = (verts - torch.tensor(org, dtype=torch.float32, device=dev)) / torch.tensor(cl, dtype=torch.float32, device=dev)
+            top = torch.nan_to_num(q, nan=0.0, posinf=0.0, neginf=0.0).amax(0).floor().clamp(0, 2.0 ** 31 - 256).cpu()
+            dims = [int(t) + 1 for t in top]
+        else:
+            dims = [1, 1, 1]
+    dm = [int(d) for d in dims]
+    if len(dm) != 3:
+        raise ValueError("dims takes three values")
+    c_cell, c_org = (C.c_float * 3)(*cl), (C.c_float * 3)(*org)
+    c_dims = (C.c_int32 * 3)(*[max(min(d, 2 ** 31 - 1), -1) for d in dm])
+    n_slots = dm[0] * dm[1] * dm[2]
+    if min(dm) < 1 or n_slots > 2 ** 31 - 1 or min(cl) <= 0:
+        # the library words the refusal: it validates these on the host, before it looks at any buffer
+        check(lib().tir_simplify_count(None, V, None, F, c_cell, c_org, c_dims, None, None, None, None, None, None),
+              "tir_simplify_count")
+    nbs, nbf = int(lib().tir_simplify_blocks(n_slots)), int(lib().tir_simplify_blocks(F))
+    slots = torch.empty((n_slots,), dtype=torch.int32, device=dev)
+    counts = torch.empty((max(nbs + nbf, 1),), dtype=torch.int32, device=dev)
+    offsets = torch.empty((nbs + nbf + 2,), dtype=torch.int32, device=dev)
+    status = torch.empty((4,), dtype=torch.int32, device=dev)
+    cov = torch.empty((V,), dtype=torch.int32, device=dev)
+    _call("tir_simplify_count", _ptr(verts if V else None), V, _ptr(faces if F else None), F, c_cell, c_org, c_dims, _ptr(slots),
+          _ptr(cov if V else None), _ptr(counts), _ptr(offsets), _ptr(status), _stream())
+    n_out, n_faces, err, _ = [int(x) for x in status.cpu()]
+    if err:
+        raise _lib.TensoirHipError("simplify_mesh: " + "; ".join(msg for bit, msg in _SIMPLIFY_ERRORS if err & bit))
+    del slots
+    out_v = torch.empty((n_out, 3), dtype=torch.float32, device=dev)
+    out_n = torch.empty((n_out, 3), dtype=torch.float32, device=dev)
+    out_f = torch.empty((n_faces, 3), dtype=torch.int32, device=dev)
+    acc = torch.empty((n_out, SIMPLIFY_ACC), dtype=torch.int64, device=dev) if n_out else None
+    keys = torch.empty((n_out,), dtype=torch.int32, device=dev) if n_out else None
+    _call("tir_simplify_emit", _ptr(verts if V else None), V, _ptr(faces if F else None), F, c_cell, c_org, c_dims, float(reg),
+          _ptr(cov if V else None), _ptr(offsets), n_out, n_faces, _ptr(acc), _ptr(keys), _ptr(out_v if n_out else None),
+          _ptr(out_n if n_out else None), _ptr(out_f if n_faces else None), _stream())
+    return out_v, out_f, out_n, cov
+
+
 # ---- per-point bake (tensoir_amd/bake.py) ---------------------------------------------------------
 BAKE_ROW = 16
 

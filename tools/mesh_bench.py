@@ -4,12 +4,16 @@ checkpoint's field or (--trained) on the field tests/train_sequence.reconstruct(
 
     python tools/mesh_bench.py [--grids 300,512] [--reps 3]      # event-timed passes, counts, export_mesh wall time
     python tools/mesh_bench.py --trained --connectivity 26       # the trained lattice (a few seconds of training first)
+    python tools/mesh_bench.py --trained --grids 300 --simplify 2,3,4     # + the simplification of the full mesh per cluster size
     rocprofv3 --kernel-trace --stats --output-format csv -d DIR -o mesh -- python tools/mesh_bench.py --grids 300
     python tools/mesh_bench.py --stats DIR                       # per-kernel GPU time from that trace
 
 One JSON line per grid: dense_alpha_ms / mc_ms / ccl_label_ms / ccl_filter_ms (CUDA events around the calls; the marching-cubes
 and labelling figures include their one read-back of the totals), components, vertices, faces, export_s (extract_mesh +
-write_ply, wall clock, after a warm-up export) and export_keep1_s (the same with keep_largest=1).
+write_ply, wall clock, after a warm-up export) and export_keep1_s (the same with keep_largest=1).  With --simplify K[,K...]:
+"simplify": {K: {"ms", "vertices", "faces"}}, mesh.simplify_extracted (ops.simplify_mesh and the rescaling of its normals) on the
+marching-cubes mesh of the same pass (events around the call, its read-back of the totals included, best of --reps after one
+warm-up call).
 """
 import argparse
 import csv
@@ -29,7 +33,7 @@ def stats(d):
     for f in sorted(glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True)):
         with open(f) as fh:
             rows += list(csv.DictReader(fh))
-    keep = ("k_dense_alpha", "k_mc_", "k_exclusive_scan", "k_ccl_")
+    keep = ("k_dense_alpha", "k_mc_", "k_exclusive_scan", "k_ccl_", "k_simplify_")
     out = {}
     for r in rows:
         name = r["Name"].replace("(anonymous namespace)::", "").split("(")[0].replace("void ", "")
@@ -43,7 +47,7 @@ def stats(d):
     print(json.dumps({"kernels": out, "dense_alpha_total_ms": da, "marching_cubes_total_ms": mc, "components_total_ms": ccl}, indent=1))
 
 
-def run(grids, reps, trained=False, connectivity=6):
+def run(grids, reps, trained=False, connectivity=6, simplify=()):
     import numpy as np
     import torch
 
@@ -91,6 +95,19 @@ def run(grids, reps, trained=False, connectivity=6):
             torch.cuda.synchronize()
             lab.append(e0.elapsed_time(e1))
         del alpha, labels
+        simp = {}
+        for k in simplify:
+            ms = []
+            for r in range(reps + 1):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                sv, sf, _, _ = mesh.simplify_extracted(v, f, aabb, grid, k)
+                e1.record()
+                torch.cuda.synchronize()
+                if r:
+                    ms.append(e0.elapsed_time(e1))
+            simp[k] = {"ms": min(ms), "vertices": int(sv.shape[0]), "faces": int(sf.shape[0])}
+            del sv, sf
         with tempfile.TemporaryDirectory() as d:
             path = os.path.join(d, "m.ply")
             mesh.export_mesh(model, path, gridSize=grid)      # warm-up
@@ -106,7 +123,7 @@ def run(grids, reps, trained=False, connectivity=6):
                           "connectivity": connectivity, "components": n_comp, "largest_component": largest,
                           "export_keep1_s": export_keep1_s, "vertices": int(v.shape[0]),
                           "faces": int(f.shape[0]), "export_s": export_s, "export_vertices": nv, "export_faces": nf,
-                          "ply_bytes": ply_bytes}), flush=True)
+                          "ply_bytes": ply_bytes, **({"simplify": simp} if simp else {})}), flush=True)
         del v, f, nrm
         torch.cuda.empty_cache()
 
@@ -118,10 +135,12 @@ def main():
     ap.add_argument("--stats", default=None, help="summarise the rocprofv3 kernel stats under this directory and exit")
     ap.add_argument("--trained", action="store_true", help="time the field tests/train_sequence.reconstruct() trains")
     ap.add_argument("--connectivity", type=int, choices=(6, 26), default=6)
+    ap.add_argument("--simplify", default="", metavar="K[,K...]", help="also time the simplification of the full mesh with clusters "
+                    "of K x K x K cells")
     a = ap.parse_args()
     if a.stats:
         return stats(a.stats)
-    run([int(x) for x in a.grids.split(",")], a.reps, a.trained, a.connectivity)
+    run([int(x) for x in a.grids.split(",")], a.reps, a.trained, a.connectivity, [int(x) for x in a.simplify.split(",") if x])
 
 
 if __name__ == "__main__":
