@@ -910,6 +910,53 @@ int tir_bake_composite(const int32_t* ray_rec_off, const int32_t* ray_rec_cnt, c
 int tir_irradiance_integrate(const float* rows, const float* dirs, const float* vis, const float* env, const float* weight_d,
                              const int32_t* light_idx, int64_t M, int32_t D, int32_t n_lights, float* out, void* stream);
 
+/* ---- Per-triangle texture atlas of a mesh (tensoir_amd/mesh.py, bake_atlas / export_textured).
+ *   verts [V][3], normals [V][3] fp32, faces [F][3] int32; a size x size image (6 .. 8192) of cols x cols square cells of
+ *   T x T texels (T >= 6).  No chart solver: faces 2c and 2c+1 share cell c, whose texel origin is ((c % cols) T, (c / cols) T).
+ *   Texel (i, j) of a cell has centre (i + 0.5, j + 0.5); j counts image rows from the top and uv = texel / size (glTF's).
+ *   1. ownership: the lower face 2c owns i + j <= T - 1, the upper face 2c+1 owns i + j >= T; when F is odd, face F-1 owns all
+ *      of the last cell.  Texels outside the ceil(F / 2) used cells are unowned.
+ *   2. UV corners (cell-local, corner order 0, 1, 2): lower (1, 1), (T-3, 1), (1, T-3); upper (T-1, T-1), (3, T-1), (T-1, 3),
+ *      the lower triangle turned by 180 degrees about the cell centre.  A bilinear lookup anywhere inside a face's UV triangle
+ *      reads only texels that face owns.  uv = (cell origin + corner) / size: ONE fp32 IEEE division of two integers.
+ *   3. a texel's barycentrics: the texel centre is moved to the nearest point of the owner's UV triangle (exactly, in integer
+ *      quarter texels; gutter texels thus repeat the edge), and with (qx, qy) that point relative to corner 0 along the two
+ *      legs of length L = T - 4:  b1 = qx / L, b2 = qy / L, b0 = (L - qx - qy) / L, each one fp32 IEEE division of exact numbers.
+ *   4. point = sum b_k v_k; outward = normalize(sum b_k n_k), the face normal normalize((v1 - v0) x (v2 - v0)) when that sum is
+ *      shorter than 1e-20, and (0, 0, 1) when the face normal is too.
+ *   5. tangent of a frame with unit normal n: t = normalize(e_u - n (n . e_u)), e_u = v1 - v0 for a lower and v0 - v1 for an
+ *      upper face (the world direction of +u); when that vector is shorter than 1e-20, the same expression with the coordinate
+ *      axis of n's smallest |component| (the first of equals) in place of e_u.  b = cross(n, t); w = +1 always.
+ * tir_atlas_corners: the unwelded mesh.  Corner q = 3 f + k: pos / nrm [3F][3] = bit copies of verts / normals [faces[f][k]],
+ *   uv [3F][2] (step 2), tan [3F][4] = (t, 1) of step 5 with n = the corner's normal normalised as in step 4 (b = unit vector k).
+ * tir_atlas_texels: for the n_cells T T texels in cell-major order (c T T + j T + i): point [N][3], outward [N][3] (step 4),
+ *   face [N] = the owner.  One thread per texel; 16-byte stores when point and outward are 16-byte aligned.
+ * tir_atlas_pack: the three size x size RGBA8 images, in image order (row-major from the top), from the per-texel results of
+ *   the bake in the cell-major order above: albedo [N][3], irradiance [N][3] or NULL, roughness [N], ao [N] or NULL, normal
+ *   [N][3] (unit, in the coordinates of verts' frame), coverage [N].  With u8(x) = round(255 clamp(x, 0, 1)), half to even:
+ *     base   = u8(srgb(c)), 255;  c = albedo, or clamp(albedo / pi * irradiance, 0, 1) when irradiance is given;
+ *              srgb(x) = x <= 0.0031308 ? 12.92 x : 1.055 (x + 1e-6)^(1 / 2.4) - 0.055
+ *     orm    = u8(ao) (255 when ao is NULL), u8(roughness), 0, 255
+ *     normal = u8(0.5 + 0.5 (N . t, N . b, N . n)), 255 with the frame (t, b, n) of steps 4-5 at the texel, recomputed from the
+ *              mesh; (128, 128, 255, 255) where coverage <= 0.5 (the bake returns `outward` there)
+ *   unowned texels: (0, 0, 0, 255) in base and orm, (128, 128, 255, 255) in normal.
+ * No atomics; two calls give identical bits.  No access leaves a buffer: a face with an index outside [0, V) is read nowhere,
+ * its outputs are 0 (outward (0, 0, 1), texels as unowned) and *status, which every entry clears first, is set to 1; the caller
+ * must not use the outputs then.  Host validation before any device work: a null pointer (irradiance and ao excepted; data
+ * pointers may be null when F = 0), a negative count, size < 6, cols < 1, cols T > size, or more rows of cells than fit
+ * -> TIR_ERR_ARG; T < 6, size > 8192 or V > 2^31-1 -> TIR_ERR_UNSUPPORTED; tan must be 16-byte, the images 4-byte aligned.
+ * F = 0 returns TIR_OK and launches nothing (the images are then the caller's to fill). */
+int tir_atlas_corners(const float* verts, int64_t n_verts, const float* normals, const int32_t* faces, int64_t n_faces,
+                      int32_t size, int32_t cols, int32_t T, float* pos, float* nrm, float* tan, float* uv, int32_t* status,
+                      void* stream);
+int tir_atlas_texels(const float* verts, int64_t n_verts, const float* normals, const int32_t* faces, int64_t n_faces,
+                     int32_t size, int32_t cols, int32_t T, float* point, float* outward, int32_t* face, int32_t* status,
+                     void* stream);
+int tir_atlas_pack(const float* verts, int64_t n_verts, const float* normals, const int32_t* faces, int64_t n_faces,
+                   int32_t size, int32_t cols, int32_t T, const float* albedo, const float* irradiance, const float* roughness,
+                   const float* ao, const float* normal, const float* coverage, uint8_t* base, uint8_t* orm,
+                   uint8_t* normal_image, int32_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -170,6 +170,9 @@ SIGNATURES = {
                                     I32, I32, P, P, P, P, P, P]),
     "tir_bake_composite": (C.c_int, [P, P, P, P, P, P, P, P, P, C.POINTER(C.c_float), I64, I64, P, P]),
     "tir_irradiance_integrate": (C.c_int, [P, P, P, P, P, P, I64, I32, I32, P, P]),
+    "tir_atlas_corners": (C.c_int, [P, I64, P, P, I64, I32, I32, I32, P, P, P, P, P, P]),
+    "tir_atlas_texels": (C.c_int, [P, I64, P, P, I64, I32, I32, I32, P, P, P, P, P]),
+    "tir_atlas_pack": (C.c_int, [P, I64, P, P, I64, I32, I32, I32, P, P, P, P, P, P, P, P, P, P, P]),
 }
 
 _lib = None

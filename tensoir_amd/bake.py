@@ -4,6 +4,7 @@ occlusion and direct irradiance under one of the model's lights, evaluated at su
 
     out = bake_points(model, points, outward)          # device tensors, one row per point
     python -m tensoir_amd.bake CKPT OUT.ply [--grid N] [--level L] [--color albedo|diffuse] [--light K]
+    python -m tensoir_amd.bake CKPT OUT.glb --texture-size N [...]     # the same bake at every texel of an atlas (mesh.export_textured)
 
 Per point p with unit outward direction n and s = model.stepSize:
   1. inward march: origin o = p + n_outside * s * n, direction d = -n, n_sample samples at z_k = k * s -- the reference's short
@@ -175,14 +176,22 @@ def main(argv=None):
     ap.add_argument("--connectivity", type=int, choices=(6, 26), default=6, help="what joins two lattice points into one component")
     ap.add_argument("--simplify", type=int, default=None, metavar="K", help="reduce the mesh by quadric vertex clustering: one "
                     "vertex per block of K x K x K lattice cells (K >= 2); the attributes are baked at the reduced vertices")
+    ap.add_argument("--texture-size", type=int, default=None, metavar="N", help="write OUT as a binary glTF (.glb) with an N x N "
+                    "texture atlas baked at every texel (base colour, occlusion / roughness / metallic, normal) instead of a PLY "
+                    "with per-vertex attributes")
     a = ap.parse_args(argv)
     extra = {} if a.envmap is None else {"envmap_h": a.envmap[0], "envmap_w": a.envmap[1]}
     model = load_model(a.ckpt, "cuda", **extra)
     grid = None if a.grid is None else [a.grid] * 3
     report = {}
-    nv, nf = mesh.export_mesh(model, a.out, a.level, grid, attributes=True, color=a.color, light_idx=a.light,
-                              keep_largest=a.keep_largest, min_component_voxels=a.min_component_voxels,
-                              connectivity=a.connectivity, report=report, simplify=a.simplify)
+    if a.texture_size is not None:
+        nv, nf = mesh.export_textured(model, a.out, a.level, grid, a.texture_size, a.color, light_idx=a.light,
+                                      keep_largest=a.keep_largest, min_component_voxels=a.min_component_voxels,
+                                      connectivity=a.connectivity, report=report, simplify=a.simplify)
+    else:
+        nv, nf = mesh.export_mesh(model, a.out, a.level, grid, attributes=True, color=a.color, light_idx=a.light,
+                                  keep_largest=a.keep_largest, min_component_voxels=a.min_component_voxels,
+                                  connectivity=a.connectivity, report=report, simplify=a.simplify)
     if "table" in report:
         sizes, kept = report["table"]["sizes"].cpu(), report["kept"].cpu()
         print(f"components: dropped {int((~kept).sum())} of {kept.numel()} ({int(sizes[~kept].sum())} of {int(sizes.sum())} voxels)")

@@ -15,6 +15,9 @@
 // tir_irradiance_integrate): two reductions without atomics, every point summed in a fixed order.
 //   k_bake_composite        BAKE_LANES lanes per point walk its contiguous record segment of the short inward march
 //   k_irradiance_integrate  one wave64 per point walks its contiguous visibility row
+//
+// Texture atlas of the exported mesh (tensoir_amd/mesh.py, bake_atlas; contract: include/tensoir_hip.h, tir_atlas_*): three
+// streaming kernels, described where they start below ("per-triangle texture atlas").
 #define TIR_MC_CONSTANT __constant__
 #include "tir_common.hpp"
 #include "tir_mc_table.hpp"
@@ -1043,6 +1046,261 @@ k_irradiance_integrate(const float* __restrict__ rows, const float* __restrict__
     if (lane == 0) *reinterpret_cast<float4*>(out + 4 * m) = make_float4(den > 0.f ? num / den : 1.f, irr[0], irr[1], irr[2]);
 }
 
+// ---- per-triangle texture atlas (contract: include/tensoir_hip.h, tir_atlas_*) ---------------------------------------
+//   k_atlas_corners  one thread per face corner: the unwelded vertex, its uv and its tangent
+//   k_atlas_texels   one thread per texel of the used cells (cell-major): the surface point and unit normal the bake is run at
+//   k_atlas_pack     one thread per texel of the image: the three RGBA8 images from the per-texel bake results
+// A texel's owner and its clamped barycentrics are integer arithmetic (quarter texels) followed by three fp32 divisions of exact
+// numbers, so all three kernels -- and the numpy restatement -- derive the same fp32 barycentrics for a texel.
+constexpr int ATLAS_THREADS = 256;
+
+struct AtlasLayout {
+    int32_t size, cols, T;
+    int32_t n_cells;
+    int64_t n_faces, n_verts;
+};
+
+// nearest point of the triangle (0, 0), (L, 0), (0, L) to (X, Y), all in quarter texels -> (qx, qy)
+__device__ __forceinline__ void atlas_nearest(int X, int Y, int L, int& qx, int& qy) {
+    if (X >= 0 && Y >= 0 && X + Y <= L) { qx = X; qy = Y; return; }
+    const int ax = min(max(X, 0), L), by = min(max(Y, 0), L), u = min(max((L - X + Y) / 2, 0), L);   // L - X + Y is even
+    const int64_t d0 = (int64_t)(X - ax) * (X - ax) + (int64_t)Y * Y;
+    const int64_t d1 = (int64_t)X * X + (int64_t)(Y - by) * (Y - by);
+    const int64_t d2 = (int64_t)(X - (L - u)) * (X - (L - u)) + (int64_t)(Y - u) * (Y - u);
+    qx = ax; qy = 0;
+    int64_t d = d0;
+    if (d1 < d) { d = d1; qx = 0; qy = by; }
+    if (d2 < d) { qx = L - u; qy = u; }
+}
+
+// cell-local texel (i, j) of cell c -> owning face, and the barycentrics of the texel centre clamped to the owner's UV triangle
+__device__ __forceinline__ int64_t atlas_owner(const AtlasLayout& A, int c, int i, int j, float b[3]) {
+    const int T = A.T;
+    const bool upper = i + j >= T && 2 * (int64_t)c + 1 < A.n_faces;
+    // centre minus corner 0, in quarter texels: (i + 0.5) - 1, or T - (i + 0.5) - 1 for the upper face (the cell turned by 180 degrees)
+    const int X = upper ? 4 * (T - i) - 6 : 4 * i - 2, Y = upper ? 4 * (T - j) - 6 : 4 * j - 2, L = 4 * (T - 4);
+    int qx, qy;
+    atlas_nearest(X, Y, L, qx, qy);
+    b[0] = __fdiv_rn((float)(L - qx - qy), (float)L);
+    b[1] = __fdiv_rn((float)qx, (float)L);
+    b[2] = __fdiv_rn((float)qy, (float)L);
+    return 2 * (int64_t)c + (upper ? 1 : 0);
+}
+
+struct AtlasFace {
+    float v[3][3], n[3][3];
+};
+
+// the face's three vertices and vertex normals; false (nothing read) when an index lies outside [0, V)
+__device__ __forceinline__ bool atlas_load_face(const float* __restrict__ verts, const float* __restrict__ normals,
+                                                const int32_t* __restrict__ faces, int64_t f, int64_t n_verts, AtlasFace& F) {
+    int32_t id[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) id[k] = faces[3 * f + k];
+    if (id[0] < 0 || id[1] < 0 || id[2] < 0 || id[0] >= n_verts || id[1] >= n_verts || id[2] >= n_verts) return false;
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            F.v[k][a] = verts[3 * (int64_t)id[k] + a];
+            F.n[k][a] = normals[3 * (int64_t)id[k] + a];
+        }
+    return true;
+}
+
+__device__ __forceinline__ float atlas_len(const float x[3]) { return sqrtf(fmaf(x[2], x[2], fmaf(x[1], x[1], x[0] * x[0]))); }
+
+// normalize(sum b_k n_k); the face normal when that sum is shorter than 1e-20 (or not a number), then (0, 0, 1)
+__device__ __forceinline__ void atlas_normal(const AtlasFace& F, const float b[3], float n[3]) {
+    float s[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) s[a] = fmaf(b[2], F.n[2][a], fmaf(b[1], F.n[1][a], b[0] * F.n[0][a]));
+    float l = atlas_len(s);
+    if (!(l >= 1e-20f)) {
+        float e1[3], e2[3];
+#pragma unroll
+        for (int a = 0; a < 3; ++a) { e1[a] = F.v[1][a] - F.v[0][a]; e2[a] = F.v[2][a] - F.v[0][a]; }
+        s[0] = e1[1] * e2[2] - e1[2] * e2[1];
+        s[1] = e1[2] * e2[0] - e1[0] * e2[2];
+        s[2] = e1[0] * e2[1] - e1[1] * e2[0];
+        l = atlas_len(s);
+        if (!(l >= 1e-20f)) { s[0] = 0.f; s[1] = 0.f; s[2] = 1.f; l = 1.f; }
+    }
+#pragma unroll
+    for (int a = 0; a < 3; ++a) n[a] = s[a] / l;
+}
+
+// t = normalize(e - n (n . e)) with e the world direction of +u on the face; when that is shorter than 1e-20 the same with the
+// coordinate axis of n's smallest |component| (the first of equals) in place of e, which is never short for a unit n
+__device__ __forceinline__ void atlas_tangent(const AtlasFace& F, bool upper, const float n[3], float t[3]) {
+    float e[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) e[a] = upper ? F.v[0][a] - F.v[1][a] : F.v[1][a] - F.v[0][a];
+    float d = fmaf(n[2], e[2], fmaf(n[1], e[1], n[0] * e[0]));
+#pragma unroll
+    for (int a = 0; a < 3; ++a) t[a] = fmaf(-n[a], d, e[a]);
+    float l = atlas_len(t);
+    if (!(l >= 1e-20f)) {
+        const float a0 = fabsf(n[0]), a1 = fabsf(n[1]), a2 = fabsf(n[2]);
+        const int ax = (a0 <= a1 && a0 <= a2) ? 0 : (a1 <= a2 ? 1 : 2);
+        d = ax == 0 ? n[0] : (ax == 1 ? n[1] : n[2]);
+#pragma unroll
+        for (int a = 0; a < 3; ++a) t[a] = fmaf(-n[a], d, a == ax ? 1.f : 0.f);
+        l = atlas_len(t);
+    }
+#pragma unroll
+    for (int a = 0; a < 3; ++a) t[a] = t[a] / l;
+}
+
+__global__ void __launch_bounds__(ATLAS_THREADS)
+k_atlas_corners(const float* __restrict__ verts, const float* __restrict__ normals, const int32_t* __restrict__ faces,
+                AtlasLayout A, float* __restrict__ pos, float* __restrict__ nrm, float* __restrict__ tan, float* __restrict__ uv,
+                int32_t* __restrict__ status) {
+    const int64_t q = (int64_t)blockIdx.x * ATLAS_THREADS + threadIdx.x;
+    if (q >= 3 * A.n_faces) return;
+    const int64_t f = q / 3;
+    const int k = (int)(q - 3 * f);
+    const bool upper = f & 1;
+    const int c = (int)(f >> 1), T = A.T;
+    const int cx = k == 1 ? T - 3 : 1, cy = k == 2 ? T - 3 : 1;                     // the lower face's corner, cell-local
+    const int x = (c % A.cols) * T + (upper ? T - cx : cx), y = (c / A.cols) * T + (upper ? T - cy : cy);
+    uv[2 * q] = __fdiv_rn((float)x, (float)A.size);
+    uv[2 * q + 1] = __fdiv_rn((float)y, (float)A.size);
+    AtlasFace F;
+    float t[3] = {0.f, 0.f, 0.f}, p[3] = {0.f, 0.f, 0.f}, m[3] = {0.f, 0.f, 0.f};
+    if (atlas_load_face(verts, normals, faces, f, A.n_verts, F)) {
+        const float b[3] = {k == 0 ? 1.f : 0.f, k == 1 ? 1.f : 0.f, k == 2 ? 1.f : 0.f};
+        float n[3];
+        atlas_normal(F, b, n);
+        atlas_tangent(F, upper, n, t);
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            p[a] = k == 0 ? F.v[0][a] : (k == 1 ? F.v[1][a] : F.v[2][a]);
+            m[a] = k == 0 ? F.n[0][a] : (k == 1 ? F.n[1][a] : F.n[2][a]);
+        }
+    } else {
+        *status = 1;                                   // every writer stores the same word: no atomic needed
+    }
+#pragma unroll
+    for (int a = 0; a < 3; ++a) { pos[3 * q + a] = p[a]; nrm[3 * q + a] = m[a]; }
+    *reinterpret_cast<float4*>(tan + 4 * q) = make_float4(t[0], t[1], t[2], 1.f);
+}
+
+// VEC: point and outward are 16-byte aligned -- a block's 256 x 3 floats go through LDS and leave as 192 16-byte stores
+template <bool VEC>
+__global__ void __launch_bounds__(ATLAS_THREADS)
+k_atlas_texels(const float* __restrict__ verts, const float* __restrict__ normals, const int32_t* __restrict__ faces,
+               AtlasLayout A, int32_t n_texels, float* __restrict__ point, float* __restrict__ outward,
+               int32_t* __restrict__ face, int32_t* __restrict__ status) {
+    __shared__ __align__(16) float s_p[VEC ? 3 * ATLAS_THREADS : 4], s_o[VEC ? 3 * ATLAS_THREADS : 4];      // read back 16 bytes at a time
+    const int32_t base = (int32_t)blockIdx.x * ATLAS_THREADS, idx = base + (int32_t)threadIdx.x;
+    float p[3] = {0.f, 0.f, 0.f}, o[3] = {0.f, 0.f, 1.f};
+    if (idx < n_texels) {
+        const int tt = A.T * A.T, c = idx / tt, r = idx - c * tt, j = r / A.T, i = r - j * A.T;
+        float b[3];
+        const int64_t f = atlas_owner(A, c, i, j, b);
+        face[idx] = (int32_t)f;
+        AtlasFace F;
+        if (atlas_load_face(verts, normals, faces, f, A.n_verts, F)) {
+#pragma unroll
+            for (int a = 0; a < 3; ++a) p[a] = fmaf(b[2], F.v[2][a], fmaf(b[1], F.v[1][a], b[0] * F.v[0][a]));
+            atlas_normal(F, b, o);
+        } else {
+            *status = 1;
+        }
+    }
+    if constexpr (VEC) {
+#pragma unroll
+        for (int a = 0; a < 3; ++a) { s_p[3 * threadIdx.x + a] = p[a]; s_o[3 * threadIdx.x + a] = o[a]; }
+        __syncthreads();
+        const int n_fl = 3 * min(ATLAS_THREADS, n_texels - base), o4 = 4 * (int)threadIdx.x;      // floats this block owns
+        if (o4 >= n_fl) return;
+        float* gp = point + 3 * (int64_t)base + o4;
+        float* go = outward + 3 * (int64_t)base + o4;
+        if (o4 + 4 <= n_fl) {
+            *reinterpret_cast<float4*>(gp) = *reinterpret_cast<const float4*>(s_p + o4);
+            *reinterpret_cast<float4*>(go) = *reinterpret_cast<const float4*>(s_o + o4);
+        } else {
+            for (int k = 0; o4 + k < n_fl; ++k) { gp[k] = s_p[o4 + k]; go[k] = s_o[o4 + k]; }
+        }
+    } else {
+        if (idx >= n_texels) return;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) { point[3 * (int64_t)idx + a] = p[a]; outward[3 * (int64_t)idx + a] = o[a]; }
+    }
+}
+
+// round(255 x) of a value in [0, 1] (a NaN counts as 0)
+__device__ __forceinline__ unsigned atlas_u8(float x) { return (unsigned)rintf(255.0f * fminf(fmaxf(x, 0.f), 1.f)); }
+
+// relight.linear2srgb_torch, its + 1e-6 included
+__device__ __forceinline__ float atlas_srgb(float c) {
+    const float x = fminf(fmaxf(c, 0.f), 1.f);
+    return x <= 0.0031308f ? x * 12.92f : 1.055f * powf(x + 1e-6f, 1.0f / 2.4f) - 0.055f;
+}
+
+__device__ __forceinline__ uint32_t atlas_rgba(unsigned r, unsigned g, unsigned b) { return r | (g << 8) | (b << 16) | 0xff000000u; }
+
+struct AtlasBake {
+    const float *albedo, *irradiance, *roughness, *ao, *normal, *coverage;     // cell-major; irradiance and ao may be null
+};
+
+__global__ void __launch_bounds__(ATLAS_THREADS)
+k_atlas_pack(const float* __restrict__ verts, const float* __restrict__ normals, const int32_t* __restrict__ faces, AtlasLayout A,
+             AtlasBake B, uint32_t* __restrict__ base, uint32_t* __restrict__ orm, uint32_t* __restrict__ nimg,
+             int32_t* __restrict__ status) {
+    const int32_t px = (int32_t)blockIdx.x * ATLAS_THREADS + (int32_t)threadIdx.x;
+    if (px >= A.size * A.size) return;
+    const int y = px / A.size, x = px - y * A.size, T = A.T;
+    const int cx = x / T, cy = y / T, c = cy * A.cols + cx;
+    uint32_t o_base = atlas_rgba(0, 0, 0), o_orm = o_base, o_n = atlas_rgba(128, 128, 255);       // an unowned texel
+    AtlasFace F;
+    float b[3];
+    if (cx < A.cols && c < A.n_cells) {
+        const int i = x - cx * T, j = y - cy * T;
+        const int64_t f = atlas_owner(A, c, i, j, b);
+        if (atlas_load_face(verts, normals, faces, f, A.n_verts, F)) {
+            const int64_t k = (int64_t)c * T * T + j * T + i;
+            float col[3];
+#pragma unroll
+            for (int a = 0; a < 3; ++a) {
+                col[a] = B.albedo[3 * k + a];
+                if (B.irradiance) col[a] = fminf(fmaxf(col[a] / 3.14159265358979323846f * B.irradiance[3 * k + a], 0.f), 1.f);
+            }
+            o_base = atlas_rgba(atlas_u8(atlas_srgb(col[0])), atlas_u8(atlas_srgb(col[1])), atlas_u8(atlas_srgb(col[2])));
+            o_orm = atlas_rgba(B.ao ? atlas_u8(B.ao[k]) : 255u, atlas_u8(B.roughness[k]), 0);
+            if (B.coverage[k] > 0.5f) {
+                float n[3], t[3];
+                atlas_normal(F, b, n);
+                atlas_tangent(F, f & 1, n, t);
+                const float bt[3] = {n[1] * t[2] - n[2] * t[1], n[2] * t[0] - n[0] * t[2], n[0] * t[1] - n[1] * t[0]};
+                const float N[3] = {B.normal[3 * k], B.normal[3 * k + 1], B.normal[3 * k + 2]};
+                const float dt = fmaf(N[2], t[2], fmaf(N[1], t[1], N[0] * t[0]));
+                const float db = fmaf(N[2], bt[2], fmaf(N[1], bt[1], N[0] * bt[0]));
+                const float dn = fmaf(N[2], n[2], fmaf(N[1], n[1], N[0] * n[0]));
+                o_n = atlas_rgba(atlas_u8(fmaf(0.5f, dt, 0.5f)), atlas_u8(fmaf(0.5f, db, 0.5f)), atlas_u8(fmaf(0.5f, dn, 0.5f)));
+            }
+        } else {
+            *status = 1;
+        }
+    }
+    base[px] = o_base;
+    orm[px] = o_orm;
+    nimg[px] = o_n;
+}
+
+// host-side validation shared by the tir_atlas_* entries: 0, or a negative TIR_ERR_*; fills the layout
+int atlas_validate(int64_t V, int64_t F, int32_t size, int32_t cols, int32_t T, AtlasLayout* A) {
+    if (V < 0 || F < 0 || size < 6 || cols < 1 || (int64_t)cols * T > size) return TIR_ERR_ARG;
+    if (T < 6 || size > 8192 || V > INT32_MAX) return TIR_ERR_UNSUPPORTED;
+    const int64_t n_cells = (F + 1) / 2, rows = (n_cells + cols - 1) / cols;
+    if (rows * T > size) return TIR_ERR_ARG;
+    A->size = size; A->cols = cols; A->T = T;
+    A->n_cells = (int32_t)n_cells;
+    A->n_faces = F; A->n_verts = V;
+    return TIR_OK;
+}
+
 }  // namespace
 
 extern "C" int tir_bake_composite(const int32_t* ray_rec_off, const int32_t* ray_rec_cnt, const float* rec_w, const float* rec_xyz,
@@ -1083,6 +1341,67 @@ extern "C" int tir_irradiance_integrate(const float* rows, const float* dirs, co
     else
         hipLaunchKernelGGL(k_irradiance_integrate<false>, dim3((unsigned)nblk), dim3(BAKE_THREADS), 0, tir_stream(stream), rows,
                            dirs, vis, env, weight_d, light_idx, M, (int)D, (int)n_lights, out);
+    TIR_CHECK_LAUNCH();
+    return TIR_OK;
+}
+
+extern "C" int tir_atlas_corners(const float* verts, int64_t n_verts, const float* normals, const int32_t* faces, int64_t n_faces,
+                                 int32_t size, int32_t cols, int32_t T, float* pos, float* nrm, float* tan, float* uv,
+                                 int32_t* status, void* stream) {
+    AtlasLayout A;
+    if (!status || (n_faces > 0 && (!verts || !normals || !faces || !pos || !nrm || !tan || !uv))) return TIR_ERR_ARG;
+    const int rc = atlas_validate(n_verts, n_faces, size, cols, T, &A);
+    if (rc) return rc;
+    if ((uintptr_t)tan & 15) return TIR_ERR_ARG;
+    if (n_faces == 0) return TIR_OK;
+    hipStream_t st = tir_stream(stream);
+    const hipError_t e = hipMemsetAsync(status, 0, sizeof(int32_t), st);
+    if (e != hipSuccess) return -(int)e;
+    hipLaunchKernelGGL(k_atlas_corners, dim3((unsigned)((3 * n_faces + ATLAS_THREADS - 1) / ATLAS_THREADS)), dim3(ATLAS_THREADS), 0,
+                       st, verts, normals, faces, A, pos, nrm, tan, uv, status);
+    TIR_CHECK_LAUNCH();
+    return TIR_OK;
+}
+
+extern "C" int tir_atlas_texels(const float* verts, int64_t n_verts, const float* normals, const int32_t* faces, int64_t n_faces,
+                                int32_t size, int32_t cols, int32_t T, float* point, float* outward, int32_t* face,
+                                int32_t* status, void* stream) {
+    AtlasLayout A;
+    if (!status || (n_faces > 0 && (!verts || !normals || !faces || !point || !outward || !face))) return TIR_ERR_ARG;
+    const int rc = atlas_validate(n_verts, n_faces, size, cols, T, &A);
+    if (rc) return rc;
+    if (n_faces == 0) return TIR_OK;
+    hipStream_t st = tir_stream(stream);
+    const hipError_t e = hipMemsetAsync(status, 0, sizeof(int32_t), st);
+    if (e != hipSuccess) return -(int)e;
+    const int32_t n = A.n_cells * T * T;                               // at most size^2 <= 2^26
+    const dim3 grid((unsigned)((n + ATLAS_THREADS - 1) / ATLAS_THREADS)), block(ATLAS_THREADS);
+    if ((((uintptr_t)point | (uintptr_t)outward) & 15) == 0)
+        hipLaunchKernelGGL(k_atlas_texels<true>, grid, block, 0, st, verts, normals, faces, A, n, point, outward, face, status);
+    else
+        hipLaunchKernelGGL(k_atlas_texels<false>, grid, block, 0, st, verts, normals, faces, A, n, point, outward, face, status);
+    TIR_CHECK_LAUNCH();
+    return TIR_OK;
+}
+
+extern "C" int tir_atlas_pack(const float* verts, int64_t n_verts, const float* normals, const int32_t* faces, int64_t n_faces,
+                              int32_t size, int32_t cols, int32_t T, const float* albedo, const float* irradiance,
+                              const float* roughness, const float* ao, const float* normal, const float* coverage, uint8_t* base,
+                              uint8_t* orm, uint8_t* normal_image, int32_t* status, void* stream) {
+    AtlasLayout A;
+    if (!status || !base || !orm || !normal_image) return TIR_ERR_ARG;
+    if (n_faces > 0 && (!verts || !normals || !faces || !albedo || !roughness || !normal || !coverage)) return TIR_ERR_ARG;
+    const int rc = atlas_validate(n_verts, n_faces, size, cols, T, &A);
+    if (rc) return rc;
+    if (((uintptr_t)base | (uintptr_t)orm | (uintptr_t)normal_image) & 3) return TIR_ERR_ARG;
+    if (n_faces == 0) return TIR_OK;
+    hipStream_t st = tir_stream(stream);
+    const hipError_t e = hipMemsetAsync(status, 0, sizeof(int32_t), st);
+    if (e != hipSuccess) return -(int)e;
+    const AtlasBake B{albedo, irradiance, roughness, ao, normal, coverage};
+    hipLaunchKernelGGL(k_atlas_pack, dim3((unsigned)((size * size + ATLAS_THREADS - 1) / ATLAS_THREADS)), dim3(ATLAS_THREADS), 0, st,
+                       verts, normals, faces, A, B, reinterpret_cast<uint32_t*>(base), reinterpret_cast<uint32_t*>(orm),
+                       reinterpret_cast<uint32_t*>(normal_image), status);
     TIR_CHECK_LAUNCH();
     return TIR_OK;
 }

@@ -1658,3 +1658,105 @@ def irradiance_integrate(rows, dirs, vis, env, weight_d, light_idx):
     _call("tir_irradiance_integrate", _ptr(rows), _ptr(dirs), _ptr(vis), _ptr(env), _ptr(weight_d), _ptr(light_idx), M, D,
           env.shape[0], _ptr(out), _stream())
     return out
+
+
+# ---- per-triangle texture atlas (tensoir_amd/mesh.py: bake_atlas, export_textured) -----------------
+ATLAS_MIN_T = 6
+ATLAS_MAX_SIZE = 8192
+
+
+def atlas_layout(F, size):
+    """The atlas of F faces in a size x size image (contract: include/tensoir_hip.h, tir_atlas_*) -> (cols, T): cols x cols
+    square cells of T x T texels, two faces per cell.  Host arithmetic only.  ValueError when size is not an integer in
+    6 .. 8192 or leaves a cell fewer than 6 texels per side (the message names the smallest size that works)."""
+    import math
+    import numbers
+    if isinstance(size, bool) or not isinstance(size, numbers.Integral) or not ATLAS_MIN_T <= size <= ATLAS_MAX_SIZE:
+        raise ValueError(f"size: expected an integer in {ATLAS_MIN_T} .. {ATLAS_MAX_SIZE}, not {size!r}")
+    if int(F) < 0:
+        raise ValueError(f"the number of faces must not be negative, got {F}")
+    n_cells = (int(F) + 1) // 2
+    cols = math.isqrt(n_cells - 1) + 1 if n_cells > 0 else 1          # ceil(sqrt(n_cells))
+    T = int(size) // cols
+    if T < ATLAS_MIN_T:
+        raise ValueError(f"size {size} leaves {T} texels per cell side: {F} faces need a size of at least {ATLAS_MIN_T * cols}")
+    return cols, T
+
+
+def _atlas_mesh(verts, normals, faces):
+    verts = f32(verts, "verts", 3).view(-1, 3)
+    normals = f32(normals, "normals", 3).view(-1, 3)
+    faces = i32(faces, "faces").view(-1, 3)
+    if normals.shape != verts.shape or normals.device != verts.device or faces.device != verts.device:
+        raise ValueError("verts and normals take one row per vertex, and faces lives on their device")
+    return verts, normals, faces
+
+
+def _atlas_status(status, what):
+    if int(status.item()):
+        raise _lib.TensoirHipError(f"{what}: a face index lies outside [0, V)")
+
+
+def atlas_corners(verts, normals, faces, size, cols, T):
+    """tir_atlas_corners: the unwelded mesh of the atlas -> (pos [3F, 3], nrm [3F, 3], tan [3F, 4], uv [3F, 2]) f32 on verts'
+    device; pos / nrm are bit copies of verts / normals [faces].  One 4-byte read-back (the error word)."""
+    verts, normals, faces = _atlas_mesh(verts, normals, faces)
+    V, F, dev = verts.shape[0], faces.shape[0], verts.device
+    pos, nrm, uv = (torch.empty((3 * F, k), dtype=torch.float32, device=dev) for k in (3, 3, 2))
+    tan = torch.empty((3 * F, 4), dtype=torch.float32, device=dev)
+    status = torch.zeros((1,), dtype=torch.int32, device=dev)
+    data = lambda t: _ptr(t if F else None)
+    _call("tir_atlas_corners", data(verts), V, data(normals), data(faces), F, int(size), int(cols), int(T), data(pos), data(nrm),
+          data(tan), data(uv), _ptr(status), _stream())
+    _atlas_status(status, "atlas_corners")
+    return pos, nrm, tan, uv
+
+
+def atlas_texels(verts, normals, faces, size, cols, T):
+    """tir_atlas_texels: where the bake samples the surface, for the ceil(F / 2) * T * T texels of the used cells in cell-major
+    order -> (point [N, 3] f32, outward [N, 3] f32 unit, face [N] i32), in the coordinates of verts / normals."""
+    verts, normals, faces = _atlas_mesh(verts, normals, faces)
+    V, F, dev = verts.shape[0], faces.shape[0], verts.device
+    N = ((F + 1) // 2) * int(T) * int(T)
+    point = torch.empty((N, 3), dtype=torch.float32, device=dev)
+    outward = torch.empty((N, 3), dtype=torch.float32, device=dev)
+    face = torch.empty((N,), dtype=torch.int32, device=dev)
+    status = torch.zeros((1,), dtype=torch.int32, device=dev)
+    data = lambda t: _ptr(t if F else None)
+    _call("tir_atlas_texels", data(verts), V, data(normals), data(faces), F, int(size), int(cols), int(T), data(point),
+          data(outward), data(face), _ptr(status), _stream())
+    _atlas_status(status, "atlas_texels")
+    return point, outward, face
+
+
+def atlas_pack(verts, normals, faces, size, cols, T, albedo, roughness, normal, coverage, irradiance=None, ao=None):
+    """tir_atlas_pack: the per-texel bake results (cell-major, as atlas_texels orders them) -> (base, orm, normal) images
+    [size, size, 4] uint8 in image order.  irradiance given: the base colour is the Lambertian radiance under it
+    (color="diffuse"); ao None: the occlusion channel is 255."""
+    verts, normals, faces = _atlas_mesh(verts, normals, faces)
+    V, F, dev = verts.shape[0], faces.shape[0], verts.device
+    size, T = int(size), int(T)
+    N = ((F + 1) // 2) * T * T
+    albedo, normal = f32(albedo, "albedo", 3).view(-1, 3), f32(normal, "normal", 3).view(-1, 3)
+    roughness, coverage = f32(roughness, "roughness").view(-1), f32(coverage, "coverage").view(-1)
+    rows = [albedo.shape[0], normal.shape[0], roughness.shape[0], coverage.shape[0]]
+    if irradiance is not None:
+        irradiance = f32(irradiance, "irradiance", 3).view(-1, 3)
+        rows.append(irradiance.shape[0])
+    if ao is not None:
+        ao = f32(ao, "ao").view(-1)
+        rows.append(ao.shape[0])
+    if any(r != N for r in rows):
+        raise ValueError(f"the per-texel inputs take {N} rows (ceil(F / 2) * T * T), got {rows}")
+    images = [torch.empty((size, size, 4), dtype=torch.uint8, device=dev) for _ in range(3)] if 0 < size <= ATLAS_MAX_SIZE else \
+        [torch.empty((1,), dtype=torch.uint8, device=dev)] * 3             # the library words the refusal of such a size
+    status = torch.zeros((1,), dtype=torch.int32, device=dev)
+    data = lambda t: _ptr(t if F else None)
+    _call("tir_atlas_pack", data(verts), V, data(normals), data(faces), F, size, int(cols), T, data(albedo),
+          _ptr(irradiance if F else None), data(roughness), _ptr(ao if F else None), data(normal), data(coverage),
+          _ptr(images[0]), _ptr(images[1]), _ptr(images[2]), _ptr(status), _stream())
+    _atlas_status(status, "atlas_pack")
+    if F == 0:                                                             # nothing was launched: every texel is unowned
+        for img, rgba in zip(images, ((0, 0, 0, 255), (0, 0, 0, 255), (128, 128, 255, 255))):
+            img.copy_(torch.tensor(rgba, dtype=torch.uint8, device=dev).expand(size, size, 4))
+    return tuple(images)

@@ -4,12 +4,18 @@ tools/mesh_bench.py uses (the small golden checkpoint), with the default 16 x 32
     python tools/bake_bench.py [--grid 300] [--reps 3]          # one JSON line
     rocprofv3 --kernel-trace --stats --output-format csv -d DIR -o bake -- python tools/bake_bench.py --reps 1
     python tools/bake_bench.py --stats DIR                      # per-kernel GPU time from that trace
+    python tools/bake_bench.py --texture-size 2048 4096 [--simplify 3]     # the textured export instead: one JSON line per size
 
 The JSON line: geometry_ms (extract_mesh), material_ms (bake_points(lighting=False): inward march, decoders, tir_bake_composite),
 lighting_ms (the rest of bake_points: pair mask, visibility march, tir_irradiance_integrate) -- device events around the calls,
 best of --reps; export_plain_s / export_baked_s (wall clock incl. the PLY write, after a warm-up, measured in this same run: the
 yardstick for "is the bake cheap enough"); and for the two new kernels the bytes they must move, their time (events around the
-launch, summed over the chunks) and the rate as a fraction of the 6.3 TB/s HBM ceiling."""
+launch, summed over the chunks) and the rate as a fraction of the 6.3 TB/s HBM ceiling.
+
+The --texture-size leg (mesh.export_textured): layout_ms (tir_atlas_corners + tir_atlas_texels), bake_ms (field_positions
++ bake_points at every texel), pack_ms (tir_atlas_pack) -- device events, best of --reps; png_write_s (PNG compression of the
+three images + the GLB write, wall clock); export_s (the whole export_textured call, wall clock, after a warm-up); and for
+k_atlas_texels and k_atlas_pack the bytes they must move, their time and the rate against the same ceiling."""
 import argparse
 import csv
 import glob
@@ -34,6 +40,7 @@ def stats(d):
         name = r["Name"].replace("(anonymous namespace)::", "").split("(")[0].replace("void ", "")
         out[name] = {"calls": int(r["Calls"]), "total_ms": float(r["TotalDurationNs"]) / 1e6, "avg_us": float(r["AverageNs"]) / 1e3}
     top = dict(sorted(out.items(), key=lambda kv: -kv[1]["total_ms"])[:14])
+    top.update({k: v for k, v in out.items() if k.startswith("k_atlas_")})         # the streaming kernels of the textured leg
     print(json.dumps({"kernels": top, "total_ms": sum(v["total_ms"] for v in out.values())}, indent=1))
 
 
@@ -107,14 +114,99 @@ def run(n, reps):
                                  "of_hbm": rate(integ_bytes, k["tir_irradiance_integrate"]) / HBM_TBS}}), flush=True)
 
 
+def run_textured(n, sizes, simplify, reps):
+    import numpy as np
+    import torch
+
+    import tensoir_amd
+    from tensoir_amd import bake, mesh, ops
+    from tests.helpers import golden_checkpoint
+    g = np.load(os.path.join(ROOT, "tests", "golden", "small_scene.npz"))
+    model = tensoir_amd.model_from_checkpoint(golden_checkpoint(g), "cuda:0")
+    grid = [n, n, n]
+
+    def timed(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        out = fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return out, e0.elapsed_time(e1)
+
+    verts, faces, normals = mesh.extract_mesh(model, 0.005, grid, simplify=simplify)
+    V, F = int(verts.shape[0]), int(faces.shape[0])
+    rate = lambda b, ms: b / (ms * 1e-3) / 1e12
+    for size in sizes:
+        cols, T = ops.atlas_layout(F, size)
+        N = ((F + 1) // 2) * T * T
+        lay, bk, pk, kern = [], [], [], []
+        for rep in range(reps + 1):                               # the first pass warms up (record-capacity hints, tables)
+            ops.TIMING = []
+            (_, (point, outward, _)), t_lay = timed(lambda: (ops.atlas_corners(verts, normals, faces, size, cols, T),
+                                                            ops.atlas_texels(verts, normals, faces, size, cols, T)))
+            calls_lay, ops.TIMING = ops.TIMING, None
+
+            def do_bake():
+                p, d = mesh.field_positions(model.aabb, grid, point, outward)
+                return bake.bake_points(model, p.contiguous(), d.contiguous())
+            b, t_bake = timed(do_bake)
+            ops.TIMING = []
+            images, t_pack = timed(lambda: ops.atlas_pack(verts, normals, faces, size, cols, T, b["albedo"], b["roughness"], b["normal"],
+                                                          b["coverage"], ao=b["ao"]))
+            calls, ops.TIMING = calls_lay + ops.TIMING, None
+            if rep:
+                lay.append(t_lay)
+                bk.append(t_bake)
+                pk.append(t_pack)
+                kern.append({k: sum(e0.elapsed_time(e1) for name, e0, e1 in calls if name == k)
+                             for k in ("tir_atlas_corners", "tir_atlas_texels", "tir_atlas_pack")})
+        covered = float((b["coverage"] > 0.5).float().mean())
+        del b, point, outward
+        a = mesh.bake_atlas(model, verts, faces, normals, grid, size)
+        host = {k: a[k].cpu().numpy() for k in mesh.IMAGE_NAMES}
+        with tempfile.TemporaryDirectory() as d:
+            path = os.path.join(d, "m.glb")
+            t0 = time.perf_counter()
+            pngs = {k: len(mesh.write_png(v)) for k, v in host.items()}
+            t_png = time.perf_counter() - t0
+            t0 = time.perf_counter()
+            mesh.write_glb(path, a["pos"], a["nrm"], a["tan"], a["uv"], host, {})
+            t_write = time.perf_counter() - t0
+            del a
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            mesh.export_textured(model, path, 0.005, grid, size, simplify=simplify)
+            t_export = time.perf_counter() - t0
+            glb_bytes = os.path.getsize(path)
+        k = {name: min(r[name] for r in kern) for name in kern[0]}
+        mesh_bytes = F * 12 + V * 24                              # faces, vertices and normals: read once from HBM, then from cache
+        tex_bytes = N * (12 + 12 + 4) + mesh_bytes                # point, outward, face per texel
+        pack_bytes = N * (12 + 4 + 12 + 4 + 4) + 3 * 4 * size * size + mesh_bytes     # albedo, roughness, normal, coverage, ao; 3 images
+        print(json.dumps({
+            "grid": n, "simplify": simplify, "vertices": V, "faces": F, "size": size, "cols": cols, "T": T, "texels": N,
+            "covered": covered, "layout_ms": min(lay), "bake_ms": min(bk), "pack_ms": min(pk), "png_s": t_png,
+            "png_write_s": t_write, "png_bytes": pngs, "glb_bytes": glb_bytes, "export_s": t_export,
+            "bake_share_of_export": min(bk) * 1e-3 / t_export,
+            "atlas_corners_ms": k["tir_atlas_corners"],
+            "atlas_texels": {"ms": k["tir_atlas_texels"], "bytes": tex_bytes, "TB_s": rate(tex_bytes, k["tir_atlas_texels"]),
+                             "of_hbm": rate(tex_bytes, k["tir_atlas_texels"]) / HBM_TBS},
+            "atlas_pack": {"ms": k["tir_atlas_pack"], "bytes": pack_bytes, "TB_s": rate(pack_bytes, k["tir_atlas_pack"]),
+                           "of_hbm": rate(pack_bytes, k["tir_atlas_pack"]) / HBM_TBS}}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--grid", type=int, default=300)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--stats", default=None, help="summarise the rocprofv3 kernel stats under this directory and exit")
+    ap.add_argument("--texture-size", type=int, nargs="+", default=None, metavar="N", help="time the textured export "
+                    "(mesh.export_textured) at these atlas sizes instead of the per-vertex bake")
+    ap.add_argument("--simplify", type=int, default=3, help="the face budget of the --texture-size leg")
     a = ap.parse_args()
     if a.stats:
         return stats(a.stats)
+    if a.texture_size:
+        return run_textured(a.grid, a.texture_size, a.simplify, a.reps)
     run(a.grid, a.reps)
 
 
