@@ -957,6 +957,68 @@ int tir_atlas_pack(const float* verts, int64_t n_verts, const float* normals, co
                    const float* ao, const float* normal, const float* coverage, uint8_t* base, uint8_t* orm,
                    uint8_t* normal_image, int32_t* status, void* stream);
 
+/* ---- Deterministic z-buffer rasteriser of the exported mesh (tensoir_amd/raster.py; restated in numpy by
+ * tests/raster_reference.py).
+ *   Camera (the datasets' get_ray_directions + get_rays): pixel (i, j) has its centre at (i + 0.5, j + 0.5) and the camera-space
+ *   direction ((i + 0.5 - W/2) / f, (j + 0.5 - H/2) / f, 1); c2w = [R | o] is [3][4], row-major, in HOST memory, its columns x
+ *   right, y down, z forward.  p_cam = R^T (p - o);  x_px = f X / Z + W/2,  y_px = f Y / Z + H/2.
+ *   Mesh: unwelded, corner q = 3 f + k, as write_glb writes it.
+ * tir_raster_project: one thread per corner -> rows [3F][4] int32 = {sx, sy, bits(invz), flags}.  With every product, sum and
+ *   quotient rounded to fp32 on its own, in this order:  d = p - o;  X = (R[0][0] d0 + R[1][0] d1) + R[2][0] d2 (Y, Z: columns 1,
+ *   2);  x_px = (f X) / Z + W/2;  sx = rint(256 x_px), half to even (8 sub-pixel bits);  invz = 1 / Z.
+ *   faces NULL: corner q reads pos[q] (n_verts >= 3 F).  faces [F][3] given: corner q reads pos[faces[q]] (an indexed mesh).
+ *   A face is dropped when any of its corners has, tested in this order per corner: a vertex index outside [0, V) (the three
+ *   indices are tested before any vertex is read, and no vertex of such a face is read); X, Y or Z not finite; Z <= near;
+ *   |sx| or |sy| > TIR_RASTER_GUARD * 256 (an infinite x_px included).  There is no clipping.  All three rows of a dropped face are
+ *   {0, 0, 0, flags} with flags the OR of its corners' TIR_RASTER_DROP_* bits; a kept face has flags 0.  status [4], cleared
+ *   first, counts the dropped faces {index, near, guard, non-finite}, each face once under the first of index, non-finite, near,
+ *   guard that any of its corners shows.
+ * tir_raster_cover: keys [H W] uint64, cleared to 0 (= empty) by the entry.  All integer, int64, from the snapped corners
+ *   (x_k, y_k):  A = (x1 - x0)(y2 - y0) - (x2 - x0)(y1 - y0).  A == 0 draws nothing; cull != 0 draws only A < 0 (front-facing for
+ *   an outward-oriented mesh in this camera); cull == 0 draws both signs.  With n = sign(A), the centre p = (256 i + 128,
+ *   256 j + 128) of pixel (i, j) and cross(a, b) = a.x b.y - b.x a.y:
+ *     E0 = n cross(v1 - p, v2 - p),  E1 = n cross(v2 - p, v0 - p),  E2 = n cross(v0 - p, v1 - p)      (E0 + E1 + E2 = |A|)
+ *   Edge k runs from v_a to v_b (edge 0: v1 -> v2, 1: v2 -> v0, 2: v0 -> v1) with d = n (v_b - v_a); it OWNS its zero set when
+ *   d.y < 0 (a left edge: the interior lies at larger x) or d.y == 0 and d.x > 0 (a top edge: the interior lies at larger y).
+ *   The centre is inside when, for every k, E_k > 0, or E_k == 0 and edge k owns its zero set.  Two faces sharing an edge see
+ *   opposite d, so exactly one of them owns a centre on it.
+ *   Fragment depth, each step rounded on its own, E_k and |A| converted to fp32 (nearest even) first:
+ *     invz = ((E0 w0 + E1 w1) + E2 w2) / |A|,  w_k = the corners' invz;   key = (bits(invz) << 32) | (0xFFFFFFFF - face)
+ *   written by one 64-bit unsigned atomic max: the nearest fragment wins, the lower face index on equal depth, in any arrival
+ *   order.  work: [F + 1] int32 the entry owns during the call (the list of faces whose box of pixel centres holds more than 64
+ *   pixels; a second launch gives each a workgroup).
+ * tir_raster_resolve: one thread per pixel -> out [H W][4] = {int32 face (-1 = empty), b1, b2, zc}: with t_k = E_k w_k and
+ *   s = (t0 + t1) + t2 as above, b1 = t1 / s, b2 = t2 / s (perspective-correct), zc = 1 / invz of the key.
+ * tir_raster_shade: one thread per pixel, what a glTF viewer does with the file -> out [H W][TIR_RASTER_ROW] fp32 =
+ *   {albedo r g b, roughness, ao, normal x y z, coverage (1 or 0), 0, 0, 0}; an empty pixel is all zeros.  b0 = (1 - b1) - b2.
+ *   uv = sum b_k uv_k; a bilinear lookup (LINEAR, CLAMP_TO_EDGE, sample position uv * size - 0.5, no mip-maps) in the three
+ *   size x size RGBA8 images; the base colour is decoded per tap, before filtering, by the inverse of tir_atlas_pack's encoding,
+ *   s <= 0.04045 ? s / 12.92 : max(((s + 0.055) / 1.055)^2.4 - 1e-6, 0), unless raw != 0; roughness = G and ao = R of orm;
+ *   normal = normalize(tx t + ty b + tz n), (tx, ty, tz) = 2 c - 1 of the normal image, n = normalize(sum b_k nrm_k),
+ *   t = normalize(sum b_k tan_k.xyz), b = cross(n, t) * tan.w of corner 0.  base, orm and normal all NULL (tan, uv unused): a
+ *   geometry-only render, albedo / roughness / ao 0 and normal = n.
+ * All entries validate on the host before any device work: a null pointer (data pointers may be null when F = 0), a negative
+ *   count, W or H < 1, focal <= 0 or NaN, near < 0 or NaN, a misaligned buffer (rows, pix, out: 16 bytes; keys: 8; images: 4)
+ *   -> TIR_ERR_ARG; W, H or size > TIR_RASTER_MAX_SIDE, F > TIR_RASTER_MAX_FACES -> TIR_ERR_UNSUPPORTED.  F = 0 gives an empty
+ *   image.  They allocate nothing, and two calls give identical bits. */
+#define TIR_RASTER_GUARD 16384              /* pixels: a corner snapped further from the origin drops its face */
+#define TIR_RASTER_MAX_SIDE 8192
+#define TIR_RASTER_MAX_FACES 715827882      /* (2^31 - 1) / 3 */
+#define TIR_RASTER_ROW 12
+#define TIR_RASTER_DROP_NEAR      1
+#define TIR_RASTER_DROP_GUARD     2
+#define TIR_RASTER_DROP_NONFINITE 4
+#define TIR_RASTER_DROP_INDEX     8
+int tir_raster_project(const float* pos, int64_t n_verts, const int32_t* faces, int64_t n_faces, const float* c2w, float focal,
+                       int32_t W, int32_t H, float near_z, int32_t* rows, int32_t* status, void* stream);
+int tir_raster_cover(const int32_t* rows, int64_t n_faces, int32_t W, int32_t H, int32_t cull, uint64_t* keys, int32_t* work,
+                     void* stream);
+int tir_raster_resolve(const int32_t* rows, int64_t n_faces, const uint64_t* keys, int32_t W, int32_t H, int32_t* out,
+                       void* stream);
+int tir_raster_shade(const int32_t* pix, int64_t n_faces, const float* nrm, const float* tan, const float* uv, const uint8_t* base,
+                     const uint8_t* orm, const uint8_t* normal, int32_t size, int32_t raw, int32_t W, int32_t H, float* out,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -173,6 +173,10 @@ SIGNATURES = {
     "tir_atlas_corners": (C.c_int, [P, I64, P, P, I64, I32, I32, I32, P, P, P, P, P, P]),
     "tir_atlas_texels": (C.c_int, [P, I64, P, P, I64, I32, I32, I32, P, P, P, P, P]),
     "tir_atlas_pack": (C.c_int, [P, I64, P, P, I64, I32, I32, I32, P, P, P, P, P, P, P, P, P, P, P]),
+    "tir_raster_project": (C.c_int, [P, I64, P, I64, C.POINTER(C.c_float), F32, I32, I32, F32, P, P, P]),
+    "tir_raster_cover": (C.c_int, [P, I64, I32, I32, I32, P, P, P]),
+    "tir_raster_resolve": (C.c_int, [P, I64, P, I32, I32, P, P]),
+    "tir_raster_shade": (C.c_int, [P, I64, P, P, P, P, P, P, I32, I32, I32, I32, P, P]),
 }
 
 _lib = None

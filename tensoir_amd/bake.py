@@ -5,6 +5,7 @@ occlusion and direct irradiance under one of the model's lights, evaluated at su
     out = bake_points(model, points, outward)          # device tensors, one row per point
     python -m tensoir_amd.bake CKPT OUT.ply [--grid N] [--level L] [--color albedo|diffuse] [--light K]
     python -m tensoir_amd.bake CKPT OUT.glb --texture-size N [...]     # the same bake at every texel of an atlas (mesh.export_textured)
+    python -m tensoir_amd.bake CKPT OUT.glb --texture-size N --check-views V [--check-size S]   # + raster.compare_asset, one JSON line
 
 Per point p with unit outward direction n and s = model.stepSize:
   1. inward march: origin o = p + n_outside * s * n, direction d = -n, n_sample samples at z_k = k * s -- the reference's short
@@ -179,7 +180,12 @@ def main(argv=None):
     ap.add_argument("--texture-size", type=int, default=None, metavar="N", help="write OUT as a binary glTF (.glb) with an N x N "
                     "texture atlas baked at every texel (base colour, occlusion / roughness / metallic, normal) instead of a PLY "
                     "with per-vertex attributes")
+    ap.add_argument("--check-views", type=int, default=None, metavar="V", help="after writing the .glb, rasterise it from V orbit "
+                    "views, render the field from the same cameras and print the comparison (raster.compare_asset) as one JSON line")
+    ap.add_argument("--check-size", type=int, default=200, metavar="S", help="side of the S x S comparison images (default 200)")
     a = ap.parse_args(argv)
+    if a.check_views is not None and (a.texture_size is None or a.check_views < 1 or a.check_size < 1):
+        ap.error("--check-views V (V >= 1, --check-size >= 1) compares a textured export: it needs --texture-size")
     extra = {} if a.envmap is None else {"envmap_h": a.envmap[0], "envmap_w": a.envmap[1]}
     model = load_model(a.ckpt, "cuda", **extra)
     grid = None if a.grid is None else [a.grid] * 3
@@ -198,6 +204,10 @@ def main(argv=None):
     if "full" in report:
         print(f"simplify {a.simplify}: {report['full'][0]} vertices, {report['full'][1]} faces before")
     print(f"{a.out}: {nv} vertices, {nf} faces")
+    if a.check_views is not None:
+        import json
+        from . import raster
+        print(json.dumps(raster.compare_asset(model, a.out, H=a.check_size, W=a.check_size, n_views=a.check_views, grid=grid)))
 
 
 if __name__ == "__main__":

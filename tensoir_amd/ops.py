@@ -1760,3 +1760,88 @@ def atlas_pack(verts, normals, faces, size, cols, T, albedo, roughness, normal, 
         for img, rgba in zip(images, ((0, 0, 0, 255), (0, 0, 0, 255), (128, 128, 255, 255))):
             img.copy_(torch.tensor(rgba, dtype=torch.uint8, device=dev).expand(size, size, 4))
     return tuple(images)
+
+
+# ---- z-buffer rasteriser of the exported mesh (tensoir_amd/raster.py) -------------------
+RASTER_MAX_SIDE = 8192
+RASTER_ROW = 12
+RASTER_DROPS = ("index", "near", "guard", "nonfinite")     # the order of tir_raster_project's status counts
+
+
+def _raster_camera(c2w, focal):
+    c = torch.as_tensor(c2w).detach().to("cpu", torch.float32).reshape(-1)
+    if c.numel() != 12:
+        raise ValueError("c2w: expected a [3, 4] camera-to-world matrix")
+    return (C.c_float * 12)(*c.tolist()), float(focal)
+
+
+def raster_project(pos, c2w, focal, H, W, faces=None, near=1e-3):
+    """tir_raster_project: pos [3F, 3] (unwelded; or verts [V, 3] with faces [F, 3] int32) f32 on the device, c2w [3, 4] and focal
+    on the host -> (rows [3F, 4] int32 = {sx, sy, bits(1 / Z), flags}, drops = {"index", "near", "guard", "nonfinite": faces
+    dropped}).  TensoirHipError when a face index lies outside [0, V).  One 16-byte read-back (the counts)."""
+    pos = f32(pos, "pos", 3).view(-1, 3)
+    dev, V = pos.device, pos.shape[0]
+    if faces is not None:
+        faces = i32(faces, "faces").view(-1, 3)
+        if faces.device != dev:
+            raise ValueError("faces lives on pos' device")
+        F = faces.shape[0]
+    else:
+        if V % 3:
+            raise ValueError("an unwelded mesh takes three rows of pos per face")
+        F = V // 3
+    cam, focal = _raster_camera(c2w, focal)
+    rows = torch.empty((3 * F, 4), dtype=torch.int32, device=dev)
+    status = torch.zeros((4,), dtype=torch.int32, device=dev)
+    data = lambda t: _ptr(t if F else None)
+    _call("tir_raster_project", data(pos), V, data(faces), F, cam, focal, int(W), int(H), float(near), data(rows), _ptr(status),
+          _stream())
+    drops = dict(zip(RASTER_DROPS, (int(x) for x in status.tolist())))
+    if drops["index"]:
+        raise _lib.TensoirHipError("raster_project: a face index lies outside [0, V)")
+    return rows, drops
+
+
+def raster_cover(rows, H, W, cull=True):
+    """tir_raster_cover: the projected corners -> keys [H, W] int64 holding the uint64 (bits(1 / Z) << 32) | (0xFFFFFFFF - face)
+    of the nearest fragment, 0 where the pixel is empty."""
+    rows = i32(rows, "rows").view(-1, 4)
+    F = rows.shape[0] // 3
+    big = 0 < int(W) <= RASTER_MAX_SIDE and 0 < int(H) <= RASTER_MAX_SIDE
+    keys = torch.empty((int(H), int(W)) if big else (1, 1), dtype=torch.int64, device=rows.device)   # the library words the refusal
+    work = torch.empty((F + 1,), dtype=torch.int32, device=rows.device)
+    _call("tir_raster_cover", _ptr(rows if F else None), F, int(W), int(H), int(bool(cull)), _ptr(keys), _ptr(work), _stream())
+    return keys
+
+
+def raster_resolve(rows, keys):
+    """tir_raster_resolve -> (face [H, W] int32, -1 where empty; bary [H, W, 2] f32 = (b1, b2), perspective-correct; zc [H, W] f32,
+    the camera-space depth Z), views of one [H, W, 4] buffer."""
+    rows = i32(rows, "rows").view(-1, 4)
+    keys = _req(keys, torch.int64, "keys")
+    H, W = keys.shape
+    F = rows.shape[0] // 3
+    out = torch.empty((H, W, 4), dtype=torch.int32, device=rows.device)
+    _call("tir_raster_resolve", _ptr(rows if F else None), F, _ptr(keys), W, H, _ptr(out), _stream())
+    return out[..., 0], out[..., 1:3].view(torch.float32), out[..., 3].view(torch.float32), out
+
+
+def raster_shade(pix, nrm, tan=None, uv=None, images=None, raw=False):
+    """tir_raster_shade: pix [H, W, 4] (raster_resolve's buffer), the per-corner nrm [3F, 3], tan [3F, 4], uv [3F, 2] and
+    images = (base, orm, normal) [S, S, 4] uint8 on the device -> [H, W, 12] f32 rows {albedo 3, roughness, ao, normal 3,
+    coverage, 0, 0, 0}.  images None: geometry only (normal = the interpolated unit nrm)."""
+    pix = _req(pix, torch.int32, "pix", 4)
+    H, W = pix.shape[:2]
+    nrm = f32(nrm, "nrm", 3).view(-1, 3)
+    F = nrm.shape[0] // 3
+    size, ptrs = 0, [None] * 5
+    if images is not None:
+        tan, uv = f32(tan, "tan", 4).view(-1, 4), f32(uv, "uv", 2).view(-1, 2)
+        images = [_req(im, torch.uint8, "images", 4) for im in images]
+        size = images[0].shape[0]
+        if tan.shape[0] != 3 * F or uv.shape[0] != 3 * F or len(images) != 3 or any(tuple(im.shape) != (size, size, 4) for im in images):
+            raise ValueError("tan [3F, 4], uv [3F, 2] and three [S, S, 4] images are expected")
+        ptrs = [_ptr(tan if F else None), _ptr(uv if F else None)] + [_ptr(im) for im in images]
+    out = torch.empty((H, W, RASTER_ROW), dtype=torch.float32, device=pix.device)
+    _call("tir_raster_shade", _ptr(pix), F, _ptr(nrm if F else None), *ptrs, int(size), int(bool(raw)), W, H, _ptr(out), _stream())
+    return out

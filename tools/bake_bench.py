@@ -5,6 +5,7 @@ tools/mesh_bench.py uses (the small golden checkpoint), with the default 16 x 32
     rocprofv3 --kernel-trace --stats --output-format csv -d DIR -o bake -- python tools/bake_bench.py --reps 1
     python tools/bake_bench.py --stats DIR                      # per-kernel GPU time from that trace
     python tools/bake_bench.py --texture-size 2048 4096 [--simplify 3]     # the textured export instead: one JSON line per size
+    python tools/bake_bench.py --raster [--views 8] [--image 800]           # the rasteriser on the exported assets: one JSON line per mesh
 
 The JSON line: geometry_ms (extract_mesh), material_ms (bake_points(lighting=False): inward march, decoders, tir_bake_composite),
 lighting_ms (the rest of bake_points: pair mask, visibility march, tir_irradiance_integrate) -- device events around the calls,
@@ -15,7 +16,14 @@ launch, summed over the chunks) and the rate as a fraction of the 6.3 TB/s HBM c
 The --texture-size leg (mesh.export_textured): layout_ms (tir_atlas_corners + tir_atlas_texels), bake_ms (field_positions
 + bake_points at every texel), pack_ms (tir_atlas_pack) -- device events, best of --reps; png_write_s (PNG compression of the
 three images + the GLB write, wall clock); export_s (the whole export_textured call, wall clock, after a warm-up); and for
-k_atlas_texels and k_atlas_pack the bytes they must move, their time and the rate against the same ceiling."""
+k_atlas_texels and k_atlas_pack the bytes they must move, their time and the rate against the same ceiling.
+
+The --raster leg (tensoir_amd/raster.py): the simplify=3 mesh and the full mesh of the same lattice, exported with
+export_textured, rasterised at --image x --image from --views orbit cameras.  Per mesh: project_ms / cover_ms / resolve_ms / shade_ms
+(device events around each entry, memsets included, per view: the mean over the views of the best of --reps), faces and covered pixels
+per second of cover (the covered pixels are a lower bound of the fragments), the bytes resolve and shade must move against the HBM
+ceiling, and compare_wall_s (raster.compare_asset over the same views, wall clock, after a
+warm-up; it includes the field's own renders and reading the file)."""
 import argparse
 import csv
 import glob
@@ -40,7 +48,7 @@ def stats(d):
         name = r["Name"].replace("(anonymous namespace)::", "").split("(")[0].replace("void ", "")
         out[name] = {"calls": int(r["Calls"]), "total_ms": float(r["TotalDurationNs"]) / 1e6, "avg_us": float(r["AverageNs"]) / 1e3}
     top = dict(sorted(out.items(), key=lambda kv: -kv[1]["total_ms"])[:14])
-    top.update({k: v for k, v in out.items() if k.startswith("k_atlas_")})         # the streaming kernels of the textured leg
+    top.update({k: v for k, v in out.items() if k.startswith(("k_atlas_", "k_raster_"))})    # the streaming kernels of the textured / raster legs
     print(json.dumps({"kernels": top, "total_ms": sum(v["total_ms"] for v in out.values())}, indent=1))
 
 
@@ -194,6 +202,66 @@ def run_textured(n, sizes, simplify, reps):
                            "of_hbm": rate(pack_bytes, k["tir_atlas_pack"]) / HBM_TBS}}), flush=True)
 
 
+def run_raster(n, views, image, reps):
+    import numpy as np
+    import torch
+
+    import tensoir_amd
+    from tensoir_amd import mesh, ops, raster
+    from tests.helpers import golden_checkpoint
+    g = np.load(os.path.join(ROOT, "tests", "golden", "small_scene.npz"))
+    model = tensoir_amd.model_from_checkpoint(golden_checkpoint(g), "cuda:0")
+    grid = [n, n, n]
+    H = W = image
+    rate = lambda b, ms: b / (ms * 1e-3) / 1e12
+    entries = ("tir_raster_project", "tir_raster_cover", "tir_raster_resolve", "tir_raster_shade")
+    with tempfile.TemporaryDirectory() as d:
+        for simplify, size in ((3, 2048), (None, 4096)):
+            path = os.path.join(d, f"m{simplify}.glb")
+            _, F = mesh.export_textured(model, path, 0.005, grid, size, simplify=simplify)
+            report = raster.compare_asset(model, path, H=H, W=W, n_views=views, grid=grid)          # warm-up, and the cameras' focal
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            report = raster.compare_asset(model, path, H=H, W=W, n_views=views, grid=grid)
+            torch.cuda.synchronize()
+            wall = time.perf_counter() - t0
+            file = mesh.read_glb(path)
+            dev = lambda a: torch.from_numpy(a).cuda()
+            pos = mesh.field_positions(model.aabb, grid, dev(file["pos"])).contiguous()
+            nrm, tan, uv = dev(file["nrm"]), dev(file["tan"]), dev(file["uv"])
+            images = {k: dev(np.ascontiguousarray(v)) for k, v in file["images"].items()}
+            dist = 0.5 * (float(model.near_far[0]) + float(model.near_far[1]))
+            cams = raster.orbit_cameras(model.aabb, views, distance=dist)
+            best = {k: [float("inf")] * views for k in entries}
+            covered = []
+            for rep in range(reps + 1):
+                for vi, c2w in enumerate(cams):
+                    ops.TIMING = []
+                    out = raster.render_mesh(pos, nrm, tan, uv, images, c2w, report["focal"], H, W)
+                    torch.cuda.synchronize()
+                    calls, ops.TIMING = ops.TIMING, None
+                    if rep:
+                        for k in entries:
+                            best[k][vi] = min(best[k][vi], sum(e0.elapsed_time(e1) for name, e0, e1 in calls if name == k))
+                    else:
+                        covered.append(int((out["coverage"] > 0.5).sum()))
+            ms = {k: sum(v) / views for k, v in best.items()}
+            res_bytes = H * W * (8 + 16) + 3 * F * 16                       # key in, row out; the corner rows once
+            shade_bytes = H * W * (16 + 48) + 3 * F * (12 + 16 + 8) + 3 * 4 * size * size     # row in, 12 floats out; corners, images once
+            print(json.dumps({
+                "grid": n, "simplify": simplify, "faces": F, "size": size, "image": image, "views": views,
+                "covered_pixels": sum(covered) / views,
+                "project_ms": ms["tir_raster_project"], "cover_ms": ms["tir_raster_cover"], "resolve_ms": ms["tir_raster_resolve"],
+                "shade_ms": ms["tir_raster_shade"], "raster_ms": sum(ms.values()),
+                "faces_per_s": F / (ms["tir_raster_cover"] * 1e-3),
+                "covered_pixels_per_s": sum(covered) / views / (ms["tir_raster_cover"] * 1e-3),
+                "resolve": {"bytes": res_bytes, "TB_s": rate(res_bytes, ms["tir_raster_resolve"]),
+                            "of_hbm": rate(res_bytes, ms["tir_raster_resolve"]) / HBM_TBS},
+                "shade": {"bytes": shade_bytes, "TB_s": rate(shade_bytes, ms["tir_raster_shade"]),
+                          "of_hbm": rate(shade_bytes, ms["tir_raster_shade"]) / HBM_TBS},
+                "compare_wall_s": wall, "compare_mean": report["mean"]}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--grid", type=int, default=300)
@@ -202,9 +270,14 @@ def main():
     ap.add_argument("--texture-size", type=int, nargs="+", default=None, metavar="N", help="time the textured export "
                     "(mesh.export_textured) at these atlas sizes instead of the per-vertex bake")
     ap.add_argument("--simplify", type=int, default=3, help="the face budget of the --texture-size leg")
+    ap.add_argument("--raster", action="store_true", help="time the rasteriser (tensoir_amd/raster.py) on the exported assets instead")
+    ap.add_argument("--views", type=int, default=8, help="orbit views of the --raster leg")
+    ap.add_argument("--image", type=int, default=800, help="image side of the --raster leg")
     a = ap.parse_args()
     if a.stats:
         return stats(a.stats)
+    if a.raster:
+        return run_raster(a.grid, a.views, a.image, a.reps)
     if a.texture_size:
         return run_textured(a.grid, a.texture_size, a.simplify, a.reps)
     run(a.grid, a.reps)
