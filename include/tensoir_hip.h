@@ -1019,6 +1019,46 @@ int tir_raster_shade(const int32_t* pix, int64_t n_faces, const float* nrm, cons
                      const uint8_t* orm, const uint8_t* normal, int32_t size, int32_t raw, int32_t W, int32_t H, float* out,
                      void* stream);
 
+/* ---- Lighting of the exported asset: environment -> light cells, deferred GGX lighting of a G-buffer (tensoir_amd/raster.py
+ * relight_mesh / relight_glb / compare_asset(light=); restated in numpy by tests/light_reference.py).
+ * tir_env_cells: an equirectangular map hdr [H][W][3] (row 0 at the top, as Environment_Light reads it) -> cells [h w][8] fp32 =
+ *   {dir.x, dir.y, dir.z, Omega, r, g, b, 0}: the 32-byte record of tir_relight_importance_cells_packed with the cell's solid
+ *   angle in the pdf slot.  H = a h and W = b w with integers a, b >= 1.  row_w [H] (device) is the exact solid angle of one
+ *   texel of row i, Omega_i = (2 pi / W) * 2 sin(pi (i + 0.5) / H) * sin(pi / (2 H)), computed by the caller in float64 and
+ *   rounded once (ops.env_row_weights; sum_i W Omega_i = 4 pi.  The 0.5 / H end points of the reference's sin_theta table are
+ *   not copied: these weights belong to no reference function).  Cell (r, c) covers the texel rows [a r, a r + a) and columns
+ *   [b c, b c + b):  Omega = b * sum_i row_w[i];  rgb = sum_i sum_j row_w[i] hdr[i][j] / sum_i sum_j row_w[i], numerator (fused
+ *   multiply-adds) and denominator accumulated in fp32 in row-major order, one thread per cell;  dir = (cos t cos p, sin t cos p,
+ *   sin p) with p = pi / 2 - (r + 0.5) pi / h and t = pi - (c + 0.5) 2 pi / w, the centre of the cell on the h x w grid by
+ *   Environment_Light's formula (the angles are formed in double and rounded to fp32 once).
+ *   H, W, h or w < 1, H % h or W % w != 0, a null pointer, cells not 16-byte aligned -> TIR_ERR_ARG; H W > 2^28 ->
+ *   TIR_ERR_UNSUPPORTED.
+ * tir_light_gbuffer: gbuf [M][TIR_RASTER_ROW] is what tir_raster_shade writes {albedo r g b, roughness, ao, normal x y z,
+ *   coverage, 0, 0, 0}; view [M][3] the vector from the surface to the eye (any length); cells [D][8] as above; out [M][4] =
+ *   {r, g, b, coverage}.  A row whose coverage is not > 0 gives four zeros and reads no light.  A covered row, with the surface
+ *   terms of GGX_specular (models/relight_utils.py:22-49; the same formula as tir_ggx_specular) for a scalar roughness rho and a
+ *   scalar fresnel F:
+ *     V = view / max(|view|, 1e-12);  N = n / max(|n|, 1e-12) * sign(N.V) (n = the stored normal);  NoV = clamp(N.V, 1e-6, 1);
+ *     alpha2 = rho^4;  k = (rho^2 + 2 rho + 1) / 8;  alb_pi = albedo / pi
+ *   and for each cell d in ascending order, L = cells[d].dir as stored (not renormalised):
+ *     c = n.L with the stored, unflipped normal (models/relight_utils.py:433-435); the pair contributes iff c > 1e-6, with
+ *     Hv = (L + V) / 2;  Hv = Hv * rsq(max(|Hv|^2, 1e-24));  NoL, NoH, VoH = clamp(N.L, N.Hv, V.Hv to [1e-6, 1]);
+ *     spec = (F + (1 - F) 2^((-5.55473 VoH - 6.98316) VoH)) alpha2
+ *            / clamp(4 pi (NoH^2 (alpha2 - 1) + 1)^2 (NoV (1 - k) + k) (NoL (1 - k) + k), 1e-6, 4 pi)
+ *     sum_q += (((alb_pi_q + spec) * rgb_d,q) * c) * Omega_d                               (q = r, g, b; products in this order)
+ *   rsq, 2^x and the reciprocal of the denominator are the one-ulp hardware instructions; sums of products may be fused.
+ *   TIR_LIGHT_OCCLUSION multiplies the sums by ao; TIR_LIGHT_SRGB then applies linear2srgb (clamp to [0, 1], x <= 0.0031308 ?
+ *   12.92 x : 1.055 (x + 1e-6)^(1 / 2.4) - 0.055, models/relight_utils.py:489-515); without it the sums are not clamped.
+ *   One thread per row over all M rows (no compaction of the covered rows); nothing is allocated, there are no atomics and the
+ *   order per row is fixed: two calls give identical bits, and a row's result does not depend on where it stands in the buffer.
+ *   Validated on the host before any device work: M < 0, D < 1, unknown flag bits, and with M > 0 a null pointer or gbuf, cells
+ *   or out not 16-byte aligned -> TIR_ERR_ARG; D > 2^20 (or M > 2^36) -> TIR_ERR_UNSUPPORTED.  M = 0 does nothing. */
+#define TIR_LIGHT_OCCLUSION 1
+#define TIR_LIGHT_SRGB      2
+int tir_env_cells(const float* hdr, int32_t H, int32_t W, const float* row_w, int32_t h, int32_t w, float* cells, void* stream);
+int tir_light_gbuffer(const float* gbuf, const float* view, const float* cells, int64_t M, int32_t D, float fresnel, int32_t flags,
+                      float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

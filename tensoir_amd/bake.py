@@ -6,6 +6,8 @@ occlusion and direct irradiance under one of the model's lights, evaluated at su
     python -m tensoir_amd.bake CKPT OUT.ply [--grid N] [--level L] [--color albedo|diffuse] [--light K]
     python -m tensoir_amd.bake CKPT OUT.glb --texture-size N [...]     # the same bake at every texel of an atlas (mesh.export_textured)
     python -m tensoir_amd.bake CKPT OUT.glb --texture-size N --check-views V [--check-size S]   # + raster.compare_asset, one JSON line
+    ... --check-views V --check-light NAME|FILE.hdr|FILE.npy [--check-light-rows R] [--write-views DIR]   # + relit_psnr
+    ... --environment OUT.hdr [--environment-size H W]                  # + the recovered light as a Radiance picture
 
 Per point p with unit outward direction n and s = model.stepSize:
   1. inward march: origin o = p + n_outside * s * n, direction d = -n, n_sample samples at z_k = k * s -- the reference's short
@@ -160,7 +162,7 @@ def load_model(path, device="cuda", **extra):
 
 def main(argv=None):
     import argparse
-    from . import mesh
+    from . import mesh, synth
     ap = argparse.ArgumentParser(prog="python -m tensoir_amd.bake", description="Export a checkpoint's surface as a binary PLY with "
                                  "per-vertex normals, colour, roughness, ambient occlusion, coverage, albedo and direct irradiance.")
     ap.add_argument("ckpt")
@@ -183,9 +185,22 @@ def main(argv=None):
     ap.add_argument("--check-views", type=int, default=None, metavar="V", help="after writing the .glb, rasterise it from V orbit "
                     "views, render the field from the same cameras and print the comparison (raster.compare_asset) as one JSON line")
     ap.add_argument("--check-size", type=int, default=200, metavar="S", help="side of the S x S comparison images (default 200)")
+    ap.add_argument("--check-light", default=None, metavar="NAME|FILE", help="with --check-views: also light the field's and the "
+                    "asset's G-buffer with this environment and report relit_psnr; one of the synthetic maps "
+                    f"({', '.join(synth.HDR_NAMES)}; 64 x 128), a Radiance .hdr file or a .npy array [H, W, 3]")
+    ap.add_argument("--check-light-rows", type=int, default=16, metavar="R", help="light cells: R x 2R (default 16)")
+    ap.add_argument("--write-views", default=None, metavar="DIR", help="with --check-light: write every view's field-lit and "
+                    "asset-lit image as PNG into DIR")
+    ap.add_argument("--environment", default=None, metavar="OUT.hdr", help="also write the model's light --light as a Radiance "
+                    "picture (mesh.export_environment)")
+    ap.add_argument("--environment-size", type=int, nargs=2, metavar=("H", "W"), default=(256, 512))
     a = ap.parse_args(argv)
     if a.check_views is not None and (a.texture_size is None or a.check_views < 1 or a.check_size < 1):
         ap.error("--check-views V (V >= 1, --check-size >= 1) compares a textured export: it needs --texture-size")
+    if a.check_light is not None and a.check_views is None:
+        ap.error("--check-light lights the views of --check-views")
+    if a.write_views is not None and a.check_light is None:
+        ap.error("--write-views writes the images of --check-light")
     extra = {} if a.envmap is None else {"envmap_h": a.envmap[0], "envmap_w": a.envmap[1]}
     model = load_model(a.ckpt, "cuda", **extra)
     grid = None if a.grid is None else [a.grid] * 3
@@ -204,10 +219,17 @@ def main(argv=None):
     if "full" in report:
         print(f"simplify {a.simplify}: {report['full'][0]} vertices, {report['full'][1]} faces before")
     print(f"{a.out}: {nv} vertices, {nf} faces")
+    if a.environment is not None:
+        mesh.export_environment(model, a.environment, a.environment_size[0], a.environment_size[1], light=a.light)
+        print(f"{a.environment}: light {a.light}, {a.environment_size[0]} x {a.environment_size[1]}")
     if a.check_views is not None:
         import json
         from . import raster
-        print(json.dumps(raster.compare_asset(model, a.out, H=a.check_size, W=a.check_size, n_views=a.check_views, grid=grid)))
+        light = a.check_light
+        if light in synth.HDR_NAMES:
+            light = synth.make_hdr_maps(synth.HDR_NAMES, 64, 128)[light]            # as Environment_Light("synthetic:h=64,w=128")
+        print(json.dumps(raster.compare_asset(model, a.out, H=a.check_size, W=a.check_size, n_views=a.check_views, grid=grid, light=light,
+                                              light_rows=a.check_light_rows, write_views=a.write_views)))
 
 
 if __name__ == "__main__":

@@ -609,7 +609,117 @@ k_ggx(const float* __restrict__ normal, const float* __restrict__ v, const float
     spec[3 * i] = sp[0]; spec[3 * i + 1] = sp[1]; spec[3 * i + 2] = sp[2];
 }
 
+// ---- lighting of an exported asset (contract: include/tensoir_hip.h) ------------------------------------------------
+// An H x W equirectangular map reduced to h x w light cells, one thread per cell (this runs once per map): the solid-angle
+// weighted mean radiance of the cell's a x b texels, its solid angle, and the direction of its centre.
+__global__ void __launch_bounds__(256)
+k_env_cells(const float* __restrict__ hdr, int H, int W, const float* __restrict__ row_w, int h, int w, float* __restrict__ cells) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (int64_t)h * w) return;
+    const int r = (int)(t / w), c = (int)(t % w);
+    const int a = H / h, b = W / w;
+    float rgb[3] = {0.f, 0.f, 0.f};
+    float wsum = 0.f, rows = 0.f;
+    for (int i = a * r; i < a * r + a; ++i) {
+        const float wi = row_w[i];
+        rows += wi;
+        const float* p = hdr + 3 * ((size_t)i * W + (size_t)b * c);
+        for (int j = 0; j < b; ++j) {
+            rgb[0] = fmaf(wi, p[3 * j], rgb[0]); rgb[1] = fmaf(wi, p[3 * j + 1], rgb[1]); rgb[2] = fmaf(wi, p[3 * j + 2], rgb[2]);
+            wsum += wi;
+        }
+    }
+    // the centre of cell (r, c) on the h x w grid, Environment_Light's formula (models/relight_utils.py:137-142); the angles are
+    // formed in double and rounded once
+    const double PI = 3.14159265358979323846;
+    const float phi = (float)(0.5 * PI - ((double)r + 0.5) * (PI / (double)h));
+    const float theta = (float)(PI - ((double)c + 0.5) * (2.0 * PI / (double)w));
+    const float cp = cosf(phi);
+    float4* o = reinterpret_cast<float4*>(cells + 8 * (size_t)t);
+    o[0] = make_float4(cosf(theta) * cp, sinf(theta) * cp, sinf(phi), (float)b * rows);
+    o[1] = make_float4(rgb[0] / wsum, rgb[1] / wsum, rgb[2] / wsum, 0.f);
+}
+
+// Deferred lighting of a G-buffer: one thread per pixel, every per-surface quantity in registers for all D light cells.  The
+// cell index is the loop counter, the same in every lane, and cells is read-only for the kernel: the compiler fetches a record
+// with scalar loads into SGPRs, which the VALU reads as operands (no LDS tile, no per-lane addresses).  Pairs below the horizon
+// are skipped by a per-lane branch.  rsq, exp2 and rcp are the hardware's one-ulp instructions.  No atomics, a fixed order per
+// pixel: two calls give identical bits, whatever the order of the pixels.
+__global__ void __launch_bounds__(256)
+k_light_gbuffer(const float4* __restrict__ gbuf, const float* __restrict__ view, const float4* __restrict__ cells, int64_t M, int D,
+                float fresnel, int flags, float4* __restrict__ out) {
+    const int64_t m = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (m >= M) return;
+    const float4 g0 = gbuf[3 * m], g1 = gbuf[3 * m + 1], g2 = gbuf[3 * m + 2];      // TIR_RASTER_ROW = 12 floats
+    const float cov = g2.x;
+    if (!(cov > 0.f)) { out[m] = make_float4(0.f, 0.f, 0.f, 0.f); return; }
+    const float rough = g0.w, ao = g1.x;
+    const float ns[3] = {g1.y, g1.z, g1.w};                                        // the stored normal: the cosine's (unflipped)
+    const float rough3[3] = {rough, rough, rough}, fres3[3] = {fresnel, fresnel, fresnel}, alb[3] = {g0.x, g0.y, g0.z};
+    const Surface s = make_surface(ns, view + 3 * m, rough3, fres3, alb);
+    const float alpha2 = s.alpha2[0], k = s.k[0], omk = 1.f - k, omf = 1.f - fresnel;
+    const float nom1 = s.NoV * omk + k;
+    const float four_pi = 4.0f * 3.14159265358979323846f;
+    float acc[3] = {0.f, 0.f, 0.f};
+    for (int d = 0; d < D; ++d) {
+        const float4 ca = cells[2 * (size_t)d], cb = cells[2 * (size_t)d + 1];
+        const float lx = ca.x, ly = ca.y, lz = ca.z;
+        const float c = ns[0] * lx + ns[1] * ly + ns[2] * lz;
+        if (c > 1e-6f) {
+            float hx = (lx + s.V[0]) * 0.5f, hy = (ly + s.V[1]) * 0.5f, hz = (lz + s.V[2]) * 0.5f;
+            const float inv = __builtin_amdgcn_rsqf(fmaxf(hx * hx + hy * hy + hz * hz, 1e-24f));    // x / max(|x|, 1e-12)
+            hx *= inv; hy *= inv; hz *= inv;
+            const float NoL = fminf(fmaxf(s.N[0] * lx + s.N[1] * ly + s.N[2] * lz, 1e-6f), 1.f);
+            const float NoH = fminf(fmaxf(s.N[0] * hx + s.N[1] * hy + s.N[2] * hz, 1e-6f), 1.f);
+            const float VoH = fminf(fmaxf(s.V[0] * hx + s.V[1] * hy + s.V[2] * hz, 1e-6f), 1.f);
+            const float p2 = __builtin_amdgcn_exp2f(((-5.55473f) * VoH - 6.98316f) * VoH);
+            const float frac = (fresnel + omf * p2) * alpha2;
+            const float nom0 = NoH * NoH * (alpha2 - 1.f) + 1.f;
+            const float nom2 = NoL * omk + k;
+            const float nom = fminf(fmaxf(four_pi * nom0 * nom0 * nom1 * nom2, 1e-6f), four_pi);
+            const float spec = frac * __builtin_amdgcn_rcpf(nom);
+            acc[0] += (s.alb_pi[0] + spec) * cb.x * c * ca.w;
+            acc[1] += (s.alb_pi[1] + spec) * cb.y * c * ca.w;
+            acc[2] += (s.alb_pi[2] + spec) * cb.z * c * ca.w;
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+        if (flags & TIR_LIGHT_OCCLUSION) acc[q] *= ao;
+        if (flags & TIR_LIGHT_SRGB) acc[q] = linear2srgb(acc[q]);
+    }
+    out[m] = make_float4(acc[0], acc[1], acc[2], cov);
+}
+
 }  // namespace
+
+extern "C" int tir_env_cells(const float* hdr, int32_t H, int32_t W, const float* row_w, int32_t h, int32_t w, float* cells,
+                             void* stream) {
+    if (H < 1 || W < 1 || h < 1 || w < 1 || H % h != 0 || W % w != 0) return TIR_ERR_ARG;
+    if (!hdr || !row_w || !cells || reinterpret_cast<uintptr_t>(cells) % 16 != 0) return TIR_ERR_ARG;
+    if ((int64_t)H * W > ((int64_t)1 << 28)) return TIR_ERR_UNSUPPORTED;
+    const int64_t n = (int64_t)h * w;
+    hipLaunchKernelGGL(k_env_cells, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, tir_stream(stream), hdr, H, W, row_w, h, w,
+                       cells);
+    TIR_CHECK_LAUNCH();
+    return TIR_OK;
+}
+
+extern "C" int tir_light_gbuffer(const float* gbuf, const float* view, const float* cells, int64_t M, int32_t D, float fresnel,
+                                 int32_t flags, float* out, void* stream) {
+    if (M < 0 || D < 1 || (flags & ~(TIR_LIGHT_OCCLUSION | TIR_LIGHT_SRGB))) return TIR_ERR_ARG;
+    if (D > (1 << 20) || M > ((int64_t)1 << 36)) return TIR_ERR_UNSUPPORTED;
+    if (M == 0) return TIR_OK;
+    if (!gbuf || !view || !cells || !out) return TIR_ERR_ARG;
+    if (reinterpret_cast<uintptr_t>(gbuf) % 16 != 0 || reinterpret_cast<uintptr_t>(cells) % 16 != 0 ||
+        reinterpret_cast<uintptr_t>(out) % 16 != 0)
+        return TIR_ERR_ARG;
+    hipLaunchKernelGGL(k_light_gbuffer, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, tir_stream(stream),
+                       reinterpret_cast<const float4*>(gbuf), view, reinterpret_cast<const float4*>(cells), M, (int)D, fresnel,
+                       (int)flags, reinterpret_cast<float4*>(out));
+    TIR_CHECK_LAUNCH();
+    return TIR_OK;
+}
 
 extern "C" int tir_env_sg_fwd(const TirEnvSG* e, const float* dirs, int32_t D, float* out, void* stream) {
     if (!e || !e->sgs || !e->rot || e->n_sg <= 0 || e->n_lights <= 0 || D < 0) return TIR_ERR_ARG;

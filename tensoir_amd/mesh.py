@@ -552,3 +552,27 @@ def export_textured(model, path, level=0.005, gridSize=None, size=2048, color="a
     write_glb(path, a["pos"], a["nrm"], a["tan"], a["uv"], {k: a[k].cpu().numpy() for k in IMAGE_NAMES}, extras,
               occlusion=bool(bake_kw.get("lighting", True)), compress_level=int(compress_level))
     return 3 * F, F
+
+
+@torch.no_grad()
+def export_environment(model, path, H=256, W=512, light=0):
+    """The illumination the model has recovered as a Radiance picture: model.get_light_rgbs at the H x W cell-centre directions
+    of relight.Environment_Light (row i at phi = pi/2 - (i + 0.5) pi/H, column j at theta = pi - (j + 0.5) 2 pi/W, direction
+    (cos theta cos phi, sin theta cos phi, sin phi)), row `light` of the result, written with hdr.write_hdr.  Read back and
+    handed to Environment_Light(hdr_maps=...) or raster.relight_glb, the file therefore means the same illumination in world
+    space.  light_kind 'sg' and 'pixel'; 'gt' passes the data set's probe through (and raises the model's own error without
+    one).  -> the [H, W, 3] float32 array that was written (before the RGBE rounding)."""
+    from .hdr import write_hdr
+    H, W = int(H), int(W)
+    if H < 1 or W < 1:
+        raise ValueError("export_environment: H, W >= 1")
+    lat, lng = np.pi / H, 2 * np.pi / W
+    phi, theta = torch.meshgrid([torch.linspace(np.pi / 2 - 0.5 * lat, -np.pi / 2 + 0.5 * lat, H),
+                                 torch.linspace(np.pi - 0.5 * lng, -np.pi + 0.5 * lng, W)], indexing="ij")
+    dirs = torch.stack([torch.cos(theta) * torch.cos(phi), torch.sin(theta) * torch.cos(phi), torch.sin(phi)], dim=-1).view(-1, 3)
+    rgbs = model.get_light_rgbs(dirs, device=model.aabb.device)
+    if not 0 <= int(light) < rgbs.shape[0]:
+        raise ValueError(f"export_environment: light outside 0 .. {rgbs.shape[0] - 1}")
+    rgb = rgbs[int(light)].detach().reshape(H, W, 3).to("cpu", torch.float32).numpy()
+    write_hdr(path, rgb)
+    return rgb

@@ -6,6 +6,7 @@ libtensoir_hip.so.  All functions require CUDA(HIP) tensors and raise otherwise 
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 
 import torch
@@ -1844,4 +1845,47 @@ def raster_shade(pix, nrm, tan=None, uv=None, images=None, raw=False):
         ptrs = [_ptr(tan if F else None), _ptr(uv if F else None)] + [_ptr(im) for im in images]
     out = torch.empty((H, W, RASTER_ROW), dtype=torch.float32, device=pix.device)
     _call("tir_raster_shade", _ptr(pix), F, _ptr(nrm if F else None), *ptrs, int(size), int(bool(raw)), W, H, _ptr(out), _stream())
+    return out
+
+
+# ---- lighting of the exported asset (tensoir_amd/raster.py) -----------------------------
+LIGHT_OCCLUSION = 1
+LIGHT_SRGB = 2
+
+
+def env_row_weights(H, W):
+    """float64 [H]: the exact solid angle of one texel of row i of an H x W equirectangular map,
+    (2 pi / W) * 2 sin(pi (i + 0.5) / H) * sin(pi / (2 H)); W times their sum is 4 pi."""
+    i = torch.arange(int(H), dtype=torch.float64)
+    return (2.0 * math.pi / int(W)) * 2.0 * torch.sin(math.pi * (i + 0.5) / int(H)) * math.sin(math.pi / (2.0 * int(H)))
+
+
+def env_cells(hdr, h, w):
+    """tir_env_cells: an [H, W, 3] map on the device -> [h * w, 8] light cells {dir, solid angle, rgb, 0}, each the solid-angle
+    weighted mean of its (H / h) x (W / w) texels.  ValueError unless H and W are multiples of h and w."""
+    hdr = f32(hdr, "hdr", 3)
+    if hdr.dim() != 3:
+        raise ValueError("env_cells: an [H, W, 3] map is expected")
+    H, W, h, w = hdr.shape[0], hdr.shape[1], int(h), int(w)
+    if h < 1 or w < 1 or H % h or W % w:
+        raise ValueError(f"env_cells: the map's sides {H} x {W} must be multiples of the cell grid's {h} x {w}")
+    row_w = to_device(env_row_weights(H, W).to(torch.float32), hdr.device)
+    cells = torch.empty((h * w, 8), dtype=torch.float32, device=hdr.device)
+    _call("tir_env_cells", _ptr(hdr), H, W, _ptr(row_w), h, w, _ptr(cells), _stream())
+    return cells
+
+
+def light_gbuffer(gbuf, view, cells, fresnel=0.04, occlusion=True, srgb=False):
+    """tir_light_gbuffer: gbuf [..., 12] (raster_shade's rows), view [..., 3] (surface to eye), cells [D, 8] (env_cells) ->
+    [..., 4] = {r, g, b, coverage}: the environment integrated against albedo / pi + GGX over the cells above the stored normal's
+    horizon, times ao with occlusion, tone-mapped with srgb.  Rows without coverage are zeros."""
+    gbuf, view, cells = f32(gbuf, "gbuf", RASTER_ROW), f32(view, "view", 3), f32(cells, "cells", 8).view(-1, 8)
+    if gbuf.shape[:-1] != view.shape[:-1]:
+        raise ValueError("light_gbuffer: gbuf and view take one row per pixel")
+    if cells.shape[0] < 1:
+        raise ValueError("light_gbuffer: at least one light cell")
+    out = torch.empty(gbuf.shape[:-1] + (4,), dtype=torch.float32, device=gbuf.device)
+    flags = (LIGHT_OCCLUSION if occlusion else 0) | (LIGHT_SRGB if srgb else 0)
+    _call("tir_light_gbuffer", _ptr(gbuf), _ptr(view), _ptr(cells), gbuf.numel() // RASTER_ROW, cells.shape[0], float(fresnel), flags,
+          _ptr(out), _stream())
     return out

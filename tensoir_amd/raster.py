@@ -4,6 +4,8 @@ include/tensoir_hip.h, tir_raster_*), and the comparison of a textured GLB with 
     out = render_mesh(pos, nrm, tan, uv, images, c2w, focal, H, W)        # device tensors, one row per pixel
     out = render_glb("scene.glb", c2w, focal, H, W, aabb=model.aabb, grid=model.gridSize)
     report = compare_asset(model, "scene.glb", n_views=8)                  # silhouette, albedo, roughness, normals, depth
+    out = relight_glb("scene.glb", "city.hdr", c2w, focal, H, W)          # + "rgb": the asset under an environment
+    report = compare_asset(model, "scene.glb", light="city.hdr")          # + relit_psnr: the same light on field and asset
 
 Camera: the datasets' convention.  Pixel (i, j) has its centre at (i + 0.5, j + 0.5) and the camera-space direction
 ((i + 0.5 - W/2) / f, (j + 0.5 - H/2) / f, 1); c2w [3, 4] has the columns x right, y down, z forward and the eye.  All per-corner
@@ -11,6 +13,7 @@ and per-pixel work runs in libtensoir_hip.so (ops.raster_*); there is no CPU pat
 from __future__ import annotations
 
 import math
+import os
 
 import numpy as np
 import torch
@@ -84,6 +87,11 @@ def render_mesh(pos, nrm, tan, uv, images, c2w, focal, H, W, cull=True, raw=Fals
     along the pixel's unit ray, comparable with depth_map; 0 where empty), albedo [H, W, 3] (linear; the bytes / 255 with
     raw=True), roughness, ao, coverage [H, W], normal [H, W, 3], and "drops", the faces project left out.
     cull: draw front faces only (outward-oriented meshes).  No clipping: a face with a corner at Z <= near is dropped."""
+    return _render(pos, nrm, tan, uv, images, c2w, focal, H, W, cull, raw, near)[0]
+
+
+def _render(pos, nrm, tan, uv, images, c2w, focal, H, W, cull=True, raw=False, near=1e-3):
+    """render_mesh -> (its dict, the [H, W, 12] G-buffer rows of tir_raster_shade the dict's entries are views of)."""
     pos = ops.f32(pos, "pos", 3).view(-1, 3)
     dev = pos.device
     rows, drops = ops.raster_project(pos, c2w, focal, H, W, near=near)
@@ -92,7 +100,7 @@ def render_mesh(pos, nrm, tan, uv, images, c2w, focal, H, W, cull=True, raw=Fals
     out = ops.raster_shade(pix, nrm, tan, uv, _device_images(images, dev), raw)
     depth = zc * torch.linalg.norm(_camera_dirs(focal, H, W, dev), dim=-1) * (face >= 0)
     return {"face": face, "bary": bary, "depth": depth, "albedo": out[..., 0:3], "roughness": out[..., 3], "ao": out[..., 4],
-            "normal": out[..., 5:8], "coverage": out[..., 8], "drops": drops}
+            "normal": out[..., 5:8], "coverage": out[..., 8], "drops": drops}, out
 
 
 def render_glb(path, c2w, focal, H, W, aabb=None, grid=None, device="cuda", **kw):
@@ -116,12 +124,107 @@ def load_glb(path, aabb=None, grid=None, device="cuda"):
     return pos, nrm, tan, uv, dict(zip(IMAGE_NAMES, _device_images(g["images"], device)))
 
 
+def _environment(hdr, device):
+    """An environment map given as an array, a tensor or the path of a Radiance .hdr (or .npy) file -> float32 [H, W, 3] on device."""
+    if isinstance(hdr, (str, bytes)) or hasattr(hdr, "__fspath__"):
+        path = str(hdr)
+        if path.endswith(".npy"):
+            hdr = np.load(path)
+        else:
+            from .hdr import read_hdr
+            hdr = read_hdr(path)
+    t = torch.as_tensor(np.ascontiguousarray(hdr) if isinstance(hdr, np.ndarray) else hdr)
+    if t.dim() != 3 or t.shape[2] != 3:
+        raise ValueError(f"an environment map is [H, W, 3], got {tuple(t.shape)}")
+    return ops.to_device(t.detach(), device, torch.float32).contiguous()
+
+
+def environment_cells(hdr, rows=32, device="cuda"):
+    """The light cells tir_light_gbuffer integrates: the equirectangular map hdr (array, tensor or .hdr path; row 0 at the top, as
+    relight.Environment_Light reads it) reduced by solid-angle weighted means to rows x 2 rows cells (ops.env_cells) -> [2 rows^2,
+    8] on the device.  ValueError when the map's sides are not multiples of the grid's."""
+    rows = int(rows)
+    if torch.is_tensor(hdr) and hdr.is_cuda:
+        device = hdr.device
+    env = _environment(hdr, device)
+    if rows < 1 or env.shape[0] % rows or env.shape[1] % (2 * rows):
+        raise ValueError(f"environment_cells: a {env.shape[0]} x {env.shape[1]} map does not divide into {rows} x {2 * rows} cells")
+    return ops.env_cells(env, rows, 2 * rows)
+
+
+def _tone_map(x):
+    """linear2srgb of models/relight_utils.py:489-515 (what TIR_LIGHT_SRGB applies), for the background pixels."""
+    x = x.clamp(0.0, 1.0)
+    return torch.where(x <= 0.0031308, x * 12.92, 1.055 * torch.pow(x + 1e-6, 1.0 / 2.4) - 0.055)
+
+
+@torch.no_grad()
+def relight_mesh(pos, nrm, tan, uv, images, cells, c2w, focal, H, W, hdr=None, occlusion=True, srgb=True, fresnel=0.04, **render_kw):
+    """render_mesh, then what a glTF viewer does after the texture lookups: every covered pixel's albedo, roughness and normal
+    lit by the light cells (environment_cells) through albedo / pi + GGX_specular, the pixel's ray reversed as the view vector
+    (ops.light_gbuffer: one pass over the G-buffer, no shadows, no indirect light) -> render_mesh's dict plus "rgb" [H, W, 3].
+    occlusion: times the baked ambient occlusion; srgb: tone-mapped; fresnel: the scalar F0.  hdr (the [H, W, 3] map the cells
+    were made from, on the device): empty pixels show the environment behind them (ops.env_lookup, tone-mapped the same way);
+    without it they are zeros."""
+    out, gbuf = _render(pos, nrm, tan, uv, images, c2w, focal, H, W, **render_kw)
+    rays = camera_rays(c2w, focal, H, W, gbuf.device)
+    lit = ops.light_gbuffer(gbuf.view(-1, ops.RASTER_ROW), -rays[:, 3:6], cells, fresnel, occlusion, srgb)
+    rgb = lit[:, 0:3]
+    if hdr is not None:
+        back = ops.env_lookup(_environment(hdr, gbuf.device), rays[:, 3:6].contiguous())
+        rgb = torch.where(lit[:, 3:4] > 0, rgb, _tone_map(back) if srgb else back)
+    out["rgb"] = rgb.reshape(H, W, 3)
+    return out
+
+
+def relight_glb(path, hdr, c2w, focal, H, W, rows=32, aabb=None, grid=None, device="cuda", background=True, **kw):
+    """relight_mesh of a file written by mesh.export_textured under the environment hdr (array, tensor or .hdr path) reduced to
+    rows x 2 rows cells; background=False leaves the empty pixels black.  aabb, grid: as render_glb."""
+    env = _environment(hdr, device)
+    return relight_mesh(*load_glb(path, aabb, grid, device), environment_cells(env, rows), c2w, focal, H, W,
+                        hdr=env if background else None, **kw)
+
+
+def field_gbuffer(ret, n):
+    """The field's maps of one view as G-buffer rows [n, 12]: albedo, roughness, ao = 1, the normalised normal_map, coverage =
+    acc_map > 0.5."""
+    g = torch.zeros((n, ops.RASTER_ROW), dtype=torch.float32, device=ret["acc_map"].device)
+    g[:, 0:3] = ret["albedo_map"].reshape(n, 3)
+    g[:, 3] = ret["roughness_map"].reshape(n)
+    g[:, 4] = 1.0
+    g[:, 5:8] = torch.nn.functional.normalize(ret["normal_map"].reshape(n, 3), dim=-1)
+    g[:, 8] = (ret["acc_map"].reshape(n) > 0.5).to(torch.float32)
+    return g
+
+
+def relit_psnr(gbuf_a, gbuf_b, view, cells, fresnel=0.04, images=None):
+    """Two G-buffers [n, 12] of the same pixels lit by the same cells from the same view vectors (no occlusion, tone-mapped) ->
+    the PSNR in dB over the pixels covered in both (inf when the images agree there, nan when there are none).  images (a list)
+    receives the two [n, 3] images."""
+    lit = [ops.light_gbuffer(g, view, cells, float(fresnel), False, True) for g in (gbuf_a, gbuf_b)]
+    if images is not None:
+        images.extend(x[:, 0:3] for x in lit)
+    both = (lit[0][:, 3] > 0) & (lit[1][:, 3] > 0)
+    if not bool(both.any()):
+        return float("nan")
+    mse = float(((lit[0][both, 0:3] - lit[1][both, 0:3]).double() ** 2).mean())
+    return -10.0 * math.log10(mse) if mse > 0 else float("inf")
+
+
+def _write_view(path, rgb):
+    from . import mesh
+    a = torch.cat([rgb.clamp(0, 1), torch.ones_like(rgb[..., :1])], -1)
+    with open(path, "wb") as fh:
+        fh.write(mesh.write_png((a * 255.0 + 0.5).to(torch.uint8)))
+
+
 def _mean(values):
     return float(np.mean(values)) if len(values) else float("nan")
 
 
 @torch.no_grad()
-def compare_asset(model, path, cameras=None, H=200, W=200, focal=None, n_views=8, grid=None, args=None, chunk=16384):
+def compare_asset(model, path, cameras=None, H=200, W=200, focal=None, n_views=8, grid=None, args=None, chunk=16384, light=None,
+                  light_rows=16, write_views=None):
     """Render the field (Renderer_TensoIR_train under its own first light -- no novel illumination --, no white background,
     `chunk` rays per call) and the asset at `path` (render_glb, mapped to field coordinates with the lattice `grid`, default the
     model's gridSize) from the same cameras.  The renderer decodes albedo, roughness and normals only with is_relight=True, which
@@ -134,6 +237,15 @@ def compare_asset(model, path, cameras=None, H=200, W=200, focal=None, n_views=8
       normal_deg      mean angle between normal_map and the asset's shading normal
       depth_rmse      in units of the model's stepSize
       pixels          how many pixels lie in both
+    light (an environment map: array, tensor, .hdr or .npy path; default None: the report is exactly the one above) adds
+      relit_psnr      dB between the field's and the asset's image under that environment, over the pixels in both silhouettes:
+                      the field's albedo_map, roughness_map, normalised normal_map and acc_map > 0.5 are packed into G-buffer
+                      rows with ao = 1, and BOTH G-buffers go through ops.light_gbuffer with the same light_rows x 2 light_rows
+                      cells, the pixel's reversed ray as view, fresnel = model.fixed_fresnel, no occlusion, tone-mapped.  The
+                      same estimator on both sides: the number isolates what the baked albedo, roughness and normal errors do
+                      to a lit image, free of sampling noise and of shadows (which the file does not carry).  The field's own
+                      shadowed relight is relight.relight_chunk; this check does not replace it.
+    write_views (a directory, with light): every view's two images as view_KK_field.png / view_KK_asset.png.
     cameras: [n, 3, 4]; default orbit_cameras(model.aabb, n_views) at the middle of the model's near / far range, with a focal
     length that fits the box into 90 % of the image."""
     import types
@@ -153,15 +265,20 @@ def compare_asset(model, path, cameras=None, H=200, W=200, focal=None, n_views=8
     grid = [int(g) for g in (model.gridSize if grid is None else grid)]
     step = float(model.stepSize)
     asset = load_glb(path, model.aabb, grid, dev)                      # read and decoded once for all views
+    cells = None if light is None else environment_cells(_environment(light, dev), light_rows)
+    if write_views is not None:
+        if light is None:
+            raise ValueError("write_views writes the lit images: it needs light")
+        os.makedirs(write_views, exist_ok=True)
     views = []
-    for c2w in cameras:
+    for k, c2w in enumerate(cameras):
         rays = camera_rays(c2w, focal, H, W, dev)
         lidx = torch.zeros((rays.shape[0], 1), dtype=torch.int32, device=dev)
         parts = [Renderer_TensoIR_train(rays[a:a + chunk], None, lidx[a:a + chunk], model, N_samples=-1, white_bg=False, is_train=False,
                                         is_relight=True, sample_method="fixed_envirmap", device=dev, args=args, _no_graph=True)
                  for a in range(0, rays.shape[0], int(chunk))]
         ret = {k: torch.cat([p[k].reshape(p["acc_map"].shape[0], -1) for p in parts]) for k in FIELD_MAPS}
-        a = render_mesh(*asset, c2w, focal, H, W)
+        a, gbuf = _render(*asset, c2w, focal, H, W)
         fld = ret["acc_map"].reshape(H, W) > 0.5
         ast = a["coverage"] > 0.5
         both = fld & ast
@@ -179,7 +296,14 @@ def compare_asset(model, path, cameras=None, H=200, W=200, focal=None, n_views=8
             v["depth_rmse"] = float((((ret["depth_map"].reshape(H, W)[both] - a["depth"][both]).double() / step) ** 2).mean().sqrt())
         else:
             v.update({k: float("nan") for k in ("albedo_psnr", "roughness_rmse", "normal_deg", "depth_rmse")})
+        if cells is not None:
+            lit = []
+            v["relit_psnr"] = relit_psnr(field_gbuffer(ret, H * W), gbuf.view(-1, ops.RASTER_ROW), (-rays[:, 3:6]).contiguous(), cells,
+                                         model.fixed_fresnel, lit)
+            if write_views is not None:
+                for name, img in zip(("field", "asset"), lit):
+                    _write_view(os.path.join(write_views, f"view_{k:02d}_{name}.png"), img.reshape(H, W, 3))
         views.append(v)
-    keys = ("iou", "pixels", "albedo_psnr", "roughness_rmse", "normal_deg", "depth_rmse")
+    keys = ("iou", "pixels", "albedo_psnr", "roughness_rmse", "normal_deg", "depth_rmse") + (() if cells is None else ("relit_psnr",))
     mean = {k: _mean([v[k] for v in views if math.isfinite(v[k])]) for k in keys}
     return {"views": views, "mean": mean, "H": int(H), "W": int(W), "focal": float(focal), "n_views": len(views)}

@@ -489,10 +489,21 @@ class Environment_Light:
 
 
 def read_hdr(path):
-    import cv2
-    with open(path, "rb") as h:
-        buf = np.frombuffer(h.read(), np.uint8)
-    return cv2.cvtColor(cv2.imdecode(buf, cv2.IMREAD_UNCHANGED), cv2.COLOR_BGR2RGB)
+    """OpenCV's reader where there is one; tensoir_amd.hdr's where the import fails or the launcher's stand-in (shims.py) raises."""
+    try:
+        import cv2
+    except ImportError:
+        cv2 = None
+    if cv2 is not None:
+        with open(path, "rb") as h:
+            buf = np.frombuffer(h.read(), np.uint8)
+        try:
+            return cv2.cvtColor(cv2.imdecode(buf, cv2.IMREAD_UNCHANGED), cv2.COLOR_BGR2RGB)
+        except RuntimeError:
+            if not getattr(cv2, "__tensoir_shim__", False):
+                raise
+    from . import hdr
+    return hdr.read_hdr(path)
 
 
 @torch.no_grad()
