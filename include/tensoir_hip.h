@@ -1059,6 +1059,54 @@ int tir_env_cells(const float* hdr, int32_t H, int32_t W, const float* row_w, in
 int tir_light_gbuffer(const float* gbuf, const float* view, const float* cells, int64_t M, int32_t D, float fresnel, int32_t flags,
                       float* out, void* stream);
 
+/* ---- Shadows of the exported asset: one orthographic z-buffer per light cell (tensoir_amd/raster.py relight_mesh(shadows=True) /
+ * shadow_maps_for / compare_asset(shadows=True); restated in numpy by tests/shadow_reference.py).
+ * Frames: frames [D][12] fp32 (ops.shadow_frames forms them in float64 on the host and rounds once).  With L = cells[d].dir
+ *   normalised, a = the world axis with the smallest |L_a| (the lowest index on ties), u = normalize(e_a x L), v = L x u, c and r
+ *   the centre and radius of a sphere round the mesh and g = S / (2 r), row d is
+ *     {g u, S/2 - g (u.c),  g v, S/2 - g (v.c),  L / (4 r), 0.5 - (L.c) / (4 r)}
+ *   and a point p has, every product and sum rounded to fp32 on its own, in this order,
+ *     x_px = ((f0 p0 + f1 p1) + f2 p2) + f3,   y_px = ((f4 p0 + f5 p1) + f6 p2) + f7,   w = ((f8 p0 + f9 p1) + f10 p2) + f11.
+ *   w lies in about [0.25, 0.75] inside the sphere; a larger w is nearer to the light, and a positive w's bits order as unsigned
+ *   integers.  One texel is 1 / (2 S) in units of w.
+ * tir_shadow_maps: pos [V][3], faces NULL (corner q reads pos[q], V >= 3 F) or [F][3] int32, as tir_raster_project -> maps
+ *   [D][S][S] uint32, cleared to 0 (= empty) by the entry: every texel holds bits(w) of the surface nearest to cell d's light.
+ *   Per (cell, face) pair: the three corners projected as above and snapped, sx = rint(256 x_px) (half to even).  The pair is
+ *   dropped when, tested in this order: a vertex index lies outside [0, V) (no vertex of such a face is read); an x_px, y_px or w
+ *   is not finite; an |sx| or |sy| exceeds TIR_RASTER_GUARD * 256.  status [4] int64, cleared first, counts the dropped PAIRS
+ *   {index, 0, guard, non-finite} (the slots of tir_raster_project; there is no near plane).  Coverage is tir_raster_cover's
+ *   integer rule with cull = 0 (both orientations cast shadows), texel (i, j) having its centre at (256 i + 128, 256 j + 128).
+ *   Fragment depth, each step rounded on its own:  w = ((E0 w0 + E1 w1) + E2 w2) / |A|  (exact interpolation: the projection is
+ *   affine); a fragment whose w is not > 0 is not written; the others go through one 32-bit unsigned atomic max.  The maps do not
+ *   depend on the order of the faces, on the order fragments arrive in, or on work_cap.
+ *   work: [2 + 2 work_cap] int32 the entry owns during the call: pairs whose box of texel centres holds more than 64 texels are
+ *   listed there (at most work_cap of them) and walked by a workgroup each in a second launch; when the list is full the pair's
+ *   thread walks the box itself.  work_cap = 0 is allowed.
+ * tir_shadow_lookup (diagnostics and tests): pts, nrm [M][3], cells [D][8] (tir_env_cells' records) -> vis [M][D] uint8:
+ *   0: the pair does not contribute, c = n.L <= 1e-6 with c formed as tir_light_gbuffer forms it (sums of products may be fused);
+ *   2: lit;  1: shadowed.  THE VISIBILITY RULE: the point is projected as above; its texel is (floor(x_px), floor(y_px)), nearest,
+ *   no filtering; it is lit when the texel lies outside [0, S)^2 (or a coordinate is NaN), when the texel is 0, or when
+ *     w + bias >= as_float(texel),   bias = (bias_const + bias_slope * min(sqrt(max(1 - c c, 0)) * rcp(c), 8)) * texel_w
+ *   with texel_w = 0.5f / S formed once on the host in fp32, sqrt and rcp the one-ulp hardware instructions, every other step
+ *   rounded on its own.  bias_const and bias_slope are in texels.
+ * tir_light_gbuffer_shadowed: tir_light_gbuffer (above) with pts [M][3], the world position of each row's surface point: the
+ *   same thread layout, arithmetic, order, flags and validation; a pair with c > 1e-6 is added only when the visibility rule
+ *   says lit, tested before the specular term.  With empty maps the result equals tir_light_gbuffer's bit for bit.  No atomics,
+ *   a fixed order per row: two calls give identical bits, and a row's result does not depend on where it stands in the buffer.
+ * All three validate on the host before any device work: a null pointer (pos may be null when F = 0; with M = 0 the lookup and
+ *   the lighting do nothing and take null pointers), D < 1, S < 1, a negative count or work_cap, V < 3 F without faces, a
+ *   negative or non-finite bias, unknown flag bits, frames / cells / gbuf / out not 16-byte, status not 8-byte, maps / work not
+ *   4-byte aligned -> TIR_ERR_ARG; S > TIR_SHADOW_MAX_SIDE, F > TIR_RASTER_MAX_FACES, V > 2^31 - 1, D > 2^20, M > 2^36 ->
+ *   TIR_ERR_UNSUPPORTED.  F = 0 gives empty maps.  They allocate nothing. */
+#define TIR_SHADOW_MAX_SIDE 4096
+int tir_shadow_maps(const float* pos, int64_t n_verts, const int32_t* faces, int64_t n_faces, const float* frames, int32_t D,
+                    int32_t S, uint32_t* maps, int32_t* work, int32_t work_cap, int64_t* status, void* stream);
+int tir_shadow_lookup(const float* pts, const float* nrm, const float* cells, const float* frames, const uint32_t* maps, int64_t M,
+                      int32_t D, int32_t S, float bias_const, float bias_slope, uint8_t* vis, void* stream);
+int tir_light_gbuffer_shadowed(const float* gbuf, const float* view, const float* cells, const float* pts, const float* frames,
+                               const uint32_t* maps, int64_t M, int32_t D, int32_t S, float bias_const, float bias_slope, float fresnel,
+                               int32_t flags, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

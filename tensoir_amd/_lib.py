@@ -179,6 +179,9 @@ SIGNATURES = {
     "tir_raster_shade": (C.c_int, [P, I64, P, P, P, P, P, P, I32, I32, I32, I32, P, P]),
     "tir_env_cells": (C.c_int, [P, I32, I32, P, I32, I32, P, P]),
     "tir_light_gbuffer": (C.c_int, [P, P, P, I64, I32, F32, I32, P, P]),
+    "tir_shadow_maps": (C.c_int, [P, I64, P, I64, P, I32, I32, P, P, I32, P, P]),
+    "tir_shadow_lookup": (C.c_int, [P, P, P, P, P, I64, I32, I32, F32, F32, P, P]),
+    "tir_light_gbuffer_shadowed": (C.c_int, [P, P, P, P, P, P, I64, I32, I32, F32, F32, F32, I32, P, P]),
 }
 
 _lib = None

@@ -7,6 +7,7 @@ occlusion and direct irradiance under one of the model's lights, evaluated at su
     python -m tensoir_amd.bake CKPT OUT.glb --texture-size N [...]     # the same bake at every texel of an atlas (mesh.export_textured)
     python -m tensoir_amd.bake CKPT OUT.glb --texture-size N --check-views V [--check-size S]   # + raster.compare_asset, one JSON line
     ... --check-views V --check-light NAME|FILE.hdr|FILE.npy [--check-light-rows R] [--write-views DIR]   # + relit_psnr
+    ... --check-light ... --check-shadows [--shadow-size S]   # + shadow_agreement: the mesh's shadow maps against the field's visibility (4.10)
     ... --environment OUT.hdr [--environment-size H W]                  # + the recovered light as a Radiance picture
 
 Per point p with unit outward direction n and s = model.stepSize:
@@ -191,6 +192,9 @@ def main(argv=None):
     ap.add_argument("--check-light-rows", type=int, default=16, metavar="R", help="light cells: R x 2R (default 16)")
     ap.add_argument("--write-views", default=None, metavar="DIR", help="with --check-light: write every view's field-lit and "
                     "asset-lit image as PNG into DIR")
+    ap.add_argument("--check-shadows", action="store_true", help="with --check-light: also build the asset's per-cell shadow maps and "
+                    "report shadow_agreement, the share of (pixel, light cell) pairs on which they and the field's transmittance agree")
+    ap.add_argument("--shadow-size", type=int, default=256, metavar="S", help="side of the S x S shadow maps (default 256)")
     ap.add_argument("--environment", default=None, metavar="OUT.hdr", help="also write the model's light --light as a Radiance "
                     "picture (mesh.export_environment)")
     ap.add_argument("--environment-size", type=int, nargs=2, metavar=("H", "W"), default=(256, 512))
@@ -201,6 +205,8 @@ def main(argv=None):
         ap.error("--check-light lights the views of --check-views")
     if a.write_views is not None and a.check_light is None:
         ap.error("--write-views writes the images of --check-light")
+    if a.check_shadows and a.check_light is None:
+        ap.error("--check-shadows shadows the light of --check-light")
     extra = {} if a.envmap is None else {"envmap_h": a.envmap[0], "envmap_w": a.envmap[1]}
     model = load_model(a.ckpt, "cuda", **extra)
     grid = None if a.grid is None else [a.grid] * 3
@@ -229,7 +235,8 @@ def main(argv=None):
         if light in synth.HDR_NAMES:
             light = synth.make_hdr_maps(synth.HDR_NAMES, 64, 128)[light]            # as Environment_Light("synthetic:h=64,w=128")
         print(json.dumps(raster.compare_asset(model, a.out, H=a.check_size, W=a.check_size, n_views=a.check_views, grid=grid, light=light,
-                                              light_rows=a.check_light_rows, write_views=a.write_views)))
+                                              light_rows=a.check_light_rows, write_views=a.write_views,
+                                              **({"shadows": True, "shadow_size": a.shadow_size} if a.check_shadows else {}))))
 
 
 if __name__ == "__main__":

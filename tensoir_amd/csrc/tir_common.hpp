@@ -101,6 +101,42 @@ __device__ __forceinline__ float sub_rn(float a, float b) {
     return a - b;
 }
 
+// ---- shadow maps of the light cells (contract: include/tensoir_hip.h, tir_shadow_*) -- shared by tir_raster.hip
+// (the maps, tir_shadow_lookup) and tir_shade.hip (tir_light_gbuffer_shadowed).
+// A point in the orthographic frame fr [12] of one cell: map coordinates in texels and the depth w (larger = nearer the light),
+// every product and sum rounded on its own, in the order of the contract.
+__device__ __forceinline__ void shadow_project(const float* __restrict__ fr, float p0, float p1, float p2, float& x, float& y, float& w) {
+    x = add_rn(add_rn(add_rn(mul_rn(fr[0], p0), mul_rn(fr[1], p1)), mul_rn(fr[2], p2)), fr[3]);
+    y = add_rn(add_rn(add_rn(mul_rn(fr[4], p0), mul_rn(fr[5], p1)), mul_rn(fr[6], p2)), fr[7]);
+    w = add_rn(add_rn(add_rn(mul_rn(fr[8], p0), mul_rn(fr[9], p1)), mul_rn(fr[10], p2)), fr[11]);
+}
+
+// The cosine of a light cell on a stored normal, in the one form every lighting kernel uses (the products may fuse).
+__device__ __forceinline__ float light_cosine(float n0, float n1, float n2, float lx, float ly, float lz) {
+    return n0 * lx + n1 * ly + n2 * lz;
+}
+
+struct ShadowBias {
+    float constant, slope;                               // in texels
+    float texel;                                         // 1 / (2 S): one texel in units of w, formed once on the host in fp32
+};
+
+// THE visibility rule: is the point p, whose stored normal has the cosine c > 1e-6 on the cell, lit through the cell's map
+// [S][S]?  Nearest texel, no filtering.  Lit when the texel lies outside the map, is empty (0), or is not nearer to the light
+// than the point by more than the bias.  v_sqrt_f32 and v_rcp_f32 are the one-ulp instructions; the comparison is exact.
+__device__ __forceinline__ bool shadow_lit(const float* __restrict__ fr, const uint32_t* __restrict__ map, int S, float p0, float p1,
+                                           float p2, float c, const ShadowBias& b) {
+    float x, y, w;
+    shadow_project(fr, p0, p1, p2, x, y, w);
+    const float fx = floorf(x), fy = floorf(y), side = (float)S;
+    if (!(fx >= 0.f && fx < side && fy >= 0.f && fy < side)) return true;                       // a NaN coordinate included
+    const uint32_t t = map[(size_t)(int)fy * (size_t)S + (size_t)(int)fx];
+    if (t == 0u) return true;
+    const float tn = fminf(mul_rn(__builtin_amdgcn_sqrtf(fmaxf(sub_rn(1.f, mul_rn(c, c)), 0.f)), __builtin_amdgcn_rcpf(c)), 8.f);
+    const float bias = mul_rn(add_rn(b.constant, mul_rn(b.slope, tn)), b.texel);
+    return add_rn(w, bias) >= __uint_as_float(t);
+}
+
 // normalize_coord: (x - aabb0) * invaabbSize - 1   (models/tensorBase_rotated_lights.py:640-641)
 __device__ __forceinline__ float norm_coord(float x, float mn, float inv) {
     return sub_rn(mul_rn(sub_rn(x, mn), inv), 1.0f);

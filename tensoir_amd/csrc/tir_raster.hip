@@ -6,6 +6,8 @@
 //   k_raster_cover_big    one workgroup per listed face walks the face's box, 256 pixels at a time
 //   k_raster_resolve      one thread per pixel: the winning face's perspective-correct barycentrics and camera depth
 //   k_raster_shade        one thread per pixel: interpolated attributes, three bilinear RGBA8 lookups, the tangent-space normal
+//   k_shadow_maps_*       the same coverage and depth once per light cell, orthographic: one 32-bit z-buffer per cell (tir_shadow_maps,
+//                         DESIGN 4.10); k_shadow_lookup reads them back per (point, cell) pair (tir_shadow_lookup)
 // Coverage is int64 arithmetic on the snapped corners and the depth test one 64-bit unsigned atomic max per fragment of a key
 // (depth bits, inverted face index): neither depends on the order fragments arrive in, so every output repeats bit for bit.
 // Every fp32 step of project / cover / resolve is rounded on its own (tir::mul_rn & co.: the numpy restatement's float32 mode
@@ -95,12 +97,8 @@ __device__ __forceinline__ int raster_bias(int n, int dx, int dy) {
     return (dy < 0 || (dy == 0 && dx > 0)) ? 0 : 1;
 }
 
-// -> the doubled area's sign (0: nothing to draw, the face is flagged or has no area)
-__device__ __forceinline__ int raster_load(const int4* __restrict__ rows, int64_t f, RasterFace& T) {
-    const int4 a = rows[3 * f], b = rows[3 * f + 1], c = rows[3 * f + 2];
-    if (a.w | b.w | c.w) return 0;
-    T.x0 = a.x; T.y0 = a.y; T.x1 = b.x; T.y1 = b.y; T.x2 = c.x; T.y2 = c.y;
-    T.w0 = __int_as_float(a.z); T.w1 = __int_as_float(b.z); T.w2 = __int_as_float(c.z);
+// the snapped corners and their depths are in T -> the doubled area's sign (0: no area), orientation, |A| and edge ownership
+__device__ __forceinline__ int raster_setup(RasterFace& T) {
     const int64_t A = (int64_t)(T.x1 - T.x0) * (T.y2 - T.y0) - (int64_t)(T.x2 - T.x0) * (T.y1 - T.y0);
     if (A == 0) return 0;
     T.n = A < 0 ? -1 : 1;
@@ -109,6 +107,15 @@ __device__ __forceinline__ int raster_load(const int4* __restrict__ rows, int64_
     T.bias1 = raster_bias(T.n, T.x0 - T.x2, T.y0 - T.y2);
     T.bias2 = raster_bias(T.n, T.x1 - T.x0, T.y1 - T.y0);
     return T.n;
+}
+
+// -> the doubled area's sign (0: nothing to draw, the face is flagged or has no area)
+__device__ __forceinline__ int raster_load(const int4* __restrict__ rows, int64_t f, RasterFace& T) {
+    const int4 a = rows[3 * f], b = rows[3 * f + 1], c = rows[3 * f + 2];
+    if (a.w | b.w | c.w) return 0;
+    T.x0 = a.x; T.y0 = a.y; T.x1 = b.x; T.y1 = b.y; T.x2 = c.x; T.y2 = c.y;
+    T.w0 = __int_as_float(a.z); T.w1 = __int_as_float(b.z); T.w2 = __int_as_float(c.z);
+    return raster_setup(T);
 }
 
 // the three edge functions at the centre of pixel (i, j), oriented; -> inside (top-left rule)
@@ -186,6 +193,133 @@ k_raster_cover_big(const int4* __restrict__ rows, int W, int H, unsigned long lo
             const int r = p / w;
             raster_fragment(T, i0 + p - r * w, j0 + r, W, low, keys);
         }
+    }
+}
+
+// ---- shadow maps of the light cells: the same integer coverage and the same depth formula, one orthographic map
+// per cell, a 32-bit atomic max of bits(w) per fragment.  Grid (face block, chunk of cells): a thread keeps its face's corners in
+// registers for SHADOW_CELLS cells; the cell is the loop counter, the same in every lane, so its frame arrives by scalar loads.
+constexpr int SHADOW_CELLS = 16;
+
+// the face's nine coordinates -> 0, or TIR_RASTER_DROP_INDEX (then nothing was read of pos)
+__device__ __forceinline__ int shadow_corners(const float* __restrict__ pos, const int32_t* __restrict__ faces, int64_t n_verts, int64_t f,
+                                              float P[9]) {
+    int64_t v0 = 3 * f, v1 = 3 * f + 1, v2 = 3 * f + 2;
+    if (faces) {
+        const int32_t i0 = faces[3 * f], i1 = faces[3 * f + 1], i2 = faces[3 * f + 2];
+        if (i0 < 0 || i1 < 0 || i2 < 0 || i0 >= n_verts || i1 >= n_verts || i2 >= n_verts) return TIR_RASTER_DROP_INDEX;
+        v0 = i0; v1 = i1; v2 = i2;
+    }
+#pragma unroll
+    for (int a = 0; a < 3; ++a) { P[a] = pos[3 * v0 + a]; P[3 + a] = pos[3 * v1 + a]; P[6 + a] = pos[3 * v2 + a]; }
+    return 0;
+}
+
+// the face in one cell's frame -> 0 and T (corners snapped, depths w), or the drop flag of the pair
+__device__ __forceinline__ int shadow_face(const float P[9], const float* __restrict__ fr, RasterFace& T) {
+    float x[3], y[3], w[3];
+    bool finite = true, guard = true;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        tir::shadow_project(fr, P[3 * k], P[3 * k + 1], P[3 * k + 2], x[k], y[k], w[k]);
+        finite = finite && isfinite(x[k]) && isfinite(y[k]) && isfinite(w[k]);
+        x[k] = rintf(mul_rn(x[k], 256.f));
+        y[k] = rintf(mul_rn(y[k], 256.f));
+        guard = guard && fabsf(x[k]) <= (float)RASTER_GUARD && fabsf(y[k]) <= (float)RASTER_GUARD;
+    }
+    if (!finite) return TIR_RASTER_DROP_NONFINITE;
+    if (!guard) return TIR_RASTER_DROP_GUARD;
+    T.x0 = (int)x[0]; T.y0 = (int)y[0]; T.x1 = (int)x[1]; T.y1 = (int)y[1]; T.x2 = (int)x[2]; T.y2 = (int)y[2];
+    T.w0 = w[0]; T.w1 = w[1]; T.w2 = w[2];
+    return 0;
+}
+
+__device__ __forceinline__ void shadow_fragment(const RasterFace& T, int i, int j, int S, unsigned* __restrict__ map) {
+    int64_t e0, e1, e2;
+    if (!raster_edges(T, i, j, e0, e1, e2)) return;
+    float t0, t1, t2, s;
+    raster_terms(T, e0, e1, e2, t0, t1, t2, s);
+    const float w = __fdiv_rn(s, T.area);
+    if (!(w > 0.f)) return;                                        // behind the frame's range (or NaN): bits would not order
+    const unsigned key = __float_as_uint(w);
+    unsigned* p = map + (size_t)j * (size_t)S + (size_t)i;         // 0 <= i, j < S: raster_box clips to the map
+    if (*p < key) atomicMax(p, key);
+}
+
+__global__ void __launch_bounds__(RASTER_THREADS)
+k_shadow_maps_small(const float* __restrict__ pos, const int32_t* __restrict__ faces, int64_t n_verts, int64_t n_faces,
+                    const float* __restrict__ frames, int D, int S, unsigned* __restrict__ maps, int32_t* __restrict__ work, int work_cap,
+                    unsigned long long* __restrict__ status) {
+    const int64_t f = (int64_t)blockIdx.x * RASTER_THREADS + threadIdx.x;
+    if (f >= n_faces) return;
+    float P[9];
+    const int bad = shadow_corners(pos, faces, n_verts, f, P);
+    for (int d0 = (int)blockIdx.y * SHADOW_CELLS; d0 < D; d0 += (int)gridDim.y * SHADOW_CELLS) {
+        const int d1 = min(d0 + SHADOW_CELLS, D);
+        for (int d = d0; d < d1; ++d) {
+            RasterFace T;
+            const int drop = bad ? bad : shadow_face(P, frames + 12 * (size_t)d, T);
+            if (drop) {
+                atomicAdd(status + ((drop & TIR_RASTER_DROP_INDEX) ? 0 : (drop & TIR_RASTER_DROP_NONFINITE) ? 3 : 2), 1ull);
+                continue;
+            }
+            int i0, i1, j0, j1;
+            if (raster_setup(T) == 0 || !raster_box(T, S, S, i0, i1, j0, j1)) continue;
+            if ((int64_t)(i1 - i0 + 1) * (j1 - j0 + 1) > RASTER_SMALL && __atomic_load_n(work, __ATOMIC_RELAXED) < work_cap) {
+                const int slot = atomicAdd(work, 1);               // the count stays below work_cap + the threads in flight
+                if (slot < work_cap) {
+                    work[2 + 2 * (size_t)slot] = d;
+                    work[3 + 2 * (size_t)slot] = (int32_t)f;
+                    continue;
+                }
+            }
+            unsigned* map = maps + (size_t)d * (size_t)S * (size_t)S;
+            for (int j = j0; j <= j1; ++j)
+                for (int i = i0; i <= i1; ++i) shadow_fragment(T, i, j, S, map);
+        }
+    }
+}
+
+__global__ void __launch_bounds__(RASTER_THREADS)
+k_shadow_maps_big(const float* __restrict__ pos, const int32_t* __restrict__ faces, int64_t n_verts, int64_t n_faces,
+                  const float* __restrict__ frames, int D, int S, unsigned* __restrict__ maps, const int32_t* __restrict__ work,
+                  int work_cap) {
+    const int n = min(work[0], work_cap);
+    for (int b = (int)blockIdx.x; b < n; b += (int)gridDim.x) {
+        const int d = work[2 + 2 * (size_t)b];
+        const int64_t f = work[3 + 2 * (size_t)b];
+        if (d < 0 || d >= D || f < 0 || f >= n_faces) continue;                              // (listed pairs pass all of these)
+        float P[9];
+        RasterFace T;
+        int i0, i1, j0, j1;
+        if (shadow_corners(pos, faces, n_verts, f, P) || shadow_face(P, frames + 12 * (size_t)d, T) || raster_setup(T) == 0 ||
+            !raster_box(T, S, S, i0, i1, j0, j1))
+            continue;
+        const int w = i1 - i0 + 1, npx = w * (j1 - j0 + 1);                                    // <= 4096^2
+        unsigned* map = maps + (size_t)d * (size_t)S * (size_t)S;
+        for (int p = (int)threadIdx.x; p < npx; p += RASTER_THREADS) {
+            const int r = p / w;
+            shadow_fragment(T, i0 + p - r * w, j0 + r, S, map);
+        }
+    }
+}
+
+// vis [M][D]: 0 = the pair does not contribute (c <= 1e-6), 1 = shadowed, 2 = lit; one thread per point, the cells in order
+__global__ void __launch_bounds__(RASTER_THREADS)
+k_shadow_lookup(const float* __restrict__ pts, const float* __restrict__ nrm, const float4* __restrict__ cells,
+                const float* __restrict__ frames, const uint32_t* __restrict__ maps, int64_t M, int D, int S, tir::ShadowBias bias,
+                uint8_t* __restrict__ vis) {
+    const int64_t m = (int64_t)blockIdx.x * RASTER_THREADS + threadIdx.x;
+    if (m >= M) return;
+    const float p0 = pts[3 * m], p1 = pts[3 * m + 1], p2 = pts[3 * m + 2];
+    const float n0 = nrm[3 * m], n1 = nrm[3 * m + 1], n2 = nrm[3 * m + 2];
+    for (int d = 0; d < D; ++d) {
+        const float4 ca = cells[2 * (size_t)d];
+        const float c = tir::light_cosine(n0, n1, n2, ca.x, ca.y, ca.z);
+        uint8_t code = 0;
+        if (c > 1e-6f)
+            code = tir::shadow_lit(frames + 12 * (size_t)d, maps + (size_t)d * (size_t)S * (size_t)S, S, p0, p1, p2, c, bias) ? 2 : 1;
+        vis[(size_t)m * (size_t)D + (size_t)d] = code;
     }
 }
 
@@ -378,6 +512,54 @@ extern "C" int tir_raster_shade(const int32_t* pix, int64_t n_faces, const float
                  reinterpret_cast<const uint32_t*>(normal), (int)size, (int)(raw != 0)};
     hipLaunchKernelGGL(k_raster_shade, dim3(raster_blocks((int64_t)W * H, RASTER_THREADS)), dim3(RASTER_THREADS), 0, tir_stream(stream),
                        reinterpret_cast<const int4*>(pix), n_faces, M, (int)W, (int)H, reinterpret_cast<float4*>(out));
+    TIR_CHECK_LAUNCH();
+    return TIR_OK;
+}
+
+namespace {
+int shadow_side(int32_t S) { return S < 1 ? TIR_ERR_ARG : (S > TIR_SHADOW_MAX_SIDE ? TIR_ERR_UNSUPPORTED : TIR_OK); }
+}  // namespace
+
+extern "C" int tir_shadow_maps(const float* pos, int64_t n_verts, const int32_t* faces, int64_t n_faces, const float* frames, int32_t D,
+                               int32_t S, uint32_t* maps, int32_t* work, int32_t work_cap, int64_t* status, void* stream) {
+    if (!frames || !maps || !work || !status || D < 1 || n_verts < 0 || n_faces < 0 || work_cap < 0) return TIR_ERR_ARG;
+    if (n_faces > 0 && !pos) return TIR_ERR_ARG;
+    if (!faces && n_verts < 3 * n_faces) return TIR_ERR_ARG;
+    const int rc = shadow_side(S);
+    if (rc) return rc;
+    if (n_faces > TIR_RASTER_MAX_FACES || n_verts > INT32_MAX || D > (1 << 20)) return TIR_ERR_UNSUPPORTED;
+    if (((uintptr_t)frames & 15) || ((uintptr_t)maps & 3) || ((uintptr_t)work & 3) || ((uintptr_t)status & 7)) return TIR_ERR_ARG;
+    hipStream_t st = tir_stream(stream);
+    hipError_t e = hipMemsetAsync(maps, 0, sizeof(uint32_t) * (size_t)D * (size_t)S * (size_t)S, st);
+    if (e == hipSuccess) e = hipMemsetAsync(work, 0, 2 * sizeof(int32_t), st);
+    if (e == hipSuccess) e = hipMemsetAsync(status, 0, 4 * sizeof(int64_t), st);
+    if (e != hipSuccess) return -(int)e;
+    if (n_faces == 0) return TIR_OK;
+    const unsigned chunks = (unsigned)((D + SHADOW_CELLS - 1) / SHADOW_CELLS);
+    hipLaunchKernelGGL(k_shadow_maps_small, dim3(raster_blocks(n_faces, RASTER_THREADS), chunks < 65535u ? chunks : 65535u),
+                       dim3(RASTER_THREADS), 0, st, pos, faces, n_verts, n_faces, frames, (int)D, (int)S, maps, work, (int)work_cap,
+                       reinterpret_cast<unsigned long long*>(status));
+    TIR_CHECK_LAUNCH();
+    if (work_cap > 0) {
+        hipLaunchKernelGGL(k_shadow_maps_big, dim3((unsigned)(work_cap < RASTER_BIG_BLOCKS ? work_cap : RASTER_BIG_BLOCKS)),
+                           dim3(RASTER_THREADS), 0, st, pos, faces, n_verts, n_faces, frames, (int)D, (int)S, maps, work, (int)work_cap);
+        TIR_CHECK_LAUNCH();
+    }
+    return TIR_OK;
+}
+
+extern "C" int tir_shadow_lookup(const float* pts, const float* nrm, const float* cells, const float* frames, const uint32_t* maps,
+                                 int64_t M, int32_t D, int32_t S, float bias_const, float bias_slope, uint8_t* vis, void* stream) {
+    if (M < 0 || D < 1 || !(bias_const >= 0.f && bias_const < INFINITY) || !(bias_slope >= 0.f && bias_slope < INFINITY)) return TIR_ERR_ARG;
+    const int rc = shadow_side(S);
+    if (rc) return rc;
+    if (D > (1 << 20) || M > ((int64_t)1 << 36)) return TIR_ERR_UNSUPPORTED;
+    if (M == 0) return TIR_OK;
+    if (!pts || !nrm || !cells || !frames || !maps || !vis) return TIR_ERR_ARG;
+    if (((uintptr_t)cells & 15) || ((uintptr_t)frames & 15) || ((uintptr_t)maps & 3)) return TIR_ERR_ARG;
+    const tir::ShadowBias bias{bias_const, bias_slope, 0.5f / (float)S};
+    hipLaunchKernelGGL(k_shadow_lookup, dim3(raster_blocks(M, RASTER_THREADS)), dim3(RASTER_THREADS), 0, tir_stream(stream), pts, nrm,
+                       reinterpret_cast<const float4*>(cells), frames, maps, M, (int)D, (int)S, bias, vis);
     TIR_CHECK_LAUNCH();
     return TIR_OK;
 }

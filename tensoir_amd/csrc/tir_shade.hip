@@ -645,9 +645,19 @@ k_env_cells(const float* __restrict__ hdr, int H, int W, const float* __restrict
 // with scalar loads into SGPRs, which the VALU reads as operands (no LDS tile, no per-lane addresses).  Pairs below the horizon
 // are skipped by a per-lane branch.  rsq, exp2 and rcp are the hardware's one-ulp instructions.  No atomics, a fixed order per
 // pixel: two calls give identical bits, whatever the order of the pixels.
-__global__ void __launch_bounds__(256)
-k_light_gbuffer(const float4* __restrict__ gbuf, const float* __restrict__ view, const float4* __restrict__ cells, int64_t M, int D,
-                float fresnel, int flags, float4* __restrict__ out) {
+// SHADOW: a contributing pair is added only when tir::shadow_lit says so, tested before the specular term; without
+// it the instantiation is the unshadowed kernel, instruction for instruction.
+struct LightShadow {
+    const float* pts;                                    // [M][3]
+    const float* frames;                                 // [D][12]
+    const uint32_t* maps;                                // [D][S][S]
+    int S;
+    tir::ShadowBias bias;
+};
+
+template <bool SHADOW>
+__device__ __forceinline__ void light_rows(const float4* __restrict__ gbuf, const float* __restrict__ view, const float4* __restrict__ cells,
+                                           int64_t M, int D, float fresnel, int flags, float4* __restrict__ out, const LightShadow& sh) {
     const int64_t m = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (m >= M) return;
     const float4 g0 = gbuf[3 * m], g1 = gbuf[3 * m + 1], g2 = gbuf[3 * m + 2];      // TIR_RASTER_ROW = 12 floats
@@ -661,11 +671,18 @@ k_light_gbuffer(const float4* __restrict__ gbuf, const float* __restrict__ view,
     const float nom1 = s.NoV * omk + k;
     const float four_pi = 4.0f * 3.14159265358979323846f;
     float acc[3] = {0.f, 0.f, 0.f};
+    float pt[3] = {0.f, 0.f, 0.f};
+    if constexpr (SHADOW) { pt[0] = sh.pts[3 * m]; pt[1] = sh.pts[3 * m + 1]; pt[2] = sh.pts[3 * m + 2]; }
     for (int d = 0; d < D; ++d) {
         const float4 ca = cells[2 * (size_t)d], cb = cells[2 * (size_t)d + 1];
         const float lx = ca.x, ly = ca.y, lz = ca.z;
-        const float c = ns[0] * lx + ns[1] * ly + ns[2] * lz;
+        const float c = ns[0] * lx + ns[1] * ly + ns[2] * lz;                        // tir::light_cosine's expression
         if (c > 1e-6f) {
+            if constexpr (SHADOW) {
+                if (!tir::shadow_lit(sh.frames + 12 * (size_t)d, sh.maps + (size_t)d * (size_t)sh.S * (size_t)sh.S, sh.S, pt[0], pt[1],
+                                     pt[2], c, sh.bias))
+                    continue;
+            }
             float hx = (lx + s.V[0]) * 0.5f, hy = (ly + s.V[1]) * 0.5f, hz = (lz + s.V[2]) * 0.5f;
             const float inv = __builtin_amdgcn_rsqf(fmaxf(hx * hx + hy * hy + hz * hz, 1e-24f));    // x / max(|x|, 1e-12)
             hx *= inv; hy *= inv; hz *= inv;
@@ -689,6 +706,18 @@ k_light_gbuffer(const float4* __restrict__ gbuf, const float* __restrict__ view,
         if (flags & TIR_LIGHT_SRGB) acc[q] = linear2srgb(acc[q]);
     }
     out[m] = make_float4(acc[0], acc[1], acc[2], cov);
+}
+
+__global__ void __launch_bounds__(256)
+k_light_gbuffer(const float4* __restrict__ gbuf, const float* __restrict__ view, const float4* __restrict__ cells, int64_t M, int D,
+                float fresnel, int flags, float4* __restrict__ out) {
+    light_rows<false>(gbuf, view, cells, M, D, fresnel, flags, out, LightShadow{});
+}
+
+__global__ void __launch_bounds__(256)
+k_light_gbuffer_shadowed(const float4* __restrict__ gbuf, const float* __restrict__ view, const float4* __restrict__ cells, int64_t M,
+                         int D, float fresnel, int flags, float4* __restrict__ out, LightShadow sh) {
+    light_rows<true>(gbuf, view, cells, M, D, fresnel, flags, out, sh);
 }
 
 }  // namespace
@@ -717,6 +746,26 @@ extern "C" int tir_light_gbuffer(const float* gbuf, const float* view, const flo
     hipLaunchKernelGGL(k_light_gbuffer, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, tir_stream(stream),
                        reinterpret_cast<const float4*>(gbuf), view, reinterpret_cast<const float4*>(cells), M, (int)D, fresnel,
                        (int)flags, reinterpret_cast<float4*>(out));
+    TIR_CHECK_LAUNCH();
+    return TIR_OK;
+}
+
+extern "C" int tir_light_gbuffer_shadowed(const float* gbuf, const float* view, const float* cells, const float* pts, const float* frames,
+                                          const uint32_t* maps, int64_t M, int32_t D, int32_t S, float bias_const, float bias_slope,
+                                          float fresnel, int32_t flags, float* out, void* stream) {
+    if (M < 0 || D < 1 || S < 1 || (flags & ~(TIR_LIGHT_OCCLUSION | TIR_LIGHT_SRGB))) return TIR_ERR_ARG;
+    if (!(bias_const >= 0.f && bias_const < INFINITY) || !(bias_slope >= 0.f && bias_slope < INFINITY)) return TIR_ERR_ARG;
+    if (D > (1 << 20) || M > ((int64_t)1 << 36) || S > TIR_SHADOW_MAX_SIDE) return TIR_ERR_UNSUPPORTED;
+    if (M == 0) return TIR_OK;
+    if (!gbuf || !view || !cells || !out || !pts || !frames || !maps) return TIR_ERR_ARG;
+    if (reinterpret_cast<uintptr_t>(gbuf) % 16 != 0 || reinterpret_cast<uintptr_t>(cells) % 16 != 0 ||
+        reinterpret_cast<uintptr_t>(out) % 16 != 0 || reinterpret_cast<uintptr_t>(frames) % 16 != 0 ||
+        reinterpret_cast<uintptr_t>(maps) % 4 != 0)
+        return TIR_ERR_ARG;
+    const LightShadow sh{pts, frames, maps, (int)S, tir::ShadowBias{bias_const, bias_slope, 0.5f / (float)S}};
+    hipLaunchKernelGGL(k_light_gbuffer_shadowed, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, tir_stream(stream),
+                       reinterpret_cast<const float4*>(gbuf), view, reinterpret_cast<const float4*>(cells), M, (int)D, fresnel,
+                       (int)flags, reinterpret_cast<float4*>(out), sh);
     TIR_CHECK_LAUNCH();
     return TIR_OK;
 }

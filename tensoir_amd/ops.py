@@ -9,6 +9,7 @@ import ctypes as C
 import math
 import os
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -1888,4 +1889,110 @@ def light_gbuffer(gbuf, view, cells, fresnel=0.04, occlusion=True, srgb=False):
     flags = (LIGHT_OCCLUSION if occlusion else 0) | (LIGHT_SRGB if srgb else 0)
     _call("tir_light_gbuffer", _ptr(gbuf), _ptr(view), _ptr(cells), gbuf.numel() // RASTER_ROW, cells.shape[0], float(fresnel), flags,
           _ptr(out), _stream())
+    return out
+
+
+# ---- shadows of the exported asset: one orthographic z-buffer per light cell (tensoir_amd/raster.py) --------------
+SHADOW_MAX_SIDE = 4096
+SHADOW_WORK_CAP = 1 << 16      # listed (cell, face) pairs of shadow_maps' workgroup pass; any value gives the same maps
+
+
+def shadow_frames_f64(dirs, centre, radius, S):
+    """shadow_frames' host arithmetic: dirs [D, 3] (any length), centre [3], radius, S -> float64 numpy [D, 12]."""
+    L = np.asarray(dirs, np.float64).reshape(-1, 3)
+    c = np.asarray(centre, np.float64).reshape(3)
+    r, S = float(radius), int(S)
+    if L.shape[0] < 1 or not r > 0 or not np.isfinite(r) or S < 1:
+        raise ValueError("shadow_frames: at least one cell, a positive finite radius and S >= 1")
+    n = np.linalg.norm(L, axis=1, keepdims=True)
+    if not (np.isfinite(n).all() and (n > 0).all()):
+        raise ValueError("shadow_frames: every cell needs a finite direction of non-zero length")
+    L = L / n
+    u = np.cross(np.eye(3)[np.argmin(np.abs(L), axis=1)], L)         # argmin takes the first of equal values
+    u /= np.linalg.norm(u, axis=1, keepdims=True)
+    v = np.cross(L, u)
+    g = S / (2.0 * r)
+    return np.concatenate([g * u, (S / 2.0 - g * (u @ c))[:, None], g * v, (S / 2.0 - g * (v @ c))[:, None],
+                           L / (4.0 * r), (0.5 - (L @ c) / (4.0 * r))[:, None]], 1)
+
+
+def shadow_frames(cells, centre, radius, S):
+    """The orthographic frame of every light cell round the sphere (centre, radius) for S x S maps -> frames [D, 12] f32 on cells'
+    device, formed in float64 on the host (shadow_frames_f64) and rounded once.  With L = cells[d, 0:3] normalised, a the axis with
+    the smallest |L_a| (lowest index on ties), u = normalize(e_a x L), v = L x u, g = S / (2 r): row d is {g u, S/2 - g u.c, g v,
+    S/2 - g v.c, L / (4 r), 0.5 - L.c / (4 r)} (include/tensoir_hip.h).  One read-back of the D directions."""
+    cells = f32(cells, "cells", 8).view(-1, 8)
+    fr = shadow_frames_f64(cells[:, 0:3].detach().to("cpu", torch.float64).numpy(), centre, radius, S)
+    return to_device(torch.from_numpy(fr.astype(np.float32)), cells.device).contiguous()
+
+
+def _shadow_inputs(frames, maps=None):
+    frames = f32(frames, "frames", 12).view(-1, 12)
+    if frames.shape[0] < 1:
+        raise ValueError("frames: at least one light cell")
+    if maps is None:
+        return frames
+    maps = _req(maps, torch.int32, "maps")
+    if maps.dim() != 3 or maps.shape[0] != frames.shape[0] or maps.shape[1] != maps.shape[2] or maps.shape[1] < 1:
+        raise ValueError("maps: expected [D, S, S] int32 (shadow_maps), one map per row of frames")
+    return frames, maps
+
+
+def shadow_maps(pos, frames, S, faces=None, work_cap=SHADOW_WORK_CAP):
+    """tir_shadow_maps: pos [3F, 3] (unwelded; or verts [V, 3] with faces [F, 3] int32) f32 and frames [D, 12] (shadow_frames) on
+    the device -> (maps [D, S, S] int32 holding the uint32 bits(w) of the surface nearest to each cell's light, 0 where the texel
+    is empty; drops = {"index", "near", "guard", "nonfinite": dropped (cell, face) PAIRS}, near always 0).  work_cap: how many
+    pairs with large boxes the workgroup pass may take; the maps do not depend on it.  One 32-byte read-back (the counts)."""
+    pos = f32(pos, "pos", 3).view(-1, 3)
+    frames = _shadow_inputs(frames)
+    dev, V, D, S, work_cap = pos.device, pos.shape[0], frames.shape[0], int(S), int(work_cap)
+    if faces is not None:
+        faces = i32(faces, "faces").view(-1, 3)
+        if faces.device != dev:
+            raise ValueError("faces lives on pos' device")
+        F = faces.shape[0]
+    else:
+        if V % 3:
+            raise ValueError("an unwelded mesh takes three rows of pos per face")
+        F = V // 3
+    if frames.device != dev or work_cap < 0:
+        raise ValueError("shadow_maps: frames lives on pos' device, and work_cap >= 0")
+    ok = 0 < S <= SHADOW_MAX_SIDE
+    maps = torch.empty((D, S, S) if ok else (1, 1, 1), dtype=torch.int32, device=dev)          # the library words the refusal
+    work = torch.empty((2 + 2 * work_cap,), dtype=torch.int32, device=dev)
+    status = torch.zeros((4,), dtype=torch.int64, device=dev)
+    data = lambda t: _ptr(t if F else None)
+    _call("tir_shadow_maps", data(pos), V, data(faces), F, _ptr(frames), D, S, _ptr(maps), _ptr(work), work_cap, _ptr(status), _stream())
+    return maps, dict(zip(RASTER_DROPS, (int(x) for x in status.tolist())))
+
+
+def shadow_lookup(pts, nrm, cells, frames, maps, bias=(0.0, 0.0)):
+    """tir_shadow_lookup: pts, nrm [M, 3], cells [D, 8], frames [D, 12], maps [D, S, S] -> vis [M, D] uint8: 0 = the pair does not
+    contribute (n.L <= 1e-6), 1 = shadowed, 2 = lit, by the visibility rule tir_light_gbuffer_shadowed applies (nearest texel;
+    bias = (const, slope) in texels)."""
+    pts, nrm, cells = f32(pts, "pts", 3).view(-1, 3), f32(nrm, "nrm", 3).view(-1, 3), f32(cells, "cells", 8).view(-1, 8)
+    frames, maps = _shadow_inputs(frames, maps)
+    if pts.shape != nrm.shape or cells.shape[0] != frames.shape[0]:
+        raise ValueError("shadow_lookup: one normal per point and one frame per cell")
+    vis = torch.empty((pts.shape[0], cells.shape[0]), dtype=torch.uint8, device=pts.device)
+    _call("tir_shadow_lookup", _ptr(pts), _ptr(nrm), _ptr(cells), _ptr(frames), _ptr(maps), pts.shape[0], cells.shape[0], maps.shape[1],
+          float(bias[0]), float(bias[1]), _ptr(vis), _stream())
+    return vis
+
+
+def light_gbuffer_shadowed(gbuf, view, cells, pts, frames, maps, bias, fresnel=0.04, occlusion=True, srgb=False):
+    """tir_light_gbuffer_shadowed: light_gbuffer with pts [..., 3] (each row's surface point in the frames' coordinates): a cell
+    lights a row only where shadow_lookup's rule says lit.  -> [..., 4] = {r, g, b, coverage}."""
+    gbuf, view, cells = f32(gbuf, "gbuf", RASTER_ROW), f32(view, "view", 3), f32(cells, "cells", 8).view(-1, 8)
+    pts = f32(pts, "pts", 3)
+    frames, maps = _shadow_inputs(frames, maps)
+    if gbuf.shape[:-1] != view.shape[:-1] or gbuf.shape[:-1] != pts.shape[:-1]:
+        raise ValueError("light_gbuffer_shadowed: gbuf, view and pts take one row per pixel")
+    if cells.shape[0] != frames.shape[0]:
+        raise ValueError("light_gbuffer_shadowed: one frame per light cell")
+    out = torch.empty(gbuf.shape[:-1] + (4,), dtype=torch.float32, device=gbuf.device)
+    flags = (LIGHT_OCCLUSION if occlusion else 0) | (LIGHT_SRGB if srgb else 0)
+    _call("tir_light_gbuffer_shadowed", _ptr(gbuf), _ptr(view), _ptr(cells), _ptr(pts), _ptr(frames), _ptr(maps),
+          gbuf.numel() // RASTER_ROW, cells.shape[0], maps.shape[1], float(bias[0]), float(bias[1]), float(fresnel), flags, _ptr(out),
+          _stream())
     return out

@@ -6,6 +6,8 @@ include/tensoir_hip.h, tir_raster_*), and the comparison of a textured GLB with 
     report = compare_asset(model, "scene.glb", n_views=8)                  # silhouette, albedo, roughness, normals, depth
     out = relight_glb("scene.glb", "city.hdr", c2w, focal, H, W)          # + "rgb": the asset under an environment
     report = compare_asset(model, "scene.glb", light="city.hdr")          # + relit_psnr: the same light on field and asset
+    out = relight_glb("scene.glb", "city.hdr", c2w, focal, H, W, shadows=True)   # the mesh shadows itself: a shadow map per cell (4.10)
+    report = compare_asset(model, "scene.glb", light="city.hdr", shadows=True)   # + shadow_agreement: the maps against the field's visibility
 
 Camera: the datasets' convention.  Pixel (i, j) has its centre at (i + 0.5, j + 0.5) and the camera-space direction
 ((i + 0.5 - W/2) / f, (j + 0.5 - H/2) / f, 1); c2w [3, 4] has the columns x right, y down, z forward and the eye.  All per-corner
@@ -158,17 +160,59 @@ def _tone_map(x):
     return torch.where(x <= 0.0031308, x * 12.92, 1.055 * torch.pow(x + 1e-6, 1.0 / 2.4) - 0.055)
 
 
+SHADOW_BIAS = (0.5, 1.0)         # (constant, slope) in texels: the smallest candidate that passes both criteria of DESIGN 4.10
+SHADOW_MAX_BYTES = 4 << 30
+
+
+def mesh_bounds(pos):
+    """The sphere the shadow frames are laid round: -> (centre (x, y, z), radius) as host floats; the centre is the middle of the
+    positions' box, the radius half its diagonal times 1 + 1/64 (no silhouette touches a map's edge).  One aminmax on the device."""
+    pos = ops.f32(pos, "pos", 3).view(-1, 3)
+    if pos.shape[0] < 1:
+        raise ValueError("mesh_bounds: no positions")
+    lo, hi = torch.aminmax(pos, dim=0)
+    box = torch.stack([lo, hi]).to("cpu", torch.float64).numpy()
+    return tuple(float(x) for x in 0.5 * (box[0] + box[1])), 0.5 * float(np.linalg.norm(box[1] - box[0])) * (1.0 + 1.0 / 64.0)
+
+
+def shadow_maps_for(pos, cells, S=256):
+    """The shadow maps of the mesh pos [3F, 3] under the light cells [D, 8] (environment_cells): one S x S orthographic z-buffer per
+    cell round mesh_bounds(pos) -> (frames [D, 12], maps [D, S, S]), what relight_mesh(shadows=True, shadow_maps=...) and
+    ops.shadow_lookup take.  They depend on the mesh and the cells only: build them once for all views.  ValueError when the maps
+    would exceed 4 GiB."""
+    D, S = int(cells.shape[0]), int(S)
+    if D * S * S * 4 > SHADOW_MAX_BYTES:
+        raise ValueError(f"shadow maps of {D} cells at shadow_size {S} take {D * S * S * 4 / 2 ** 30:.1f} GiB (limit 4): lower "
+                         f"shadow_size, or rows (the light cells are rows x 2 rows)")
+    centre, radius = mesh_bounds(pos)
+    if not radius > 0:
+        raise ValueError("shadow_maps_for: the mesh has no extent")
+    frames = ops.shadow_frames(cells, centre, radius, S)
+    return frames, ops.shadow_maps(pos, frames, S)[0]
+
+
 @torch.no_grad()
-def relight_mesh(pos, nrm, tan, uv, images, cells, c2w, focal, H, W, hdr=None, occlusion=True, srgb=True, fresnel=0.04, **render_kw):
+def relight_mesh(pos, nrm, tan, uv, images, cells, c2w, focal, H, W, hdr=None, occlusion=True, srgb=True, fresnel=0.04, shadows=False,
+                 shadow_size=256, shadow_bias=SHADOW_BIAS, shadow_maps=None, **render_kw):
     """render_mesh, then what a glTF viewer does after the texture lookups: every covered pixel's albedo, roughness and normal
     lit by the light cells (environment_cells) through albedo / pi + GGX_specular, the pixel's ray reversed as the view vector
-    (ops.light_gbuffer: one pass over the G-buffer, no shadows, no indirect light) -> render_mesh's dict plus "rgb" [H, W, 3].
+    (ops.light_gbuffer: one pass over the G-buffer, no indirect light) -> render_mesh's dict plus "rgb" [H, W, 3].
     occlusion: times the baked ambient occlusion; srgb: tone-mapped; fresnel: the scalar F0.  hdr (the [H, W, 3] map the cells
     were made from, on the device): empty pixels show the environment behind them (ops.env_lookup, tone-mapped the same way);
-    without it they are zeros."""
+    without it they are zeros.
+    shadows (default False: no shadows, every number as before): a cell lights a pixel only where the mesh does not stand between
+    them, by one shadow_size x shadow_size shadow map per cell (hard shadows, nearest texel, shadow_bias = (constant,
+    slope) in texels).  The pixel's surface point is the ray's origin + depth x its unit direction.  shadow_maps: the (frames,
+    maps) of shadow_maps_for(pos, cells, shadow_size), for a caller who renders many views; by default they are built here."""
     out, gbuf = _render(pos, nrm, tan, uv, images, c2w, focal, H, W, **render_kw)
     rays = camera_rays(c2w, focal, H, W, gbuf.device)
-    lit = ops.light_gbuffer(gbuf.view(-1, ops.RASTER_ROW), -rays[:, 3:6], cells, fresnel, occlusion, srgb)
+    if shadows:
+        frames, maps = shadow_maps_for(pos, cells, shadow_size) if shadow_maps is None else shadow_maps
+        pts = rays[:, 0:3] + out["depth"].reshape(-1, 1) * rays[:, 3:6]
+        lit = ops.light_gbuffer_shadowed(gbuf.view(-1, ops.RASTER_ROW), -rays[:, 3:6], cells, pts, frames, maps, shadow_bias, fresnel,
+                                         occlusion, srgb)
+    else:
+        lit = ops.light_gbuffer(gbuf.view(-1, ops.RASTER_ROW), -rays[:, 3:6], cells, fresnel, occlusion, srgb)
     rgb = lit[:, 0:3]
     if hdr is not None:
         back = ops.env_lookup(_environment(hdr, gbuf.device), rays[:, 3:6].contiguous())
@@ -179,7 +223,8 @@ def relight_mesh(pos, nrm, tan, uv, images, cells, c2w, focal, H, W, hdr=None, o
 
 def relight_glb(path, hdr, c2w, focal, H, W, rows=32, aabb=None, grid=None, device="cuda", background=True, **kw):
     """relight_mesh of a file written by mesh.export_textured under the environment hdr (array, tensor or .hdr path) reduced to
-    rows x 2 rows cells; background=False leaves the empty pixels black.  aabb, grid: as render_glb."""
+    rows x 2 rows cells; background=False leaves the empty pixels black.  aabb, grid: as render_glb.  shadows, shadow_size,
+    shadow_bias (and everything else of relight_mesh) pass through."""
     env = _environment(hdr, device)
     return relight_mesh(*load_glb(path, aabb, grid, device), environment_cells(env, rows), c2w, focal, H, W,
                         hdr=env if background else None, **kw)
@@ -211,6 +256,24 @@ def relit_psnr(gbuf_a, gbuf_b, view, cells, fresnel=0.04, images=None):
     return -10.0 * math.log10(mse) if mse > 0 else float("inf")
 
 
+def _shadow_agreement(model, relight, args, rays, field_depth, asset, both, cells, smaps, max_pixels):
+    """compare_asset's shadow_agreement of one view: rays [n, 6], field_depth [n], the asset's render dict, both [n] bool."""
+    idx = torch.nonzero(both).reshape(-1)
+    if idx.numel() == 0:
+        return float("nan")
+    idx = idx[::max(1, -(-idx.numel() // max(max_pixels, 1)))]                  # a fixed stride: no random numbers
+    o, d = rays[idx, 0:3], rays[idx, 3:6]
+    D = cells.shape[0]
+    codes = ops.shadow_lookup(o + asset["depth"].reshape(-1, 1)[idx] * d, asset["normal"].reshape(-1, 3)[idx], cells, *smaps, SHADOW_BIAS)
+    pts = (o + field_depth.reshape(-1, 1)[idx] * d).repeat_interleave(D, dim=0)
+    L = torch.nn.functional.normalize(cells[:, 0:3], dim=-1).repeat(idx.numel(), 1)
+    vis = relight.compute_transmittance(model, pts, L, nSample=args.second_nSample, vis_near=args.second_near, vis_far=args.second_far)[0]
+    field_lit = vis.reshape(idx.numel(), D) > 0.5
+    on = codes != 0
+    n = int(on.sum())
+    return float(((codes == 2) == field_lit)[on].sum()) / n if n else float("nan")
+
+
 def _write_view(path, rgb):
     from . import mesh
     a = torch.cat([rgb.clamp(0, 1), torch.ones_like(rgb[..., :1])], -1)
@@ -224,7 +287,7 @@ def _mean(values):
 
 @torch.no_grad()
 def compare_asset(model, path, cameras=None, H=200, W=200, focal=None, n_views=8, grid=None, args=None, chunk=16384, light=None,
-                  light_rows=16, write_views=None):
+                  light_rows=16, write_views=None, shadows=False, shadow_size=256, shadow_pixels=4096):
     """Render the field (Renderer_TensoIR_train under its own first light -- no novel illumination --, no white background,
     `chunk` rays per call) and the asset at `path` (render_glb, mapped to field coordinates with the lattice `grid`, default the
     model's gridSize) from the same cameras.  The renderer decodes albedo, roughness and normals only with is_relight=True, which
@@ -245,7 +308,16 @@ def compare_asset(model, path, cameras=None, H=200, W=200, focal=None, n_views=8
                       same estimator on both sides: the number isolates what the baked albedo, roughness and normal errors do
                       to a lit image, free of sampling noise and of shadows (which the file does not carry).  The field's own
                       shadowed relight is relight.relight_chunk; this check does not replace it.
-    write_views (a directory, with light): every view's two images as view_KK_field.png / view_KK_asset.png.
+    shadows (with light; default False: the report is exactly the one above) adds
+      shadow_agreement  the share of (pixel, light cell) pairs on which the asset's shadow maps (shadow_maps_for at shadow_size,
+                      SHADOW_BIAS) and the field's own visibility agree.  Up to shadow_pixels pixels of those in both silhouettes,
+                      taken by a fixed stride.  Asset side: ops.shadow_lookup at the asset's surface points and shading normals.
+                      Field side: relight.compute_transmittance(model, ray origin + depth_map x direction, L, args' second_nSample,
+                      second_near, second_far) > 0.5 means lit.  Counted over the pairs that contribute on the asset side (n.L >
+                      1e-6); nan when there are none.  Every other number is what it is without shadows: relit_psnr stays the
+                      unshadowed comparison.
+    write_views (a directory, with light): every view's two images as view_KK_field.png / view_KK_asset.png, and with shadows
+    the asset under its own shadows as view_KK_asset_shadowed.png.
     cameras: [n, 3, 4]; default orbit_cameras(model.aabb, n_views) at the middle of the model's near / far range, with a focal
     length that fits the box into 90 % of the image."""
     import types
@@ -270,6 +342,12 @@ def compare_asset(model, path, cameras=None, H=200, W=200, focal=None, n_views=8
         if light is None:
             raise ValueError("write_views writes the lit images: it needs light")
         os.makedirs(write_views, exist_ok=True)
+    smaps = None
+    if shadows:
+        if cells is None:
+            raise ValueError("shadows compares the shadows of a light: it needs light")
+        from . import relight
+        smaps = shadow_maps_for(asset[0], cells, shadow_size)
     views = []
     for k, c2w in enumerate(cameras):
         rays = camera_rays(c2w, focal, H, W, dev)
@@ -303,7 +381,16 @@ def compare_asset(model, path, cameras=None, H=200, W=200, focal=None, n_views=8
             if write_views is not None:
                 for name, img in zip(("field", "asset"), lit):
                     _write_view(os.path.join(write_views, f"view_{k:02d}_{name}.png"), img.reshape(H, W, 3))
+        if smaps is not None:
+            v["shadow_agreement"] = _shadow_agreement(model, relight, args, rays, ret["depth_map"].reshape(-1), a, both.reshape(-1), cells,
+                                                      smaps, int(shadow_pixels))
+            if write_views is not None:
+                pts = rays[:, 0:3] + a["depth"].reshape(-1, 1) * rays[:, 3:6]
+                img = ops.light_gbuffer_shadowed(gbuf.view(-1, ops.RASTER_ROW), (-rays[:, 3:6]).contiguous(), cells, pts, *smaps, SHADOW_BIAS,
+                                                 float(model.fixed_fresnel), False, True)
+                _write_view(os.path.join(write_views, f"view_{k:02d}_asset_shadowed.png"), img[:, 0:3].reshape(H, W, 3))
         views.append(v)
-    keys = ("iou", "pixels", "albedo_psnr", "roughness_rmse", "normal_deg", "depth_rmse") + (() if cells is None else ("relit_psnr",))
+    keys = ("iou", "pixels", "albedo_psnr", "roughness_rmse", "normal_deg", "depth_rmse") + (() if cells is None else ("relit_psnr",)) + \
+           (() if smaps is None else ("shadow_agreement",))
     mean = {k: _mean([v[k] for v in views if math.isfinite(v[k])]) for k in keys}
     return {"views": views, "mean": mean, "H": int(H), "W": int(W), "focal": float(focal), "n_views": len(views)}
