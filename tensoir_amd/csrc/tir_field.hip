@@ -583,7 +583,13 @@ __device__ __forceinline__ void app_split4(const float (&v)[4], _Float16* __rest
     *reinterpret_cast<uint2*>(xl) = make_uint2(lo[0], lo[1]);
 }
 
-template <int C4, bool RAD, bool INTR, bool JIT, bool HX = false>
+// ONE (RAD && INTR on a field with exactly one light): light_mean = (0 + light_line[0]) / 1 IS light_line[0], so val * lr and
+// val * lm are the same products, the two X tiles the same tile and the two MFMA chains the same accumulators.  The body forms
+// ONE product tile (val * light row 0), runs ONE accumulator pair and stores it to both outputs; the per-record light lookup
+// (idx_map, light_idx, clamp: every index clamps to row 0) is gone.  Bit-identical to the two-chain form, with one theoretical
+// exception: a light entry that is exactly -0.0f has mean +0.0f, so an intrinsic feature that is an all-zero sum could differ in
+// the sign of its zero.  Two alternating chains of 32-cycle v_mfma_f32_16x16x4_f32 keep dependent MFMAs 64 cycles apart.
+template <int C4, bool RAD, bool INTR, bool JIT, bool HX = false, bool ONE = false>
 __device__ __forceinline__ void
 app_mfma_body(const TirField& f, const float* __restrict__ xyz, const int32_t* __restrict__ light_idx,
               const int32_t* __restrict__ idx_map, float* __restrict__ rad_feat, float* __restrict__ int_feat,
@@ -591,7 +597,9 @@ app_mfma_body(const TirField& f, const float* __restrict__ xyz, const int32_t* _
               const int bid, const int nblk) {
     if (n_dev) n = min(n, (int64_t)max(*n_dev, 0));        // device-side point count (no host sync needed)
     constexpr int CA = C4 * 4;
-    constexpr int NX = (RAD ? 1 : 0) + (INTR ? 1 : 0);
+    static_assert(!ONE || (RAD && INTR && !JIT), "single-light mode: both features of the unjittered records");
+    constexpr int NX = ONE ? 1 : (RAD ? 1 : 0) + (INTR ? 1 : 0);
+    constexpr bool INTR2 = INTR && !ONE;                   // the intrinsic feature has a product tile and a chain of its own
     static_assert(!HX || CA <= 64, "half-split contraction: one VM group must fit two 32-wide k-steps");
     constexpr int W_FLOATS = HX ? (2 * 3 * 2 * 2 * 64 * 16) / 4 : 3 * CA * 32;          // operand tiles hi + lo | fp32 basis_mat^T
     constexpr int X_FLOATS = HX ? (NX * 2 * 16 * TIR_XHX * 2) / 4 : NX * CA * TIR_XLD;   // per wave
@@ -647,7 +655,9 @@ app_mfma_body(const TirField& f, const float* __restrict__ xyz, const int32_t* _
             if (jt.xyz_out && c == 0 && s < n) { jt.xyz_out[3 * s] = p[0]; jt.xyz_out[3 * s + 1] = p[1]; jt.xyz_out[3 * s + 2] = p[2]; }
         }
         const float* lrow = nullptr;
-        if (RAD) {
+        if constexpr (ONE) {
+            lrow = LT;                                     // row 0 of the staged light_line (the launcher stages it: lt_rows = 1)
+        } else if (RAD) {
             int64_t lsel = idx_map ? (int64_t)idx_map[sc] : sc;
             if (idx_div > 1) lsel /= idx_div;
             int li = light_idx[lsel];
@@ -706,7 +716,7 @@ app_mfma_body(const TirField& f, const float* __restrict__ xyz, const int32_t* _
                             xr[0] = val[0] * lr.x; xr[TIR_XLD] = val[1] * lr.y; xr[2 * TIR_XLD] = val[2] * lr.z; xr[3 * TIR_XLD] = val[3] * lr.w;
                         }
                     }
-                    if (INTR) {
+                    if (INTR2) {
                         const float4 lm = ld4(lmean + k * CA + 4 * ch4);
                         if constexpr (HX) {
                             const float vi[4] = {val[0] * lm.x, val[1] * lm.y, val[2] * lm.z, val[3] * lm.w};
@@ -736,7 +746,7 @@ app_mfma_body(const TirField& f, const float* __restrict__ xyz, const int32_t* _
                         accr[0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah0, bl, accr[0], 0, 0, 0);
                         accr[1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah1, bl, accr[1], 0, 0, 0);
                     }
-                    if (INTR) {
+                    if (INTR2) {
                         const _Float16* xi = XH + (RAD ? 2 * 16 * TIR_XHX : 0) + jj * TIR_XHX + 32 * t + 8 * kq;
                         const app_f16x8 bh = *reinterpret_cast<const app_f16x8*>(xi), bl = *reinterpret_cast<const app_f16x8*>(xi + 16 * TIR_XHX);
                         acci[0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah0, bh, acci[0], 0, 0, 0);
@@ -757,7 +767,7 @@ app_mfma_body(const TirField& f, const float* __restrict__ xyz, const int32_t* _
                     accr[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, br, accr[0], 0, 0, 0);
                     accr[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, br, accr[1], 0, 0, 0);
                 }
-                if (INTR) {
+                if (INTR2) {
                     const float bi = X[((RAD ? CA : 0) + 4 * t + kq) * TIR_XLD + jj];
                     acci[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, bi, acci[0], 0, 0, 0);
                     acci[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, bi, acci[1], 0, 0, 0);
@@ -777,22 +787,23 @@ app_mfma_body(const TirField& f, const float* __restrict__ xyz, const int32_t* _
                     else for (int r = 0; r < 4; ++r) if (row0 + r < out_stride) o[r] = accr[mt][r];
                 }
                 if (INTR) {
+                    const f32x4 (&ai)[2] = ONE ? accr : acci;      // single-light mode: the one accumulator pair is both features
                     float* o = int_feat + so * out_stride + row0;
-                    if (row0 + 4 <= out_stride && (out_stride & 3) == 0) *reinterpret_cast<float4*>(o) = make_float4(acci[mt][0], acci[mt][1], acci[mt][2], acci[mt][3]);
-                    else for (int r = 0; r < 4; ++r) if (row0 + r < out_stride) o[r] = acci[mt][r];
+                    if (row0 + 4 <= out_stride && (out_stride & 3) == 0) *reinterpret_cast<float4*>(o) = make_float4(ai[mt][0], ai[mt][1], ai[mt][2], ai[mt][3]);
+                    else for (int r = 0; r < 4; ++r) if (row0 + r < out_stride) o[r] = ai[mt][r];
                 }
             }
         }
     }
 }
 
-template <int C4, bool RAD, bool INTR, bool JIT = false, bool HX = false>
+template <int C4, bool RAD, bool INTR, bool JIT = false, bool HX = false, bool ONE = false>
 __global__ void __launch_bounds__(256)
 k_vm_app_mfma(TirField f, const float* __restrict__ xyz, const int32_t* __restrict__ light_idx,
               const int32_t* __restrict__ idx_map, float* __restrict__ rad_feat, float* __restrict__ int_feat,
               int out_stride, int idx_div, int64_t n, const int32_t* __restrict__ n_dev, int xcd_on, TirJitter jt, int lt_rows) {
-    app_mfma_body<C4, RAD, INTR, JIT, HX>(f, xyz, light_idx, idx_map, rad_feat, int_feat, out_stride, idx_div, n, n_dev, xcd_on, jt,
-                                          lt_rows, (int)blockIdx.x, (int)gridDim.x);
+    app_mfma_body<C4, RAD, INTR, JIT, HX, ONE>(f, xyz, light_idx, idx_map, rad_feat, int_feat, out_stride, idx_div, n, n_dev, xcd_on, jt,
+                                               lt_rows, (int)blockIdx.x, (int)gridDim.x);
 }
 
 // The two appearance gathers of the primary stage in ONE launch: workgroups [0, nb0) compute the radiance + intrinsic
@@ -812,6 +823,25 @@ k_vm_app_primary(TirField f, const float* __restrict__ xyz, const int32_t* __res
     } else {
         app_mfma_body<C4, false, true, true, HX>(f, xyz, nullptr, nullptr, nullptr, int_feat_jit, out_stride, 0, n, n_dev, xcd_on, jt,
                                                  lt_rows, (int)blockIdx.x - nb0, (int)gridDim.x - nb0);
+    }
+}
+
+// The merged launch for a field with ONE light (every single-light configuration, the bench scene among them): the record
+// slice runs the single-contraction mode of app_mfma_body, so a record pass issues the 72 matrix instructions of a jitter pass
+// instead of 144 and the two halves of the grid cost the same.  A kernel of its own name: k_vm_app_primary<C4, HX> stays the
+// multi-light code, instruction for instruction.
+template <int C4, bool HX = false>
+__global__ void __launch_bounds__(256)
+k_vm_app_primary_one(TirField f, const float* __restrict__ xyz, float* __restrict__ rad_feat, float* __restrict__ int_feat,
+                     float* __restrict__ int_feat_jit, int out_stride, int64_t n, const int32_t* __restrict__ n_dev, int xcd_on,
+                     TirJitter jt, int nb0) {
+    if ((int)blockIdx.x < nb0) {
+        TirJitter none{0.0f, 0ull, 0ull, nullptr, nullptr};
+        app_mfma_body<C4, true, true, false, HX, true>(f, xyz, nullptr, nullptr, rad_feat, int_feat, out_stride, 0, n, n_dev, xcd_on, none,
+                                                       1, (int)blockIdx.x, nb0);
+    } else {
+        app_mfma_body<C4, false, true, true, HX>(f, xyz, nullptr, nullptr, nullptr, int_feat_jit, out_stride, 0, n, n_dev, xcd_on, jt,
+                                                 0, (int)blockIdx.x - nb0, (int)gridDim.x - nb0);
     }
 }
 
@@ -1211,6 +1241,14 @@ static int launch_app(const TirField* f, const float* xyz, const int32_t* li, co
         hipLaunchKernelGGL((k_vm_app_mfma<C4, false, true, true>), g, b, lds, s, *f, xyz, li, map, rad, intr, stride, idx_div, n, n_dev, xcd_on, jt, lt_rows);
         return TIR_OK;
     }
+    if constexpr (C4 == 12) {
+        if (rad && intr && f->n_lights == 1) {      // one light: one contraction feeds both features (app_mfma_body ONE)
+            const size_t lds1 = (size_t)(3 * CA * 32 + 2 * 3 * CA + 4 * CA * TIR_XLD) * sizeof(float);
+            if (int rc = tir_allow_dynamic_lds(reinterpret_cast<const void*>(k_vm_app_mfma<C4, true, true, false, false, true>), 160 * 1024)) return rc;
+            hipLaunchKernelGGL((k_vm_app_mfma<C4, true, true, false, false, true>), g, b, lds1, s, *f, xyz, li, map, rad, intr, stride, idx_div, n, n_dev, xcd_on, jt, 1);
+            return TIR_OK;
+        }
+    }
     if (rad && intr) hipLaunchKernelGGL((k_vm_app_mfma<C4, true, true>), g, b, lds, s, *f, xyz, li, map, rad, intr, stride, idx_div, n, n_dev, xcd_on, jt, lt_rows);
     else if (rad)    hipLaunchKernelGGL((k_vm_app_mfma<C4, true, false>), g, b, lds, s, *f, xyz, li, map, rad, intr, stride, idx_div, n, n_dev, xcd_on, jt, lt_rows);
     else             hipLaunchKernelGGL((k_vm_app_mfma<C4, false, true>), g, b, lds, s, *f, xyz, li, map, rad, intr, stride, idx_div, n, n_dev, xcd_on, jt, lt_rows);
@@ -1282,6 +1320,22 @@ static int app_primary_launch(const TirField* f, const float* xyz, const int32_t
     nb = (nb + 7) / 8 * 8;                                   // both slices start at a multiple of 8 (XCD mapping)
     const int xcd_on = tir_xcd_mapping(f);
     TirJitter jt{scale, (unsigned long long)seed, (unsigned long long)offset, reinterpret_cast<const long long*>(rng_state), xyz_out};
+    if (f->n_lights == 1) {
+        // one light: light_mean is light_line[0], the record slice contracts once for both features (k_vm_app_primary_one);
+        // light_idx and idx_map are not read (every index clamps to row 0)
+        const size_t lds1 = (w_floats + (size_t)2 * 3 * CA + 4 * (x_floats / 2)) * sizeof(float);       // one feature set per wave
+        if (hx) {
+            if (int rc = tir_allow_dynamic_lds(reinterpret_cast<const void*>(k_vm_app_primary_one<C4, true>), 160 * 1024)) return rc;
+            hipLaunchKernelGGL((k_vm_app_primary_one<C4, true>), dim3((unsigned)(2 * nb)), dim3(256), lds1, tir_stream(stream), *f, xyz,
+                               rad_feat, int_feat, int_feat_jit, out_stride, n, n_dev, xcd_on, jt, (int)nb);
+        } else {
+            if (int rc = tir_allow_dynamic_lds(reinterpret_cast<const void*>(k_vm_app_primary_one<C4, false>), 160 * 1024)) return rc;
+            hipLaunchKernelGGL((k_vm_app_primary_one<C4, false>), dim3((unsigned)(2 * nb)), dim3(256), lds1, tir_stream(stream), *f, xyz,
+                               rad_feat, int_feat, int_feat_jit, out_stride, n, n_dev, xcd_on, jt, (int)nb);
+        }
+        TIR_CHECK_LAUNCH();
+        return TIR_OK;
+    }
     if (hx) {
         if (int rc = tir_allow_dynamic_lds(reinterpret_cast<const void*>(k_vm_app_primary<C4, true>), 160 * 1024)) return rc;
         hipLaunchKernelGGL((k_vm_app_primary<C4, true>), dim3((unsigned)(2 * nb)), dim3(256), lds, tir_stream(stream), *f, xyz, light_idx, idx_map,

@@ -959,10 +959,13 @@ k_indirect_fused(TirField f, TirFieldHalf fh, const float* __restrict__ packed, 
         const float* lrow;
         const _Float16* lrow16;
         {
-            unsigned lsel = rec_map ? (unsigned)rec_map[sgc] : (unsigned)sgc, rem_;      // record -> ray: / idx_div (n < 2^31, launcher)
-            lsel = udiv(lsel, by_div, rem_);
-            int li = light_idx[lsel];
-            li = min(max(li, 0), f.n_lights - 1);
+            int li = 0;                        // one light: every index clamps to row 0, no lookup (wave-uniform branch)
+            if (f.n_lights > 1) {
+                unsigned lsel = rec_map ? (unsigned)rec_map[sgc] : (unsigned)sgc, rem_;      // record -> ray: / idx_div (n < 2^31, launcher)
+                lsel = udiv(lsel, by_div, rem_);
+                li = light_idx[lsel];
+                li = min(max(li, 0), f.n_lights - 1);
+            }
             lrow = n_lt ? LT + li * (3 * CA) : f.light_line + (size_t)li * (3 * CA);
             lrow16 = LT16 + li * (3 * CA);
         }
@@ -1339,10 +1342,13 @@ k_indirect_fused_hp(TirField f, const float* __restrict__ packed, const float* _
             const int64_t sac = sa < n ? sa : n - 1, sbc = sb < n ? sb : n - 1;
             pA[0] = xyz[3 * sac]; pA[1] = xyz[3 * sac + 1]; pA[2] = xyz[3 * sac + 2];
             pB[0] = xyz[3 * sbc]; pB[1] = xyz[3 * sbc + 1]; pB[2] = xyz[3 * sbc + 2];
-            unsigned la = rec_map ? (unsigned)rec_map[sac] : (unsigned)sac, lb = rec_map ? (unsigned)rec_map[sbc] : (unsigned)sbc, rem_;
-            la = udiv(la, by_div, rem_); lb = udiv(lb, by_div, rem_);
-            int lia = light_idx[la], lib = light_idx[lb];
-            lia = min(max(lia, 0), f.n_lights - 1); lib = min(max(lib, 0), f.n_lights - 1);
+            int lia = 0, lib = 0;              // one light: every index clamps to row 0, no lookup (wave-uniform branch)
+            if (f.n_lights > 1) {
+                unsigned la = rec_map ? (unsigned)rec_map[sac] : (unsigned)sac, lb = rec_map ? (unsigned)rec_map[sbc] : (unsigned)sbc, rem_;
+                la = udiv(la, by_div, rem_); lb = udiv(lb, by_div, rem_);
+                lia = light_idx[la]; lib = light_idx[lb];
+                lia = min(max(lia, 0), f.n_lights - 1); lib = min(max(lib, 0), f.n_lights - 1);
+            }
             lrA = LT + lia * (3 * CA);         // (the launcher stages every light row in LDS: n_lights <= 16)
             lrB = LT + lib * (3 * CA);
         }
