@@ -27,7 +27,7 @@ from __future__ import annotations
 
 import torch
 
-from . import ops, relight
+from . import capacity, ops, relight
 
 MAX_SAMPLES = 256      # the secondary march's limit
 
@@ -45,18 +45,18 @@ def _shading_normals(model, f, xyz, intr):
 
 
 def _march_records(model, f, origins, dirs, z):
-    """The inward march with its w > thres samples recorded; the record buffers are sized from the previous call's count and
-    the march is repeated with room when they overflow (the count is read back: one host synchronisation per chunk)."""
+    """The inward march with its w > thres samples recorded: the synchronous form of the record-capacity protocol (capacity.py) --
+    the count is read back (one host synchronisation per chunk) and the march repeated with room when it did not fit."""
     n = origins.shape[0]
-    hints = model.__dict__.setdefault("_bake_cap_hints", {})
-    cap = hints.get(n) or relight._rec_capacity(n)
+    rc = capacity.PassCapacity(model.__dict__.setdefault("_bake_cap_hints", {}), n, 1.5, decay=0, max_entries=32)
+    cap = rc.hinted() or relight._rec_capacity(n)
     while True:
         _, _, rec = ops.march_secondary(f, origins, dirs, z, n, None, None, None, model.march_t_stop, True, cap, False, 0)
         total = int(rec["counter"][0].item())
         if total <= cap:
             break
-        cap = int(total * 1.25) + 1024
-    ops.learn_capacity(hints, n, total, 1.5, decay=0, max_entries=32)
+        cap = rc.regrow(total)
+    rc.settle(total)
     return rec, total
 
 

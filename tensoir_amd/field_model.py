@@ -17,7 +17,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import indirect, ops
+from . import capacity, indirect, ops
 from ._lib import TensoirHipError, TirField
 
 MAT_MODE = [[0, 1], [0, 2], [1, 2]]
@@ -1003,18 +1003,15 @@ class TensorVMSplit(nn.Module):
                         raise
             out = self.unpack_maps(maps, is_relight, want_mask=_want_mask)
             return (out, maps) if _return_maps else out
-        # Record capacity: the number A of w > thres samples is only known on the device.  The first call per
-        # (B, S) reads it back (one host sync in the middle of the pass); later inference calls size their buffers
-        # from the previous count, bound every kernel by the device-side count (n_dev) and check for overflow
-        # once everything -- incl. the caller's shading stage when _defer_check -- has been queued.
-        hints = self.__dict__.setdefault("_app_cap_hints", {})
-        cap = hints.get((B, S)) if (not is_train and _brdf_jitter_dense is None) else None
+        # record-capacity protocol: capacity.py; without a hint this pass counts exactly (one host sync mid-pass)
+        rc = capacity.PassCapacity(self.__dict__.setdefault("_app_cap_hints", {}), (B, S), 1.25, ceiling=B * S, max_entries=64,
+                                   capture=self.__dict__.get("_capture"), check_key=("primary", B, S))
+        cap = rc.hinted() if (not is_train and _brdf_jitter_dense is None) else None
         words = viewdirs = None
         if cap is None:
             weight, acc, depth, _tend, cnt = ops.march_primary(f, rays, jitter, S, self.march_t_stop)
             offsets = ops.exclusive_scan(cnt)
-            A = int(offsets[-1].item())                  # the one host sync of the pass
-            n_dev = total_dev = None
+            A, n_dev = int(offsets[-1].item()), None     # the one host sync of the pass
         else:
             # hinted (sync-free) route: ONE launch marches, emits the view-direction table, re-arms the counters of the
             # later kernels of this pass and scans the record counts (its last workgroup)
@@ -1023,8 +1020,7 @@ class TensorVMSplit(nn.Module):
                                                                                             cap, words)
             self.__dict__["_rec_counter_armed"] = words[1:3]
             A, n_dev = cap, offsets[B:]
-            # eager calls: the count travels to the host while the rest of the pass is queued (no queue drain at the check)
-            total_host = None if self.__dict__.get("_capture") is not None else ops.AsyncCount(total_dev)
+            rc.watch(total_dev, cap)
         rec_ray, rec_k, rec_w, rec_xyz = ops.compact_primary(f, rays, jitter, weight, offsets, A)
         rgb = brdf = brdf_j = pred = derived = None
         rng_state = None
@@ -1089,24 +1085,13 @@ class TensorVMSplit(nn.Module):
         if self.normals_kind not in NORMAL_LOSS_KINDS and is_relight:
             maps[:, 16] = 0.0        # the orientation loss is only filled in the branches that predict AND derive (:953-968)
 
-        def finish():
-            """True when the pass is valid; False when the record capacity overflowed (the caller re-runs)."""
-            total = A if total_dev is None else (total_host.get() if total_host is not None else int(total_dev.item()))
-            ops.learn_capacity(hints, (B, S), total, 1.25, ceiling=B * S, max_entries=64)
-            if total_dev is not None and total > cap:
-                hints.pop((B, S), None)               # next call takes the exact (synchronising) route
-                return False
-            return True
-        capture = self.__dict__.get("_capture")
-        if capture is not None:                       # HIP-graph capture (tensoir_amd/graph.py): no host reads here;
-            if total_dev is None:                     # the owner of the graph checks the counters after each replay
-                raise TensoirHipError("graph capture needs a warmed-up record-capacity hint (run one eager call first)")
-            capture.append((total_dev, cap, ("primary", B, S)))
-        elif _defer_check:
-            self.__dict__["_pending_primary"] = finish
-        elif not finish():
-            return self.forward(rays_chunk, light_idx, white_bg, is_train, ndc_ray, is_relight, N_samples,
-                                _brdf_jitter_dense, _return_maps, False, _want_mask)
+        if rc.capture is None:                        # (capturing: the graph's owner checks the registered counter after each replay)
+            finish = rc.settle if words is not None else functools.partial(rc.settle, A)
+            if _defer_check:
+                self.__dict__["_pending_primary"] = finish
+            elif not finish():
+                return self.forward(rays_chunk, light_idx, white_bg, is_train, ndc_ray, is_relight, N_samples,
+                                    _brdf_jitter_dense, _return_maps, False, _want_mask)
         out = self.unpack_maps(maps, is_relight, want_mask=_want_mask, smooth=smooth)
         return (out, maps) if _return_maps else out
 

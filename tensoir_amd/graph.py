@@ -24,7 +24,7 @@ import gc
 
 import torch
 
-from . import indirect, ops, relight  # noqa: F401  (relight: imported for its caches being warmed by the eager call)
+from . import capacity, indirect, ops, relight  # noqa: F401  (relight: imported for its caches being warmed by the eager call)
 from ._lib import TensoirHipError
 from .renderer import Renderer_TensoIR_train
 
@@ -128,9 +128,8 @@ class GraphedRenderer:
         torch.cuda.synchronize()
         # never capture with less room than an earlier capture of this renderer had: a chunked image render walks
         # through light and heavy chunks, and the capacity should converge to the heaviest instead of following the last
-        for (kind, *key), cap in self.__dict__.get("_cap_floor", {}).items():
-            hints = self.model._app_cap_hints if kind == "primary" else self.model._rec_cap_hints
-            k = tuple(key) if kind == "primary" else key[0]
+        for key, cap in self.__dict__.get("_cap_floor", {}).items():
+            hints, k, _ = capacity.check_site(self.model, key)
             if k in hints:
                 hints[k] = max(hints[k], cap)
         shrink = self.__dict__.pop("_test_shrink_capacity", None)      # tests: capture with a capacity that is too small
@@ -187,14 +186,9 @@ class GraphedRenderer:
         """A replay produced `total` records for `key`: the next capture gets room for it (and the eager call that
         precedes the capture relearns the hint)."""
         floor = self.__dict__.setdefault("_cap_floor", {})
-        need = int(total * 1.25) + 4096
-        if key[0] == "primary":
-            need = min(need, key[1] * key[2])              # never more than rays x samples
+        hints, k, need = capacity.check_site(self.model, key, total)
         floor[key] = max(floor.get(key, 0), need)
-        if key[0] == "primary":
-            self.model._app_cap_hints.pop((key[1], key[2]), None)
-        else:
-            self.model._rec_cap_hints.pop(key[1], None)
+        hints.pop(k, None)
 
     def validate(self):
         """Wait for the queued replays and report whether all of them stayed within the captured record capacities.

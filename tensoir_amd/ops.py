@@ -61,7 +61,6 @@ def mlp_aux_table(m: "PackedMlp", aux):
     return table
 
 
-
 # While a HIP graph is being captured (GraphedRenderer._capture sets this to a list it keeps for the graph's lifetime) every
 # cached table a captured launch reads is appended here: the graph bakes the table's raw address, so the tensor must outlive
 # its cache entry (the cache holds at most four tables per decoder and evicts on the fifth aux tensor).
@@ -164,40 +163,8 @@ def _stream(t=None):
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
-class AsyncCount:
-    """A device-side int32 counter on its way to the host: the copy into pinned memory and an event are queued NOW, on the
-    current stream, right behind the kernel that produced the counter.  `get()` waits for that event only -- not for the
-    launches queued afterwards -- so a capacity check at the end of a pass does not drain the launch queue (with
-    `tensor.item()` it does: the GPU then idles while the host queues the next stage)."""
-
-    def __init__(self, counter):
-        self.pin = torch.empty(1, dtype=torch.int32, pin_memory=True)
-        self.pin.copy_(counter.view(-1)[:1], non_blocking=True)
-        self.ev = torch.cuda.Event()
-        self.ev.record(torch.cuda.current_stream(counter.device))      # the counter's device, which need not be current
-        self.value = None
-
-    def get(self) -> int:
-        if self.value is None:
-            self.ev.synchronize()
-            self.value = int(self.pin[0])
-            self.pin = None
-        return self.value
-
-
-def learn_capacity(hints, key, total, growth, *, ceiling=None, decay=0.97, max_entries):
-    """Record capacity for the next call of problem size `key`, learnt from this call's count `total`: growth x the count plus
-    slack, never below 16 k rows, and decaying slowly from the previous hint (a heavy batch after a light one must not
-    overflow); at most `ceiling` rows where the caller knows a bound.  `hints` is the caller's plain dict; it is emptied
-    when it holds more than `max_entries` sizes."""
-    if len(hints) > max_entries:
-        hints.clear()
-    cap = max(int(total * growth) + 4096, 1 << 14, int(decay * hints.get(key, 0)))
-    hints[key] = cap if ceiling is None else min(cap, ceiling)
-
-
 class AsyncFloats:
-    """A few device floats on their way to the host (AsyncCount for float tables): copy into pinned memory + event queued NOW.
+    """A few device floats on their way to the host (capacity.AsyncCount for float tables): copy into pinned memory + event queued NOW.
     Pinned buffers and events are recycled (a training step creates one of these per parameter version)."""
     _free = []
 

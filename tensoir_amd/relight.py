@@ -8,7 +8,7 @@ import os
 import numpy as np
 import torch
 
-from . import indirect, ops
+from . import capacity, indirect, ops
 from .field_model import safe_l2_normalize  # noqa: F401  (re-exported, as the reference module does)
 
 MAP_STRIDE = ops.MAP_STRIDE
@@ -97,128 +97,101 @@ def _map_measure(probe_map, vis, packed, full_rows, count, n_rays, map_limit):
     return measure
 
 
+def _decode_pass(tensoIR, f, vis, rec, n_rows, n_dev, count, lookup, n_rays, force_full, keep_records, training, probe_map):
+    """The record-decoding middle of one march attempt of _secondary: pick the tier (`full` when force_full, else the precision
+    policy's), run the range guard where its maxima are at hand, decode the first n_rows records -- through indirect.establish
+    when the policy has no verdict yet; count() = the valid rows, asked for after the f16 decode has been queued -- and pack or
+    accumulate them per ray -> (indirect_rgb, rng); rng = a range check still pending (judged at the end-of-pass check)."""
+    capturing = tensoIR.__dict__.get("_capture") is not None
+    mode = "full" if force_full else indirect.mode(tensoIR, training)
+    if mode == "probe" and capturing:
+        raise ops._lib.TensoirHipError("graph capture needs an established indirect-light precision verdict (run the pass eagerly first)")
+    if n_rows <= 0:
+        return torch.zeros((n_rays, 3), dtype=torch.float32, device=vis.device), None
+    rec_ray, rec_w, rec_xyz = rec["ray"][:n_rows], rec["w"][:n_rows], rec["xyz"][:n_rows]
+    fh = tensoIR.packed_field_half(_fresh=True) if (mode != "full" and ops.secondary_app_impl() == "h16") else None
+    rng = tensoIR.half_range(_fresh=True) if (fh is not None and ops.INDIRECT_GUARD) else None
+    if rng is not None and (mode == "probe" or rng.ready()):   # a pass that waits anyway, or maxima that have arrived: now
+        if _range_failed(tensoIR, rng):
+            mode, fh = "full", None
+        rng = None
+    if capturing and rng is not None and not rng.ready():
+        raise ops._lib.TensoirHipError("graph capture needs a finished range check of the fp16 field shadow (run the pass eagerly first)")
+
+    def decode(kind):
+        return _decode_records(tensoIR, f, fh, kind, rec_xyz, rec_ray, n_dev, *lookup)
+
+    def packed(rgb):
+        if keep_records:       # the caller's integration kernel sums the records itself (tir_shade_integrate_records)
+            return {"off": rec["off"], "cnt": rec["cnt"], "w": rec_w, "rgb": rgb}
+        return ops.accumulate_records(rec["off"], rec["cnt"], rec_w, rgb, n_rays)
+
+    if mode != "probe":        # (probe: auto policy, no verdict for these parameters yet -> self-check on this pass's own records)
+        return packed(decode(mode)), rng
+    if probe_map is not None:
+        decode = functools.lru_cache(maxsize=None)(decode)       # the full rows: measured against, and the last tier
+        # a TRAINING pass renders the map as a no_grad constant of the loss (models/relight_utils.py:344): there the
+        # policy accepts up to the contract's own tolerance; inference / export use the strict limit
+        measure = _map_measure(probe_map, vis, packed, lambda: decode("full"), lambda: min(count(), n_rows), n_rays,
+                               ops.INDIRECT_PROBE["train_map_limit" if training else "map_limit"])
+        try_hp = ops.INDIRECT_HP
+    else:
+        def measure(rows):
+            return indirect.record_estimate(rows, min(count(), n_rows), lambda sel: _decode_records(
+                tensoIR, f, None, "full", rec_xyz[sel].contiguous(), rec_ray[sel].contiguous(), None, *lookup))
+        try_hp = ops.INDIRECT_HP and _fusable(f, *lookup[2:], n_rows) and ops.AUX_TABLE and ops.MLP_IMPL == "bf16x3"
+    return packed(indirect.establish(tensoIR, decode, measure, try_hp, train_limit=training and probe_map is not None)[1]), rng
+
+
 def _secondary(tensoIR, origins, dirs, n_rays, z, org_map, dir_map, active, light_idx, light_div,
                want_indirect, want_nerfactor=False, n_dirs=0, keep_records=False, ids=None, defer=False, training=False,
                probe_map=None):
-    """Shared driver of compute_transmittance / compute_radiance / render_with_BRDF:
-    march (+ record the w > thres samples) -> appearance gather -> radiance decoder -> per-ray sum.
-
-    No host synchronisation on the record count: the record buffers are sized from the previous call's
-    count (x1.5), the gather / decoder kernels read the actual count from device memory (n_dev), and the
-    count is checked once after everything has been queued; an overflow (rare) re-runs the stage.
-
+    """Shared driver of compute_transmittance / compute_radiance / render_with_BRDF: march (+ record the w > thres samples) ->
+    _decode_pass, repeated until the records fit and the range guard holds, under the record-capacity protocol of capacity.py.
     An inference pass marches through the dense density volume (packed_field_dense); a training pass keeps the VM kernels."""
     f = tensoIR.packed_field() if training else tensoIR.packed_field_dense()
-    dev = origins.device
     if not want_indirect:
         vis, oma, _ = ops.march_secondary(f, origins, dirs, z, n_rays, org_map, dir_map, active,
                                           tensoIR.march_t_stop, False, 0, want_nerfactor, n_dirs)
         return vis, oma, None
-    hints = tensoIR.__dict__.setdefault("_rec_cap_hints", {})      # record capacity learnt per problem size
-    cap = hints.get(n_rays, 0)
-    first = cap <= 0
-    capture = tensoIR.__dict__.get("_capture")
-    if capture is not None and first:
-        raise ops._lib.TensoirHipError("graph capture needs a warmed-up secondary record-capacity hint")
-    if first:
-        cap = _rec_capacity(n_rays)
+    rc = capacity.PassCapacity(tensoIR.__dict__.setdefault("_rec_cap_hints", {}), n_rays, 1.5, max_entries=32,
+                               capture=tensoIR.__dict__.get("_capture"), check_key=("secondary", n_rays))
+    first = rc.hinted() is None
+    cap = _rec_capacity(n_rays) if first else rc.hinted()
+    extra = {} if ids is None else dict(ray_ids=ids["pair_ids"], n_ids_dev=ids["n_active"], vis=ids["vis"], rec_cnt=ids["rec_cnt"])
     # a record counter the primary march of this pass has already zeroed on the device (no fill launch); first attempt only
     armed = tensoIR.__dict__.pop("_rec_counter_armed", None)
-    force_full = False
+    if armed is not None and armed.device == origins.device:
+        extra["counter"] = armed
+    lookup, force_full = (light_idx, light_div, dirs, dir_map, n_dirs), False
     while True:
-        extra = {} if ids is None else dict(ray_ids=ids["pair_ids"], n_ids_dev=ids["n_active"], vis=ids["vis"],
-                                            rec_cnt=ids["rec_cnt"])
-        if armed is not None and armed.device == dev:
-            extra["counter"] = armed
-        armed = None
         vis, oma, rec = ops.march_secondary(f, origins, dirs, z, n_rays, org_map, dir_map, active,
                                             tensoIR.march_t_stop, True, cap, want_nerfactor, n_dirs, **extra)
+        extra.pop("counter", None)
         n_total, n_dev = rec["counter"][0:1], rec["counter"][1:2]      # all records / the written prefix consumers may read
-        # later attempts: the count travels to the host while the gather / decoder launches are queued
-        total_host = None if (first or capture is not None) else ops.AsyncCount(n_total)
         if first:                                      # no history yet: learn the count before sizing buffers
             total = int(n_total.item())
             if total > cap:
-                cap = int(total * 1.25) + 1024
+                cap = rc.regrow(total)
                 continue
-            n_rows = total
         else:
-            n_rows = cap
-        mode = "full" if force_full else indirect.mode(tensoIR, training)
-        if mode == "probe" and capture is not None:
-            raise ops._lib.TensoirHipError("graph capture needs an established indirect-light precision verdict (run the pass eagerly first)")
-        rng = None
-        if n_rows > 0:
-            rec_ray, rec_w, rec_xyz = rec["ray"][:n_rows], rec["w"][:n_rows], rec["xyz"][:n_rows]
-            fh = tensoIR.packed_field_half(_fresh=True) if (mode != "full" and ops.secondary_app_impl() == "h16") else None
-            rng = tensoIR.half_range(_fresh=True) if (fh is not None and ops.INDIRECT_GUARD) else None
-            if rng is not None and (mode == "probe" or rng.ready()):   # a pass that waits anyway, or maxima that have arrived: now
-                if _range_failed(tensoIR, rng):
-                    mode, fh = "full", None
-                rng = None
-            if capture is not None and rng is not None and not rng.ready():
-                raise ops._lib.TensoirHipError("graph capture needs a finished range check of the fp16 field shadow (run the pass eagerly first)")
-            lookup = (light_idx, light_div, dirs, dir_map, n_dirs)
-
-            def decode(kind):
-                return _decode_records(tensoIR, f, fh, kind, rec_xyz, rec_ray, n_dev, *lookup)
-
-            def packed(rgb):
-                if keep_records:       # the caller's integration kernel sums the records itself (tir_shade_integrate_records)
-                    return {"off": rec["off"], "cnt": rec["cnt"], "w": rec_w, "rgb": rgb}
-                return ops.accumulate_records(rec["off"], rec["cnt"], rec_w, rgb, n_rays)
-
-            if mode == "probe":        # auto policy, no verdict for these parameters yet: self-check on this pass's own records
-                def count():           # (asked for after the f16 decode has been queued)
-                    return min(total if first else total_host.get(), n_rows)
-                if probe_map is not None:
-                    decode = functools.lru_cache(maxsize=None)(decode)       # the full rows: measured against, and the last tier
-                    # a TRAINING pass renders the map as a no_grad constant of the loss (models/relight_utils.py:344): there the
-                    # policy accepts up to the contract's own tolerance; inference / export use the strict limit
-                    measure = _map_measure(probe_map, vis, packed, lambda: decode("full"), count, n_rays,
-                                           ops.INDIRECT_PROBE["train_map_limit" if training else "map_limit"])
-                    try_hp = ops.INDIRECT_HP
-                else:
-                    def measure(rows):
-                        return indirect.record_estimate(rows, count(), lambda sel: _decode_records(
-                            tensoIR, f, None, "full", rec_xyz[sel].contiguous(), rec_ray[sel].contiguous(), None, *lookup))
-                    try_hp = ops.INDIRECT_HP and _fusable(f, dirs, dir_map, n_dirs, n_rows) and ops.AUX_TABLE and ops.MLP_IMPL == "bf16x3"
-                _, rgb = indirect.establish(tensoIR, decode, measure, try_hp, train_limit=training and probe_map is not None)
-            else:
-                rgb = decode(mode)
-            indirect_rgb = packed(rgb)
+            rc.watch(n_total, cap)                     # (capturing: registers the counter with the graph's owner instead)
+        out, rng = _decode_pass(tensoIR, f, vis, rec, total if first else cap, n_dev, lambda: total if first else rc.count.get(), lookup,
+                                n_rays, force_full, keep_records, training, probe_map)
+        if not first and (defer or rc.capture is not None):
+            break                                      # settled later: by the caller, after ITS launches are queued too / by the graph's owner
+        total = total if first else rc.count.get()     # waits for the march only, not for what was queued behind it
+        if total <= cap and _range_failed(tensoIR, rng):
+            force_full = True                          # re-run, decoding with the primary-stage kernels
+        elif rc.settle(total):
+            return vis, oma, out
         else:
-            indirect_rgb = torch.zeros((n_rays, 3), dtype=torch.float32, device=dev)
-
-        if first:
-            if _range_failed(tensoIR, rng):
-                force_full = True
-                continue
-            break
-        if capture is not None:                        # HIP-graph capture: the graph owner reads the counter after replay
-            if _range_failed(tensoIR, rng):
-                raise ops._lib.TensoirHipError("graph capture: the fp16 field shadow fails the range guard")
-            capture.append((n_total, cap, ("secondary", n_rays)))
-            return vis, oma, indirect_rgb
-        if defer:                                      # the caller checks after ITS remaining launches are queued too
-            def check():
-                total = total_host.get()
-                if total > cap:
-                    hints.pop(n_rays, None)            # the re-run learns the count first
-                    return False
-                ops.learn_capacity(hints, n_rays, total, 1.5, max_entries=32)
-                return not _range_failed(tensoIR, rng)     # (a failed range guard: the re-run decodes with the primary-stage kernels)
-            tensoIR.__dict__.setdefault("_pending_checks", []).append(check)
-            return vis, oma, indirect_rgb
-        total = total_host.get()                       # waits for the march only, not for what was queued behind it
-        if total <= cap:
-            if _range_failed(tensoIR, rng):
-                force_full = True
-                continue
-            break
-        cap = int(total * 1.25) + 1024                 # overflow: some rays were dropped -> redo with room
-    ops.learn_capacity(hints, n_rays, total, 1.5, max_entries=32)
-    return vis, oma, indirect_rgb
+            cap = rc.regrow(total)                     # overflow: some rays were dropped -> redo with room
+    if rc.capture is None:                             # (a failed range guard too makes the caller re-run: then with the primary-stage kernels)
+        tensoIR.__dict__.setdefault("_pending_checks", []).append(lambda: rc.settle() and not _range_failed(tensoIR, rng))
+    elif _range_failed(tensoIR, rng):
+        raise ops._lib.TensoirHipError("graph capture: the fp16 field shadow fails the range guard")
+    return vis, oma, out
 
 
 @torch.no_grad()

@@ -57,9 +57,7 @@ def Renderer_TensoIR_train(rays=None, normal_gt=None, light_idx=None, tensoIR=No
                 tensoIR.__dict__["_boundary_graphs"].pop(next(k for k, v in tensoIR.__dict__["_boundary_graphs"].items() if v[0] is gr), None)
     rays = ops.to_device(rays, device)
     light_idx = ops.to_device(light_idx, device, torch.int32)
-    # Record capacities (primary w > thres samples, secondary records) come from the previous call; the device-side
-    # counts are read once, after every launch of the pass has been queued; an overflow (rare) re-runs the pass with
-    # exact counts.  Same for the training forward (the autograd graph of a discarded attempt is simply dropped).
+    # record-capacity protocol (capacity.py): an overflow re-runs the pass (a discarded training attempt's autograd graph is dropped)
     for attempt in range(2):
         (rgb_map, depth_map, normal_map, albedo_map, roughness_map, fresnel_map, acc_map, normals_diff_map,
          normals_orientation_loss_map, acc_mask, albedo_smoothness_loss, roughness_smoothness_loss), maps = \

@@ -18,7 +18,7 @@ from types import SimpleNamespace
 
 import torch
 
-from . import ops
+from . import capacity, ops
 from ._lib import TensoirHipError, TirFieldGrad
 
 
@@ -222,25 +222,21 @@ class PrimaryRenderFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, model, rays, lidx, S, white_bg, is_relight, jitter, noise_dense, defer, *params):
-        """Record capacity as in the inference forward (field_model.forward): the number A of w > thres samples lives
-        on the device.  With a capacity learnt from the previous step the buffers are sized cap rows, every kernel is
-        bounded by the device-side count, and A is read once everything has been queued (`finish`; when `defer` the
-        caller -- Renderer_TensoIR_train -- calls it after its shading stage is queued too).  The backward runs on
-        the exact [:A] views."""
+        """Record-capacity protocol: capacity.py, as in field_model.forward; `finish` also trims the saved rows,
+        so that the backward runs on the exact [:A] views."""
         f = model.packed_field()
         dev = rays.device
         B = rays.shape[0]
         weight, sigma, acc, depth, _tend, cnt = ops.march_primary_train(f, rays, jitter, S, model.march_t_stop)
-        hints = model.__dict__.setdefault("_train_cap_hints", {})
-        cap = hints.get((B, S)) if noise_dense is None else None
+        rc = capacity.PassCapacity(model.__dict__.setdefault("_train_cap_hints", {}), (B, S), 1.25, ceiling=B * S, max_entries=64)
+        cap = rc.hinted() if noise_dense is None else None
         if cap is None:
             offsets = ops.exclusive_scan(cnt)
-            A = int(offsets[-1].item())                    # first step of a batch shape: one host sync mid-pass
-            n_dev = total_dev = None
+            A, n_dev = int(offsets[-1].item()), None       # first step of a batch shape: one host sync mid-pass
         else:
             offsets, total_dev = ops.exclusive_scan_capped(cnt, cap)
             A, n_dev = cap, offsets[B:]
-            total_host = ops.AsyncCount(total_dev)       # on its way to the host while the rest of the pass is queued
+            rc.watch(total_dev, cap)
         rec_ray, rec_k, rec_w, rec_xyz = ops.compact_primary(f, rays, jitter, weight, offsets, A)
         st = SimpleNamespace(model=model, rays=rays, lidx=lidx, S=S, white_bg=white_bg, is_relight=is_relight,
                              jitter=jitter, weight=weight, sigma=sigma, acc=acc, depth=depth, offsets=offsets, A=A,
@@ -306,23 +302,16 @@ class PrimaryRenderFn(torch.autograd.Function):
             maps[:, 16] = 0.0            # only the predict-and-derive branches fill it (tensorBase_rotated_lights.py:953-968)
 
         def finish():
-            """Read the record count; trim the saved rows to it.  False = the capacity overflowed (re-run the pass)."""
-            if total_dev is None:
-                total = A
-            else:
-                total = total_host.get()
-                if total > cap:
-                    hints.pop((B, S), None)            # next call takes the exact (synchronising) route
-                    st.valid = False
-                    return False
-                _trim_state(st, total)
-            if noise_dense is None:
-                ops.learn_capacity(hints, (B, S), total, 1.25, ceiling=B * S, max_entries=64)
-            return True
+            """Settle the record count; trim the saved rows to it.  False = the capacity overflowed (re-run the pass)."""
+            st.valid = rc.settle()
+            if st.valid:
+                _trim_state(st, rc.count.get())
+            return st.valid
 
-        st.finish = None if total_dev is None else finish
-        if total_dev is None:
-            finish()
+        st.finish = None if cap is None else finish
+        if cap is None:
+            if noise_dense is None:
+                rc.settle(A)
         elif defer:
             model.__dict__["_pending_primary"] = _FinishOnce(st)
         elif not _FinishOnce(st)():

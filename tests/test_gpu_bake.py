@@ -211,6 +211,26 @@ def test_chunking_and_repetition_do_not_change_the_result():
     check_ranges(a)
 
 
+def test_record_capacity_routes_do_not_change_the_bake():
+    """bake._march_records under the record-capacity protocol (capacity.py): no hint, the hint that call left, and a hint forced far
+    too small (the march overflows and is repeated with room) bake bit-identical rows, and the overflow relearns the hint."""
+    from tensoir_amd import bake
+    c = BC.case("a16")
+    m = BC.model(c)
+    pts, nrm, n = c.points.cuda(), c.outward.cuda(), c.points.shape[0]
+    m.__dict__.pop("_bake_cap_hints", None)
+    first = bake.bake_points(m, pts, nrm, light_idx=c.light_idx)
+    assert m._bake_cap_hints[n] > 1
+    hinted = bake.bake_points(m, pts, nrm, light_idx=c.light_idx)
+    m._bake_cap_hints[n] = 1
+    overflow = bake.bake_points(m, pts, nrm, light_idx=c.light_idx)
+    torch.cuda.synchronize()
+    assert int((first["coverage"] > 0.5).sum()) > 1                      # (more than one record: capacity 1 did overflow)
+    assert m._bake_cap_hints[n] > 1
+    for k in OUTPUTS:
+        assert torch.equal(hinted[k], first[k]) and torch.equal(overflow[k], first[k]), k
+
+
 # ---- export ------------------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def trained():

@@ -1,6 +1,6 @@
 """Host logic of round 5 that needs no GPU: the verdict state machine of the indirect-light precision policy
 (indirect.mode / set_verdict), its self-check ladder and record estimate (indirect.establish / record_estimate), the
-record-capacity hint (ops.learn_capacity), the range guard's bound (ops.HalfRange.judge), the shard layout used by the image
+record-capacity hint and protocol (capacity.learn_capacity, capacity.PassCapacity, capacity.check_site), the range guard's bound (ops.HalfRange.judge), the shard layout used by the image
 all-gather (dist._layout / gather_records at world 1) and the arithmetic of bench.simulate_ranks."""
 import math
 import os
@@ -219,7 +219,7 @@ def test_record_estimate_statistics(auto_policy, monkeypatch):
 
 def test_learn_capacity():
     """The record-capacity hint of every stage (primary forward, training forward, secondary march, bake)."""
-    from tensoir_amd.ops import learn_capacity
+    from tensoir_amd.capacity import learn_capacity
     h = {}
     learn_capacity(h, "k", 1000, 1.25, max_entries=64)
     assert h == {"k": 16384}                                             # the floor of 16 k rows
@@ -242,6 +242,102 @@ def test_learn_capacity():
     h = {i: 1000000 for i in range(32)}
     learn_capacity(h, 5, 1000, 1.5, max_entries=32)
     assert len(h) == 32 and h[5] == 970000
+
+
+class _Count:
+    """A count source of capacity.PassCapacity that needs no device: answers a chosen integer, remembers what was queued."""
+    made = []
+
+    def __init__(self, counter):
+        self.counter, self.gets = counter, 0
+        _Count.made.append(self)
+
+    def get(self):
+        self.gets += 1
+        return self.counter["total"]
+
+
+@pytest.fixture
+def counts():
+    _Count.made = []
+    return _Count.made
+
+
+PRIMARY = dict(ceiling=4096 * 512, max_entries=64)
+
+
+def test_pass_capacity_without_a_hint(counts):
+    from tensoir_amd.capacity import PassCapacity, learn_capacity
+    hints = {"other": 7}
+    rc = PassCapacity(hints, (4096, 512), 1.25, count_source=_Count, **PRIMARY)
+    assert rc.hinted() is None and counts == [] and hints == {"other": 7}
+    # the caller's exact route hands its own count in: learnt, nothing queued
+    assert rc.settle(30000) is True and counts == []
+    want = {"other": 7}
+    learn_capacity(want, (4096, 512), 30000, 1.25, **PRIMARY)
+    assert hints == want
+
+
+@pytest.mark.parametrize("site", [(1.25, dict(ceiling=4096 * 512, max_entries=64)), (1.5, dict(max_entries=32)),
+                                  (1.5, dict(decay=0, max_entries=32))], ids=["primary", "secondary", "bake"])
+def test_pass_capacity_hinted_and_fits(counts, site):
+    from tensoir_amd.capacity import PassCapacity, learn_capacity
+    growth, learn = site
+    hints, want = {"k": 500000, "other": 7}, {"k": 500000, "other": 7}
+    rc = PassCapacity(hints, "k", growth, count_source=_Count, **learn)
+    cap = rc.hinted()
+    assert cap == 500000
+    counter = {"total": 123456}
+    rc.watch(counter, cap)
+    assert len(counts) == 1 and counts[0].counter is counter and counts[0].gets == 0       # queued at watch(), not read yet
+    assert rc.settle() is True and counts[0].gets == 1
+    learn_capacity(want, "k", 123456, growth, **learn)
+    assert hints == want and hints["k"] != 500000
+    counter["total"] = cap                                               # exactly full still fits
+    rc.watch(counter, cap)
+    assert rc.settle() is True
+
+
+def test_pass_capacity_overflow_drops_the_hint_and_learns_nothing(counts):
+    from tensoir_amd.capacity import PassCapacity
+    hints = {i: 1000000 for i in range(70)}                              # (above max_entries: a learn would empty the table)
+    rc = PassCapacity(hints, 5, 1.25, count_source=_Count, **PRIMARY)
+    rc.watch({"total": 1000001}, rc.hinted())
+    assert rc.settle() is False
+    assert hints == {i: 1000000 for i in range(70) if i != 5}
+    assert rc.regrow(1000001) == int(1000001 * 1.25) + 1024 and PassCapacity.regrow(0) == 1024
+
+
+def test_pass_capacity_while_capturing(counts):
+    from tensoir_amd._lib import TensoirHipError
+    from tensoir_amd.capacity import PassCapacity
+    checks, hints, counter = [], {77: 20000}, object()
+    rc = PassCapacity(hints, 77, 1.5, max_entries=32, capture=checks, check_key=("secondary", 77), count_source=_Count)
+    rc.watch(counter, rc.hinted())
+    assert len(checks) == 1 and checks[0][0] is counter and checks[0][1:] == (20000, ("secondary", 77))
+    assert counts == [] and hints == {77: 20000}                         # no host read is queued inside a capture
+    with pytest.raises(TensoirHipError):
+        PassCapacity({}, 77, 1.5, max_entries=32, capture=checks, check_key=("secondary", 77), count_source=_Count).hinted()
+    assert len(checks) == 1 and counts == []
+
+
+def test_pass_capacity_ceiling_caps_the_hint(counts):
+    from tensoir_amd.capacity import PassCapacity
+    hints = {(64, 100): 6300}
+    rc = PassCapacity(hints, (64, 100), 1.25, ceiling=64 * 100, max_entries=64, count_source=_Count)
+    rc.watch({"total": 6000}, rc.hinted())
+    assert rc.settle() is True and hints[(64, 100)] == 6400              # 1.25 x 6000 + 4096 and the 16 k floor are both above B * S
+
+
+def test_check_site_maps_graph_keys():
+    from tensoir_amd.capacity import check_site
+    m = types.SimpleNamespace(_app_cap_hints={(4096, 512): 1}, _rec_cap_hints={524288: 2})
+    hints, key, need = check_site(m, ("primary", 4096, 512), 100000)
+    assert hints is m._app_cap_hints and key == (4096, 512) and need == int(100000 * 1.25) + 4096
+    assert check_site(m, ("primary", 64, 100), 6000)[2] == 6400          # never more than rays x samples
+    hints, key, need = check_site(m, ("secondary", 524288), 3000000)
+    assert hints is m._rec_cap_hints and key == 524288 and need == int(3000000 * 1.25) + 4096
+    assert key in hints
 
 
 def test_half_range_bound():
