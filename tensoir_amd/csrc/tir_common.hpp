@@ -2,6 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <initializer_list>
+#include <type_traits>
 #include "tensoir_hip.h"
 
 #define TIR_WAVE 64
@@ -70,6 +72,115 @@ static inline bool tir_dense_sigma_ok(const TirField* f) {
     if (!f->dense_sigma || f->dense_pitch <= f->grid[0]) return false;
     const int64_t Y = f->grid[1], Z = f->grid[2], pb = (int64_t)f->dense_pitch * 4;
     return f->grid[0] >= 2 && Y >= 1 && Z >= 1 && Y * Z < (1 << 24) && pb < (1 << 24) && Y * Z * pb < ((int64_t)1 << 32);
+}
+
+// ---- host side of the gather and decoder entry points (tir_field.hip, tir_mlp.hip, tir_vm_app_bwd): every precondition and
+// every launch formula is stated once here; where the entries differ, the difference is an argument with its reason.
+static inline bool tir_any_null(std::initializer_list<const void*> ptrs) {
+    for (const void* p : ptrs) if (!p) return true;
+    return false;
+}
+static inline bool tir_aligned16(std::initializer_list<const void*> ptrs) {          // (a null pointer counts as aligned)
+    for (const void* p : ptrs) if (reinterpret_cast<uintptr_t>(p) % 16 != 0) return false;
+    return true;
+}
+
+// What a kernel family reads of an appearance field.  A default TirAppNeeds is the fp32 gathers': fp32 tables at any alignment,
+// all light tables, 64-bit tap addresses, several widths, app_dim in 1..27, feature rows of app_dim..32 floats; every
+// departure is named where the entry states its needs.
+struct TirAppNeeds {
+    const TirFieldHalf* half = nullptr;   // the planes / lines are the fp16 shadow tables, not the TirField's fp32 ones
+    bool aligned16 = false;               // taps are loaded as 16-byte vectors from a 16-byte aligned base
+    bool light_mean = true;               // false only for the hp fused entry, which has no intrinsic (mean-light) feature set
+    bool index32 = false;                 // plane taps addressed with 32-bit element offsets (tir_app_index_ok)
+    int n_acomp = 0;                      // the one width the family is built for; 0: several -- refused where the kernel is chosen,
+                                          // AFTER the n == 0 return (kept as found: an empty call with an unbuilt width is TIR_OK there)
+    int app_dim = 0;                      // app_dim must equal this; 0: 1..27
+    bool feature_rows = true;             // the entry writes / reads feature rows of out_stride floats
+    int stride_max = 32;                  // out_stride <= this
+    TirAppNeeds& fp16_tables(const TirFieldHalf* fh) { half = fh; return *this; }
+    TirAppNeeds& aligned() { aligned16 = true; return *this; }
+    TirAppNeeds& no_light_mean() { light_mean = false; return *this; }
+    TirAppNeeds& element_index32() { index32 = true; return *this; }
+    TirAppNeeds& width(int n) { n_acomp = n; return *this; }
+    TirAppNeeds& app_dim_is(int d) { app_dim = d; return *this; }            // the fused entries feed the decoder's F columns
+    TirAppNeeds& no_feature_rows() { feature_rows = false; return *this; }     // the fused entries keep the features in registers
+    TirAppNeeds& stride_unbounded() { stride_max = 0x7fffffff; return *this; }   // tir_vm_app_bwd: kept as found; not known to be needed
+};
+
+// "An appearance field this kernel family can read": TIR_ERR_ARG for a missing / misaligned table, then TIR_ERR_UNSUPPORTED for
+// a shape no kernel is built for, then TIR_ERR_ARG for the row stride -- the order every entry had.  f is not null.
+static inline int tir_check_app_field(const TirField* f, const TirAppNeeds& need, int out_stride) {
+    for (int i = 0; i < 3; ++i) {
+        const void* plane = need.half ? need.half->aplane[i] : static_cast<const void*>(f->aplane[i]);
+        const void* line = need.half ? need.half->aline[i] : static_cast<const void*>(f->aline[i]);
+        if (f->grid[i] < 2 || !plane || !line || (need.aligned16 && !tir_aligned16({plane, line}))) return TIR_ERR_ARG;
+    }
+    if (!f->basis_t || !f->light_line || (need.light_mean && !f->light_mean)) return TIR_ERR_ARG;
+    if (need.n_acomp && f->n_acomp != need.n_acomp) return TIR_ERR_UNSUPPORTED;
+    if (need.app_dim ? f->app_dim != need.app_dim : (f->app_dim < 1 || f->app_dim > 27)) return TIR_ERR_UNSUPPORTED;
+    if (need.index32 && !tir_app_index_ok(f)) return TIR_ERR_UNSUPPORTED;
+    if (need.feature_rows && (out_stride < f->app_dim || out_stride > need.stride_max)) return TIR_ERR_ARG;
+    return TIR_OK;
+}
+
+// The rows of a call: n >= 0, every pointer of `need` present when n > 0, every pointer of `aligned` 16-byte aligned; THE n == 0
+// return of the gather and decoder entries; then go() -- whatever the entry refuses only for a non-empty call, and the launch.
+template <typename Go>
+static inline int tir_with_rows(int64_t n, std::initializer_list<const void*> need, std::initializer_list<const void*> aligned, Go&& go) {
+    if (n < 0 || (n > 0 && tir_any_null(need)) || !tir_aligned16(aligned)) return TIR_ERR_ARG;
+    if (n == 0) return TIR_OK;
+    return go();
+}
+
+// the dynamic-LDS limit the appearance gathers and their backward raise their kernels to (all of a CU's LDS)
+constexpr int TIR_APP_LDS_LIMIT = 160 * 1024;
+
+// Workgroups of a persistent gather: one per `rows` records up to `cap`, a multiple of 8 under the partitioned XCD order.
+static inline unsigned tir_gather_blocks(int64_t n, int rows, int cap, int xcd_on) {
+    int64_t blocks = (n + rows - 1) / rows;
+    if (blocks > cap) blocks = cap;
+    if (xcd_on) blocks = (blocks + 7) / 8 * 8;
+    return (unsigned)blocks;
+}
+
+// Workgroups of a launch that carries n_jobs jobs: `total` split evenly, at least one and at most `units` (tiles, steps) per job.
+static inline unsigned tir_job_split(int64_t units, int total, int n_jobs) {
+    int per = total / n_jobs;
+    if (per < 1) per = 1;
+    if (units < per) per = (int)units;
+    return (unsigned)(per * n_jobs);
+}
+
+// One launch: the kernel's dynamic-LDS limit first where the entry raises it (lds_limit > 0), the launch, the runtime's verdict.
+template <typename... P, typename... A>
+static inline int tir_launch(void (*kernel)(P...), int lds_limit, dim3 grid, dim3 block, size_t lds, hipStream_t s, const A&... args) {
+    if (lds_limit > 0)
+        if (int rc = tir_allow_dynamic_lds(reinterpret_cast<const void*>(kernel), lds_limit)) return rc;
+    hipLaunchKernelGGL(kernel, grid, block, lds, s, args...);
+    TIR_CHECK_LAUNCH();
+    return TIR_OK;
+}
+
+// n_acomp -> C4 = n_acomp / 4 among the widths the caller lists (those its kernel family is instantiated for): fn(constant<C4>).
+template <int... C4S, typename Fn>
+static inline int tir_dispatch_c4(int n_acomp, Fn&& fn) {
+    int rc = TIR_ERR_UNSUPPORTED;
+    (void)((n_acomp == 4 * C4S && ((rc = fn(std::integral_constant<int, C4S>{})), true)) || ...);
+    return rc;
+}
+
+// The (RAD, INTR) variants of a gather family: both feature sets, radiance only, intrinsic only -- (false, false) is not built.
+// kernel_of(R, I) names the family's kernel for bool constants R, I.  lds_limit > 0 raises the dynamic-LDS limit of ALL THREE,
+// not only of the one returned: a graph capture relies on the eager warm-up pass having made exactly these calls.
+template <typename KernelOf>
+static inline auto tir_rad_intr_kernel(bool rad, bool intr, int lds_limit, int& rc, KernelOf&& kernel_of) {
+    const auto both = kernel_of(std::true_type{}, std::true_type{}), r = kernel_of(std::true_type{}, std::false_type{}),
+               i = kernel_of(std::false_type{}, std::true_type{});
+    rc = TIR_OK;
+    for (auto k : {both, r, i})
+        if (lds_limit > 0 && !rc) rc = tir_allow_dynamic_lds(reinterpret_cast<const void*>(k), lds_limit);
+    return rad && intr ? both : rad ? r : i;
 }
 
 // matMode / vecMode of the reference (models/tensorBase_rotated_lights.py:398-399)

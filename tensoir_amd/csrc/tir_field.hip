@@ -1171,20 +1171,19 @@ k_vm_app_h16(TirField f, TirFieldHalf fh, const float* __restrict__ xyz, const i
     }
 }
 
+// ---- host side of the appearance gathers.  Preconditions, launch geometry and the template dispatch are tir_common.hpp's
+// (tir_check_app_field, tir_with_rows, tir_gather_blocks, tir_dispatch_c4, tir_rad_intr_kernel, tir_launch).
+#define TIR_APP_ARGS *f, xyz, li, map, rad, intr, stride, idx_div, n, n_dev
+
 template <int C4>
 static int launch_app_bf16(const TirField* f, const float* xyz, const int32_t* li, const int32_t* map,
                            float* rad, float* intr, int stride, int idx_div, int64_t n, const int32_t* n_dev, hipStream_t s) {
     const int nx = (rad ? 1 : 0) + (intr ? 1 : 0);
     const size_t lds = (size_t)2 * 3 * 2 * 2 * 64 * 16 + (size_t)4 * nx * 16 * TIR_XS * sizeof(float);
-    int64_t blocks = (n + 63) / 64;
-    if (blocks > 2048) blocks = 2048;
     const int xcd_on = tir_xcd_mapping(f);
-    if (xcd_on) blocks = (blocks + 7) / 8 * 8;
-    dim3 g((unsigned)blocks), b(256);
-    if (rad && intr) hipLaunchKernelGGL((k_vm_app_bf16<C4, true, true>), g, b, lds, s, *f, xyz, li, map, rad, intr, stride, idx_div, n, n_dev, xcd_on);
-    else if (rad)    hipLaunchKernelGGL((k_vm_app_bf16<C4, true, false>), g, b, lds, s, *f, xyz, li, map, rad, intr, stride, idx_div, n, n_dev, xcd_on);
-    else             hipLaunchKernelGGL((k_vm_app_bf16<C4, false, true>), g, b, lds, s, *f, xyz, li, map, rad, intr, stride, idx_div, n, n_dev, xcd_on);
-    return TIR_OK;
+    int rc;
+    const auto k = tir_rad_intr_kernel(rad, intr, 0, rc, [](auto R, auto I) { return k_vm_app_bf16<C4, decltype(R)::value, decltype(I)::value>; });
+    return tir_launch(k, 0, dim3(tir_gather_blocks(n, 64, 2048, xcd_on)), dim3(256), lds, s, TIR_APP_ARGS, xcd_on);
 }
 
 // the half-split contraction (app_mfma_body HX) for the plain gather: radiance only, both, or intrinsic only
@@ -1195,106 +1194,72 @@ static int launch_app_hx(const TirField* f, const float* xyz, const int32_t* li,
     const int nx = (rad ? 1 : 0) + (intr ? 1 : 0);
     const int lt_rows = (rad && f->n_lights <= 16) ? f->n_lights : 0;
     const size_t lds = ((size_t)(2 * 3 * 2 * 2 * 64 * 16) / 4 + (size_t)(lt_rows + 1) * 3 * CA + 4 * (size_t)(nx * 2 * 16 * TIR_XHX * 2) / 4) * sizeof(float);
-    int64_t blocks = (n + 63) / 64;
-    if (blocks > 2048) blocks = 2048;
     const int xcd_on = tir_xcd_mapping(f);
-    if (xcd_on) blocks = (blocks + 7) / 8 * 8;
-    dim3 g((unsigned)blocks), b(256);
     const TirJitter jt{0.0f, 0ull, 0ull, nullptr, nullptr};
-    if (int rc = tir_allow_dynamic_lds(reinterpret_cast<const void*>(k_vm_app_mfma<C4, true, true, false, true>), 160 * 1024)) return rc;
-    if (int rc = tir_allow_dynamic_lds(reinterpret_cast<const void*>(k_vm_app_mfma<C4, true, false, false, true>), 160 * 1024)) return rc;
-    if (int rc = tir_allow_dynamic_lds(reinterpret_cast<const void*>(k_vm_app_mfma<C4, false, true, false, true>), 160 * 1024)) return rc;
-    if (rad && intr) hipLaunchKernelGGL((k_vm_app_mfma<C4, true, true, false, true>), g, b, lds, s, *f, xyz, li, map, rad, intr, stride, idx_div, n, n_dev, xcd_on, jt, lt_rows);
-    else if (rad)    hipLaunchKernelGGL((k_vm_app_mfma<C4, true, false, false, true>), g, b, lds, s, *f, xyz, li, map, rad, intr, stride, idx_div, n, n_dev, xcd_on, jt, lt_rows);
-    else             hipLaunchKernelGGL((k_vm_app_mfma<C4, false, true, false, true>), g, b, lds, s, *f, xyz, li, map, rad, intr, stride, idx_div, n, n_dev, xcd_on, jt, lt_rows);
-    return TIR_OK;
+    // (launch_app's refusal of lds > 160 KB is absent here: kept as found; the widths built, <= 48 components, need 70 KB at most)
+    int rc;
+    const auto k = tir_rad_intr_kernel(rad, intr, TIR_APP_LDS_LIMIT, rc,
+                                       [](auto R, auto I) { return k_vm_app_mfma<C4, decltype(R)::value, decltype(I)::value, false, true>; });
+    if (rc) return rc;
+    return tir_launch(k, 0, dim3(tir_gather_blocks(n, 64, 2048, xcd_on)), dim3(256), lds, s, TIR_APP_ARGS, xcd_on, jt, lt_rows);
 }
 
 template <int C4>
 static int launch_app(const TirField* f, const float* xyz, const int32_t* li, const int32_t* map,
                       float* rad, float* intr, int stride, int idx_div, int64_t n, const int32_t* n_dev, hipStream_t s, bool valu,
-                      const TirJitter& jt = TirJitter{0.0f, 0ull, 0ull, nullptr, nullptr}) {
+                      const TirJitter& jt) {
+    int rc;
     if (valu) {
-        dim3 g((unsigned)((n + 255) / 256)), b(256);
-        if (rad && intr) hipLaunchKernelGGL((k_vm_app_valu<C4, true, true>), g, b, 0, s, *f, xyz, li, map, rad, intr, stride, idx_div, n, n_dev);
-        else if (rad)    hipLaunchKernelGGL((k_vm_app_valu<C4, true, false>), g, b, 0, s, *f, xyz, li, map, rad, intr, stride, idx_div, n, n_dev);
-        else             hipLaunchKernelGGL((k_vm_app_valu<C4, false, true>), g, b, 0, s, *f, xyz, li, map, rad, intr, stride, idx_div, n, n_dev);
-        return TIR_OK;
+        const auto k = tir_rad_intr_kernel(rad, intr, 0, rc, [](auto R, auto I) { return k_vm_app_valu<C4, decltype(R)::value, decltype(I)::value>; });
+        return tir_launch(k, 0, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, TIR_APP_ARGS);
     }
     constexpr int CA = C4 * 4;
     const int nx = (rad ? 1 : 0) + (intr ? 1 : 0);
     const int lt_rows = (rad && f->n_lights <= 16) ? f->n_lights : 0;         // light_line rows staged in LDS (576 B each)
     const size_t lds = (size_t)(3 * CA * 32 + (lt_rows + 1) * 3 * CA + 4 * nx * CA * TIR_XLD) * sizeof(float);
-    int64_t blocks = (n + 63) / 64;
-    if (blocks > 2048) blocks = 2048;
     const int xcd_on = tir_xcd_mapping(f);
-    if (xcd_on) blocks = (blocks + 7) / 8 * 8;
-    dim3 g((unsigned)blocks), b(256);
-    if (lds > 160 * 1024) return TIR_ERR_UNSUPPORTED;
+    const dim3 g(tir_gather_blocks(n, 64, 2048, xcd_on)), b(256);
+    // kept as found; not known to be needed: the widths built stay below it (96 components, 16 light rows: 106 KB)
+    if (lds > (size_t)TIR_APP_LDS_LIMIT) return TIR_ERR_UNSUPPORTED;
     // > 64 KB only for unusually wide fields; harmless otherwise
-    if (int rc = tir_allow_dynamic_lds(reinterpret_cast<const void*>(k_vm_app_mfma<C4, true, true>), 160 * 1024)) return rc;
-    if (int rc = tir_allow_dynamic_lds(reinterpret_cast<const void*>(k_vm_app_mfma<C4, true, false>), 160 * 1024)) return rc;
-    if (int rc = tir_allow_dynamic_lds(reinterpret_cast<const void*>(k_vm_app_mfma<C4, false, true>), 160 * 1024)) return rc;
-    if (jt.scale != 0.0f) {
+    const auto k = tir_rad_intr_kernel(rad, intr, TIR_APP_LDS_LIMIT, rc,
+                                       [](auto R, auto I) { return k_vm_app_mfma<C4, decltype(R)::value, decltype(I)::value>; });
+    if (rc) return rc;
+    if (jt.scale != 0.0f) {                                                    // the jitter variant exists for the intrinsic feature alone
         if (rad || !intr) return TIR_ERR_ARG;
-        if (int rc = tir_allow_dynamic_lds(reinterpret_cast<const void*>(k_vm_app_mfma<C4, false, true, true>), 160 * 1024)) return rc;
-        hipLaunchKernelGGL((k_vm_app_mfma<C4, false, true, true>), g, b, lds, s, *f, xyz, li, map, rad, intr, stride, idx_div, n, n_dev, xcd_on, jt, lt_rows);
-        return TIR_OK;
+        return tir_launch(k_vm_app_mfma<C4, false, true, true>, TIR_APP_LDS_LIMIT, g, b, lds, s, TIR_APP_ARGS, xcd_on, jt, lt_rows);
     }
     if constexpr (C4 == 12) {
         if (rad && intr && f->n_lights == 1) {      // one light: one contraction feeds both features (app_mfma_body ONE)
             const size_t lds1 = (size_t)(3 * CA * 32 + 2 * 3 * CA + 4 * CA * TIR_XLD) * sizeof(float);
-            if (int rc = tir_allow_dynamic_lds(reinterpret_cast<const void*>(k_vm_app_mfma<C4, true, true, false, false, true>), 160 * 1024)) return rc;
-            hipLaunchKernelGGL((k_vm_app_mfma<C4, true, true, false, false, true>), g, b, lds1, s, *f, xyz, li, map, rad, intr, stride, idx_div, n, n_dev, xcd_on, jt, 1);
-            return TIR_OK;
+            return tir_launch(k_vm_app_mfma<C4, true, true, false, false, true>, TIR_APP_LDS_LIMIT, g, b, lds1, s, TIR_APP_ARGS, xcd_on, jt, 1);
         }
     }
-    if (rad && intr) hipLaunchKernelGGL((k_vm_app_mfma<C4, true, true>), g, b, lds, s, *f, xyz, li, map, rad, intr, stride, idx_div, n, n_dev, xcd_on, jt, lt_rows);
-    else if (rad)    hipLaunchKernelGGL((k_vm_app_mfma<C4, true, false>), g, b, lds, s, *f, xyz, li, map, rad, intr, stride, idx_div, n, n_dev, xcd_on, jt, lt_rows);
-    else             hipLaunchKernelGGL((k_vm_app_mfma<C4, false, true>), g, b, lds, s, *f, xyz, li, map, rad, intr, stride, idx_div, n, n_dev, xcd_on, jt, lt_rows);
-    return TIR_OK;
+    return tir_launch(k, 0, g, b, lds, s, TIR_APP_ARGS, xcd_on, jt, lt_rows);
 }
 
-static int app_fwd(const TirField* f, const float* xyz, const int32_t* light_idx, const int32_t* idx_map,
-                   float* rad_feat, float* int_feat, int32_t out_stride, int32_t idx_div, int64_t n, const int32_t* n_dev, void* stream,
-                   bool valu, bool split_bf16 = false, const TirJitter& jt = TirJitter{0.0f, 0ull, 0ull, nullptr, nullptr}) {
+enum AppContraction { APP_FP32, APP_VALU, APP_BF16X3, APP_HX };      // which kernel family of the plain gather an entry runs
+
+static int app_fwd(const TirField* f, const float* xyz, const int32_t* li, const int32_t* map, float* rad, float* intr,
+                   int32_t stride, int32_t idx_div, int64_t n, const int32_t* n_dev, void* stream, AppContraction how,
+                   const TirJitter& jt = TirJitter{0.0f, 0ull, 0ull, nullptr, nullptr}) {
     if (!f) return TIR_ERR_ARG;
-    for (int i = 0; i < 3; ++i)
-        if (f->grid[i] < 2 || !f->aplane[i] || !f->aline[i]) return TIR_ERR_ARG;
-    if (!f->basis_t || !f->light_mean || !f->light_line) return TIR_ERR_ARG;
-    if (f->app_dim < 1 || f->app_dim > 27) return TIR_ERR_UNSUPPORTED;
-    if (out_stride < f->app_dim || out_stride > 32) return TIR_ERR_ARG;
-    if (n < 0 || (n > 0 && !xyz) || (!rad_feat && !int_feat) || (rad_feat && !light_idx)) return TIR_ERR_ARG;
-    if (n == 0) return TIR_OK;
-    hipStream_t s = tir_stream(stream);
-    int rc;
-    if (split_bf16) {
-        switch (f->n_acomp) {
-            case 48: rc = launch_app_bf16<12>(f, xyz, light_idx, idx_map, rad_feat, int_feat, out_stride, idx_div, n, n_dev, s); break;
-            case 24: rc = launch_app_bf16<6>(f, xyz, light_idx, idx_map, rad_feat, int_feat, out_stride, idx_div, n, n_dev, s); break;
-            case 16: rc = launch_app_bf16<4>(f, xyz, light_idx, idx_map, rad_feat, int_feat, out_stride, idx_div, n, n_dev, s); break;
-            default: return TIR_ERR_UNSUPPORTED;
-        }
-        if (rc) return rc;
-        TIR_CHECK_LAUNCH();
-        return TIR_OK;
-    }
-    switch (f->n_acomp) {
-        case 48: rc = launch_app<12>(f, xyz, light_idx, idx_map, rad_feat, int_feat, out_stride, idx_div, n, n_dev, s, valu, jt); break;
-        case 24: rc = launch_app<6>(f, xyz, light_idx, idx_map, rad_feat, int_feat, out_stride, idx_div, n, n_dev, s, valu, jt); break;
-        case 16: rc = launch_app<4>(f, xyz, light_idx, idx_map, rad_feat, int_feat, out_stride, idx_div, n, n_dev, s, valu, jt); break;
-        case 96: rc = launch_app<24>(f, xyz, light_idx, idx_map, rad_feat, int_feat, out_stride, idx_div, n, n_dev, s, valu, jt); break;
-        default: return TIR_ERR_UNSUPPORTED;
-    }
-    if (rc) return rc;
-    TIR_CHECK_LAUNCH();
-    return TIR_OK;
+    if (int rc = tir_check_app_field(f, TirAppNeeds(), stride)) return rc;
+    if ((!rad && !intr) || (rad && !li)) return TIR_ERR_ARG;
+    return tir_with_rows(n, {xyz}, {}, [&] {
+        hipStream_t s = tir_stream(stream);
+        // 96 components per plane have the fp32 gathers only
+        if (how == APP_BF16X3) return tir_dispatch_c4<12, 6, 4>(f->n_acomp, [&](auto c4) { return launch_app_bf16<decltype(c4)::value>(f, xyz, li, map, rad, intr, stride, idx_div, n, n_dev, s); });
+        if (how == APP_HX) return tir_dispatch_c4<12, 6, 4>(f->n_acomp, [&](auto c4) { return launch_app_hx<decltype(c4)::value>(f, xyz, li, map, rad, intr, stride, idx_div, n, n_dev, s); });
+        return tir_dispatch_c4<12, 6, 4, 24>(f->n_acomp, [&](auto c4) { return launch_app<decltype(c4)::value>(f, xyz, li, map, rad, intr, stride, idx_div, n, n_dev, s, how == APP_VALU, jt); });
+    });
 }
+#undef TIR_APP_ARGS
 
 extern "C" int tir_vm_app_fwd(const TirField* f, const float* xyz, const int32_t* light_idx,
                               const int32_t* idx_map, float* rad_feat, float* int_feat, int32_t out_stride,
                               int32_t idx_div, int64_t n, const int32_t* n_dev, void* stream) {
-    return app_fwd(f, xyz, light_idx, idx_map, rad_feat, int_feat, out_stride, idx_div, n, n_dev, stream, false);
+    return app_fwd(f, xyz, light_idx, idx_map, rad_feat, int_feat, out_stride, idx_div, n, n_dev, stream, APP_FP32);
 }
 
 // Intrinsic feature of the JITTERED points xyz + scale * N(0,1) (models/tensorBase_rotated_lights.py:937-938) with the
@@ -1304,119 +1269,74 @@ extern "C" int tir_vm_app_jitter_fwd(const TirField* f, const float* xyz, int64_
                                      float* int_feat, int32_t out_stride, void* stream) {
     if (!xyz_out || !int_feat || scale == 0.0f) return TIR_ERR_ARG;
     TirJitter jt{scale, (unsigned long long)seed, (unsigned long long)offset, reinterpret_cast<const long long*>(rng_dev), xyz_out};
-    return app_fwd(f, xyz, nullptr, nullptr, nullptr, int_feat, out_stride, 0, n, n_dev, stream, false, false, jt);
+    return app_fwd(f, xyz, nullptr, nullptr, nullptr, int_feat, out_stride, 0, n, n_dev, stream, APP_FP32, jt);
 }
 
-static int app_primary_launch(const TirField* f, const float* xyz, const int32_t* light_idx, const int32_t* idx_map, float* rad_feat,
-                              float* int_feat, int32_t out_stride, int64_t n, const int32_t* n_dev, float scale, uint64_t seed,
-                              uint64_t offset, const int64_t* rng_state, float* xyz_out, float* int_feat_jit, void* stream, bool hx) {
-    constexpr int C4 = 12, CA = 48;
-    const int lt_rows = f->n_lights <= 16 ? f->n_lights : 0;
-    const size_t w_floats = hx ? (2 * 3 * 2 * 2 * 64 * 16) / 4 : 3 * CA * 32;
-    const size_t x_floats = hx ? (2 * 2 * 16 * TIR_XHX * 2) / 4 : 2 * CA * TIR_XLD;         // per wave, two feature sets
-    const size_t lds = (w_floats + (size_t)(lt_rows + 1) * 3 * CA + 4 * x_floats) * sizeof(float);
-    int64_t nb = (n + 63) / 64;
-    if (nb > 1024) nb = 1024;
-    nb = (nb + 7) / 8 * 8;                                   // both slices start at a multiple of 8 (XCD mapping)
-    const int xcd_on = tir_xcd_mapping(f);
-    TirJitter jt{scale, (unsigned long long)seed, (unsigned long long)offset, reinterpret_cast<const long long*>(rng_state), xyz_out};
-    if (f->n_lights == 1) {
-        // one light: light_mean is light_line[0], the record slice contracts once for both features (k_vm_app_primary_one);
-        // light_idx and idx_map are not read (every index clamps to row 0)
-        const size_t lds1 = (w_floats + (size_t)2 * 3 * CA + 4 * (x_floats / 2)) * sizeof(float);       // one feature set per wave
-        if (hx) {
-            if (int rc = tir_allow_dynamic_lds(reinterpret_cast<const void*>(k_vm_app_primary_one<C4, true>), 160 * 1024)) return rc;
-            hipLaunchKernelGGL((k_vm_app_primary_one<C4, true>), dim3((unsigned)(2 * nb)), dim3(256), lds1, tir_stream(stream), *f, xyz,
-                               rad_feat, int_feat, int_feat_jit, out_stride, n, n_dev, xcd_on, jt, (int)nb);
-        } else {
-            if (int rc = tir_allow_dynamic_lds(reinterpret_cast<const void*>(k_vm_app_primary_one<C4, false>), 160 * 1024)) return rc;
-            hipLaunchKernelGGL((k_vm_app_primary_one<C4, false>), dim3((unsigned)(2 * nb)), dim3(256), lds1, tir_stream(stream), *f, xyz,
-                               rad_feat, int_feat, int_feat_jit, out_stride, n, n_dev, xcd_on, jt, (int)nb);
+// tir_vm_app_fwd (both features) + tir_vm_app_jitter_fwd on the same points in one launch (48 appearance components); HX: the
+// basis_mat contraction on fp16 hi + lo operands (three products; app_mfma_body HX).
+template <bool HX>
+static int app_primary_fwd(const TirField* f, const float* xyz, const int32_t* light_idx, const int32_t* idx_map, float* rad_feat,
+                           float* int_feat, int32_t out_stride, int64_t n, const int32_t* n_dev, float scale, uint64_t seed,
+                           uint64_t offset, const int64_t* rng_state, float* xyz_out, float* int_feat_jit, void* stream) {
+    if (!f || !rad_feat || !int_feat || !xyz_out || !int_feat_jit || !light_idx || scale == 0.0f) return TIR_ERR_ARG;
+    if (int rc = tir_check_app_field(f, TirAppNeeds().width(48), out_stride)) return rc;
+    return tir_with_rows(n, {xyz}, {}, [&] {
+        constexpr int C4 = 12, CA = 48;
+        const int lt_rows = f->n_lights <= 16 ? f->n_lights : 0;
+        const size_t w_floats = HX ? (2 * 3 * 2 * 2 * 64 * 16) / 4 : 3 * CA * 32;
+        const size_t x_floats = HX ? (2 * 2 * 16 * TIR_XHX * 2) / 4 : 2 * CA * TIR_XLD;         // per wave, two feature sets
+        // two slices of nb workgroups; both start at a multiple of 8 (XCD mapping) whether or not the mapping is on
+        const int nb = (int)tir_gather_blocks(n, 64, 1024, 1);
+        const dim3 g(2 * nb), b(256);
+        const int xcd_on = tir_xcd_mapping(f);
+        const TirJitter jt{scale, (unsigned long long)seed, (unsigned long long)offset, reinterpret_cast<const long long*>(rng_state), xyz_out};
+        if (f->n_lights == 1) {
+            // one light: light_mean is light_line[0], the record slice contracts once for both features (k_vm_app_primary_one);
+            // light_idx and idx_map are not read (every index clamps to row 0)
+            const size_t lds1 = (w_floats + (size_t)2 * 3 * CA + 4 * (x_floats / 2)) * sizeof(float);       // one feature set per wave
+            return tir_launch(k_vm_app_primary_one<C4, HX>, TIR_APP_LDS_LIMIT, g, b, lds1, tir_stream(stream), *f, xyz, rad_feat, int_feat,
+                              int_feat_jit, out_stride, n, n_dev, xcd_on, jt, nb);
         }
-        TIR_CHECK_LAUNCH();
-        return TIR_OK;
-    }
-    if (hx) {
-        if (int rc = tir_allow_dynamic_lds(reinterpret_cast<const void*>(k_vm_app_primary<C4, true>), 160 * 1024)) return rc;
-        hipLaunchKernelGGL((k_vm_app_primary<C4, true>), dim3((unsigned)(2 * nb)), dim3(256), lds, tir_stream(stream), *f, xyz, light_idx, idx_map,
-                           rad_feat, int_feat, int_feat_jit, out_stride, n, n_dev, xcd_on, jt, lt_rows, (int)nb);
-    } else {
-        if (int rc = tir_allow_dynamic_lds(reinterpret_cast<const void*>(k_vm_app_primary<C4, false>), 160 * 1024)) return rc;
-        hipLaunchKernelGGL((k_vm_app_primary<C4, false>), dim3((unsigned)(2 * nb)), dim3(256), lds, tir_stream(stream), *f, xyz, light_idx, idx_map,
-                           rad_feat, int_feat, int_feat_jit, out_stride, n, n_dev, xcd_on, jt, lt_rows, (int)nb);
-    }
-    TIR_CHECK_LAUNCH();
-    return TIR_OK;
+        const size_t lds = (w_floats + (size_t)(lt_rows + 1) * 3 * CA + 4 * x_floats) * sizeof(float);
+        return tir_launch(k_vm_app_primary<C4, HX>, TIR_APP_LDS_LIMIT, g, b, lds, tir_stream(stream), *f, xyz, light_idx, idx_map, rad_feat,
+                          int_feat, int_feat_jit, out_stride, n, n_dev, xcd_on, jt, lt_rows, nb);
+    });
 }
 
-// tir_vm_app_fwd (both features) + tir_vm_app_jitter_fwd on the same points in one launch (48 appearance components).
+// the fp32 contraction: the default primary stage (ops.APP_CONTRACTION)
 extern "C" int tir_vm_app_primary_fwd(const TirField* f, const float* xyz, const int32_t* light_idx, const int32_t* idx_map,
                                       float* rad_feat, float* int_feat, int32_t out_stride, int64_t n, const int32_t* n_dev,
                                       float scale, uint64_t seed, uint64_t offset, const int64_t* rng_state, float* xyz_out,
                                       float* int_feat_jit, void* stream) {
-    if (!f || !rad_feat || !int_feat || !xyz_out || !int_feat_jit || !light_idx || scale == 0.0f) return TIR_ERR_ARG;
-    for (int i = 0; i < 3; ++i)
-        if (f->grid[i] < 2 || !f->aplane[i] || !f->aline[i]) return TIR_ERR_ARG;
-    if (!f->basis_t || !f->light_mean || !f->light_line) return TIR_ERR_ARG;
-    if (f->n_acomp != 48 || f->app_dim < 1 || f->app_dim > 27) return TIR_ERR_UNSUPPORTED;
-    if (out_stride < f->app_dim || out_stride > 32) return TIR_ERR_ARG;
-    if (n < 0 || (n > 0 && !xyz)) return TIR_ERR_ARG;
-    if (n == 0) return TIR_OK;
-    return app_primary_launch(f, xyz, light_idx, idx_map, rad_feat, int_feat, out_stride, n, n_dev, scale, seed, offset, rng_state, xyz_out,
-                              int_feat_jit, stream, false);
+    return app_primary_fwd<false>(f, xyz, light_idx, idx_map, rad_feat, int_feat, out_stride, n, n_dev, scale, seed, offset, rng_state,
+                                  xyz_out, int_feat_jit, stream);
 }
 
-// ... with the basis_mat contraction on fp16 hi + lo operands (three products; app_mfma_body HX): the default primary stage of
-// inference under the split-bf16 decoders
+// the half-split contraction: an option of ops.APP_CONTRACTION, not the default
 extern "C" int tir_vm_app_primary_x3_fwd(const TirField* f, const float* xyz, const int32_t* light_idx, const int32_t* idx_map,
                                          float* rad_feat, float* int_feat, int32_t out_stride, int64_t n, const int32_t* n_dev,
                                          float scale, uint64_t seed, uint64_t offset, const int64_t* rng_state, float* xyz_out,
                                          float* int_feat_jit, void* stream) {
-    if (!f || !rad_feat || !int_feat || !xyz_out || !int_feat_jit || !light_idx || scale == 0.0f) return TIR_ERR_ARG;
-    for (int i = 0; i < 3; ++i)
-        if (f->grid[i] < 2 || !f->aplane[i] || !f->aline[i]) return TIR_ERR_ARG;
-    if (!f->basis_t || !f->light_mean || !f->light_line) return TIR_ERR_ARG;
-    if (f->n_acomp != 48 || f->app_dim < 1 || f->app_dim > 27) return TIR_ERR_UNSUPPORTED;
-    if (out_stride < f->app_dim || out_stride > 32) return TIR_ERR_ARG;
-    if (n < 0 || (n > 0 && !xyz)) return TIR_ERR_ARG;
-    if (n == 0) return TIR_OK;
-    return app_primary_launch(f, xyz, light_idx, idx_map, rad_feat, int_feat, out_stride, n, n_dev, scale, seed, offset, rng_state, xyz_out,
-                              int_feat_jit, stream, true);
+    return app_primary_fwd<true>(f, xyz, light_idx, idx_map, rad_feat, int_feat, out_stride, n, n_dev, scale, seed, offset, rng_state,
+                                 xyz_out, int_feat_jit, stream);
 }
 
 extern "C" int tir_vm_app_fwd_x3(const TirField* f, const float* xyz, const int32_t* light_idx,
                                  const int32_t* idx_map, float* rad_feat, float* int_feat, int32_t out_stride,
                                  int32_t idx_div, int64_t n, const int32_t* n_dev, void* stream) {
-    if (!f) return TIR_ERR_ARG;
-    for (int i = 0; i < 3; ++i)
-        if (f->grid[i] < 2 || !f->aplane[i] || !f->aline[i]) return TIR_ERR_ARG;
-    if (!f->basis_t || !f->light_mean || !f->light_line) return TIR_ERR_ARG;
-    if (f->app_dim < 1 || f->app_dim > 27) return TIR_ERR_UNSUPPORTED;
-    if (out_stride < f->app_dim || out_stride > 32) return TIR_ERR_ARG;
-    if (n < 0 || (n > 0 && !xyz) || (!rad_feat && !int_feat) || (rad_feat && !light_idx)) return TIR_ERR_ARG;
-    if (n == 0) return TIR_OK;
-    int rc;
-    switch (f->n_acomp) {
-        case 48: rc = launch_app_hx<12>(f, xyz, light_idx, idx_map, rad_feat, int_feat, out_stride, idx_div, n, n_dev, tir_stream(stream)); break;
-        case 24: rc = launch_app_hx<6>(f, xyz, light_idx, idx_map, rad_feat, int_feat, out_stride, idx_div, n, n_dev, tir_stream(stream)); break;
-        case 16: rc = launch_app_hx<4>(f, xyz, light_idx, idx_map, rad_feat, int_feat, out_stride, idx_div, n, n_dev, tir_stream(stream)); break;
-        default: return TIR_ERR_UNSUPPORTED;
-    }
-    if (rc) return rc;
-    TIR_CHECK_LAUNCH();
-    return TIR_OK;
+    return app_fwd(f, xyz, light_idx, idx_map, rad_feat, int_feat, out_stride, idx_div, n, n_dev, stream, APP_HX);
 }
 
 extern "C" int tir_vm_app_fwd_valu(const TirField* f, const float* xyz, const int32_t* light_idx,
                                    const int32_t* idx_map, float* rad_feat, float* int_feat, int32_t out_stride,
                                    int32_t idx_div, int64_t n, const int32_t* n_dev, void* stream) {
-    return app_fwd(f, xyz, light_idx, idx_map, rad_feat, int_feat, out_stride, idx_div, n, n_dev, stream, true);
+    return app_fwd(f, xyz, light_idx, idx_map, rad_feat, int_feat, out_stride, idx_div, n, n_dev, stream, APP_VALU);
 }
 
 extern "C" int tir_vm_app_fwd_bf16x3(const TirField* f, const float* xyz, const int32_t* light_idx,
                                      const int32_t* idx_map, float* rad_feat, float* int_feat, int32_t out_stride,
                                      int32_t idx_div, int64_t n, const int32_t* n_dev, void* stream) {
-    return app_fwd(f, xyz, light_idx, idx_map, rad_feat, int_feat, out_stride, idx_div, n, n_dev, stream, false, true);
+    return app_fwd(f, xyz, light_idx, idx_map, rad_feat, int_feat, out_stride, idx_div, n, n_dev, stream, APP_BF16X3);
 }
 
 // fp32 -> fp16 copies of up to 8 tables in one launch (same element order): the shadow planes / lines of tir_vm_app_fwd_h16
@@ -1455,22 +1375,12 @@ extern "C" int tir_vm_app_fwd_h16(const TirField* f, const TirFieldHalf* fh, con
                                   const int32_t* idx_map, float* rad_feat, int32_t out_stride, int32_t idx_div, int64_t n,
                                   const int32_t* n_dev, void* stream) {
     if (!f || !fh) return TIR_ERR_ARG;
-    for (int i = 0; i < 3; ++i)
-        if (f->grid[i] < 2 || !fh->aplane[i] || !fh->aline[i] || reinterpret_cast<uintptr_t>(fh->aplane[i]) % 16 != 0 ||
-            reinterpret_cast<uintptr_t>(fh->aline[i]) % 16 != 0) return TIR_ERR_ARG;
-    if (!f->basis_t || !f->light_mean || !f->light_line) return TIR_ERR_ARG;
-    if (f->n_acomp != 48 || f->app_dim < 1 || f->app_dim > 27 || !tir_app_index_ok(f)) return TIR_ERR_UNSUPPORTED;
-    if (out_stride < f->app_dim || out_stride > 32) return TIR_ERR_ARG;
-    if (n < 0 || (n > 0 && (!xyz || !rad_feat || !light_idx))) return TIR_ERR_ARG;
-    if (n == 0) return TIR_OK;
-    const int lt_rows = f->n_lights <= 16 ? f->n_lights : 0;
-    const size_t lds = (size_t)(3 * 3 * 2 * 32) * 16 + (size_t)(lt_rows + 1) * 144 * sizeof(float) + (size_t)4 * 32 * TIR_XH * 2;
-    int64_t blocks = (n + 127) / 128;
-    if (blocks > 2048) blocks = 2048;
-    const int xcd_on = tir_xcd_mapping(f);
-    if (xcd_on) blocks = (blocks + 7) / 8 * 8;
-    hipLaunchKernelGGL(k_vm_app_h16, dim3((unsigned)blocks), dim3(256), lds, tir_stream(stream), *f, *fh, xyz, light_idx, idx_map,
-                       rad_feat, out_stride, idx_div, n, n_dev, xcd_on, lt_rows);
-    TIR_CHECK_LAUNCH();
-    return TIR_OK;
+    if (int rc = tir_check_app_field(f, TirAppNeeds().fp16_tables(fh).aligned().element_index32().width(48), out_stride)) return rc;
+    return tir_with_rows(n, {xyz, rad_feat, light_idx}, {}, [&] {
+        const int lt_rows = f->n_lights <= 16 ? f->n_lights : 0;
+        const size_t lds = (size_t)(3 * 3 * 2 * 32) * 16 + (size_t)(lt_rows + 1) * 144 * sizeof(float) + (size_t)4 * 32 * TIR_XH * 2;
+        const int xcd_on = tir_xcd_mapping(f);
+        return tir_launch(k_vm_app_h16, 0, dim3(tir_gather_blocks(n, 128, 2048, xcd_on)), dim3(256), lds, tir_stream(stream), *f, *fh, xyz,
+                          light_idx, idx_map, rad_feat, out_stride, idx_div, n, n_dev, xcd_on, lt_rows);
+    });
 }

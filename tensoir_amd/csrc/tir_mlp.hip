@@ -2434,136 +2434,155 @@ k_mlp_wgrad_lds(TirWgradJobs jobs, int fstride, int64_t n) {
     }
 }
 
+// ---- host side of the decoders.  The shared pieces (tir_with_rows: THE n == 0 return, tir_check_app_field, tir_job_split,
+// tir_launch) are tir_common.hpp's; the decoder's own preconditions and launch formulas follow, each stated once.
+using PtrList = std::initializer_list<const void*>;
+
+bool mlp_shape_built(int feat_dim, int pe, int hidden, int out_dim) {
+    return feat_dim == F && pe == PE && hidden == HID && out_dim >= 1 && out_dim <= 4;
+}
+
 int check_mlp(const TirMlp* m) {
     if (!m || !m->packed) return TIR_ERR_ARG;
-    if (m->feat_dim != F || m->pe != PE || m->hidden != HID || m->out_dim < 1 || m->out_dim > 4)
-        return TIR_ERR_UNSUPPORTED;
-    return TIR_OK;
+    return mlp_shape_built(m->feat_dim, m->pe, m->hidden, m->out_dim) ? TIR_OK : TIR_ERR_UNSUPPORTED;
 }
+
+// "Decoder rows": a descriptor of the built shape, rows of at least F floats, `always` present even for an empty call, then
+// tir_with_rows: n >= 0, `need` present when n > 0, `aligned` 16-byte aligned, nothing to do for n == 0, else go().
+template <typename Go>
+int with_decoder_rows(const TirMlp* m, int64_t n, int32_t feat_stride, PtrList always, PtrList need, PtrList aligned, Go&& go) {
+    if (int rc = check_mlp(m)) return rc;
+    if (feat_stride < F || tir_any_null(always)) return TIR_ERR_ARG;
+    return tir_with_rows(n, need, aligned, go);
+}
+
+// Workgroups of a persistent decoder launch: one per tile of `rows` rows, up to 256 (one per CU) or the launch option
+// TirMlp::tune_grid.  The fp32-operand entries (tir_mlp_fwd, tir_mlp_train_fwd) and the single-job backward entries pass
+// NO_TUNE_GRID: they never read the option (kept as found; not known to be needed).
+constexpr int NO_TUNE_GRID = 0;
+unsigned decoder_grid(int64_t n, int rows, int tune_grid) {
+    const int64_t tiles = (n + rows - 1) / rows;
+    const int grid_max = tune_grid > 0 ? tune_grid : 256;
+    return (unsigned)(tiles < grid_max ? tiles : grid_max);
+}
+
+// 16-byte aligned rows of >= 28 floats take the dwordx4 row loads (the VEC kernels)
+bool stride_vec(int32_t feat_stride) { return feat_stride % 4 == 0 && feat_stride >= F + 1; }
+bool rows_vec(const float* feat, int32_t feat_stride) { return stride_vec(feat_stride) && tir_aligned16({feat}); }
+
+// the fused entries index records and rays with 32-bit arithmetic in the kernel
+bool fused_index_ok(int64_t n, int32_t idx_div, int32_t aux_mod) { return n < (int64_t)1 << 31 && idx_div >= 0 && aux_mod >= 0; }
 
 }  // namespace
 
 extern "C" int64_t tir_mlp_packed_floats(int32_t feat_dim, int32_t pe, int32_t hidden, int32_t out_dim) {
-    if (feat_dim != F || pe != PE || hidden != HID || out_dim < 1 || out_dim > 4) return TIR_ERR_UNSUPPORTED;
-    return TOTAL_FLOATS;
+    return mlp_shape_built(feat_dim, pe, hidden, out_dim) ? (int64_t)TOTAL_FLOATS : (int64_t)TIR_ERR_UNSUPPORTED;
 }
 
 extern "C" int tir_pack_mlp(const float* w0, const float* b0, const float* w1, const float* b1,
                             const float* w2, const float* b2, int32_t feat_dim, int32_t pe, int32_t hidden,
                             int32_t out_dim, float* packed, void* stream) {
-    if (!w0 || !b0 || !w1 || !b1 || !w2 || !b2 || !packed) return TIR_ERR_ARG;
-    if (feat_dim != F || pe != PE || hidden != HID || out_dim < 1 || out_dim > 4) return TIR_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(k_pack_mlp, dim3((TOTAL_FLOATS + 255) / 256), dim3(256), 0, tir_stream(stream),
-                       w0, b0, w1, b1, w2, b2, out_dim, packed);
-    TIR_CHECK_LAUNCH();
-    return TIR_OK;
+    if (tir_any_null({w0, b0, w1, b1, w2, b2, packed})) return TIR_ERR_ARG;
+    if (!mlp_shape_built(feat_dim, pe, hidden, out_dim)) return TIR_ERR_UNSUPPORTED;
+    return tir_launch(k_pack_mlp, 0, dim3((TOTAL_FLOATS + 255) / 256), dim3(256), 0, tir_stream(stream), w0, b0, w1, b1, w2, b2, out_dim,
+                      packed);
+}
+
+#define TIR_MLP_ARGS m->packed, feat, feat_stride, aux, aux_map, aux_mod, out, n, n_dev, m->out_dim, m->act
+
+// the fp32-operand decoder; SAVE: the hidden activations h1, h2 are kept for the backward pass (a non-SAVE entry passes null)
+template <bool SAVE>
+static int mlp_fwd(const TirMlp* m, const float* feat, int32_t feat_stride, const float* aux, const int32_t* aux_map, int32_t aux_mod,
+                   float* out, float* h1, float* h2, int64_t n, const int32_t* n_dev, void* stream) {
+    const auto go = [&] {
+        const size_t lds = (size_t)MFMA_FLOATS * sizeof(float);
+        return tir_launch(k_mlp_mfma<SAVE>, (int)lds, dim3(decoder_grid(n, 256, NO_TUNE_GRID)), dim3(512), lds, tir_stream(stream),
+                          TIR_MLP_ARGS, h1, h2);
+    };
+    if constexpr (SAVE) return with_decoder_rows(m, n, feat_stride, {}, {feat, aux, out, h1, h2}, {}, go);
+    else return with_decoder_rows(m, n, feat_stride, {}, {feat, aux, out}, {}, go);
 }
 
 extern "C" int tir_mlp_fwd(const TirMlp* m, const float* feat, int32_t feat_stride, const float* aux, const int32_t* aux_map, int32_t aux_mod,
                            float* out, int64_t n, const int32_t* n_dev, void* stream) {
-    int rc = check_mlp(m);
-    if (rc) return rc;
-    if (n < 0 || feat_stride < F || (n > 0 && (!feat || !aux || !out))) return TIR_ERR_ARG;
-    if (n == 0) return TIR_OK;
-    const size_t lds = (size_t)MFMA_FLOATS * sizeof(float);
-    if (int rc = tir_allow_dynamic_lds(reinterpret_cast<const void*>(k_mlp_mfma<false>), (int)lds)) return rc;
-    int64_t tiles = (n + 255) / 256;
-    unsigned grid = (unsigned)(tiles < 256 ? tiles : 256);
-    hipLaunchKernelGGL(k_mlp_mfma<false>, dim3(grid), dim3(512), lds, tir_stream(stream), m->packed, feat, feat_stride, aux,
-                       aux_map, aux_mod, out, n, n_dev, m->out_dim, m->act, (float*)nullptr, (float*)nullptr);
-    TIR_CHECK_LAUNCH();
-    return TIR_OK;
+    return mlp_fwd<false>(m, feat, feat_stride, aux, aux_map, aux_mod, out, nullptr, nullptr, n, n_dev, stream);
 }
 
 extern "C" int tir_mlp_train_fwd(const TirMlp* m, const float* feat, int32_t feat_stride, const float* aux,
                                  const int32_t* aux_map, int32_t aux_mod, float* out, float* h1, float* h2,
                                  int64_t n, const int32_t* n_dev, void* stream) {
-    int rc = check_mlp(m);
-    if (rc) return rc;
-    if (n < 0 || feat_stride < F || (n > 0 && (!feat || !aux || !out || !h1 || !h2))) return TIR_ERR_ARG;
-    if (n == 0) return TIR_OK;
-    const size_t lds = (size_t)MFMA_FLOATS * sizeof(float);
-    if (int rc = tir_allow_dynamic_lds(reinterpret_cast<const void*>(k_mlp_mfma<true>), (int)lds)) return rc;
-    int64_t tiles = (n + 255) / 256;
-    unsigned grid = (unsigned)(tiles < 256 ? tiles : 256);
-    hipLaunchKernelGGL(k_mlp_mfma<true>, dim3(grid), dim3(512), lds, tir_stream(stream), m->packed, feat, feat_stride, aux,
-                       aux_map, aux_mod, out, n, n_dev, m->out_dim, m->act, h1, h2);
-    TIR_CHECK_LAUNCH();
-    return TIR_OK;
+    return mlp_fwd<true>(m, feat, feat_stride, aux, aux_map, aux_mod, out, h1, h2, n, n_dev, stream);
 }
 
-template <int NPROD, bool VEC, bool SAVE>
-static int launch_bf16_v(const TirMlp* m, const float* feat, int32_t feat_stride, const float* aux, const int32_t* aux_map, int32_t aux_mod,
-                         float* out, int64_t n, const int32_t* n_dev, void* stream, float* h1 = nullptr, float* h2 = nullptr) {
-    const size_t lds = (size_t)BF_BYTES;
-    if (int rc = tir_allow_dynamic_lds(reinterpret_cast<const void*>(k_mlp_bf16<NPROD, VEC, SAVE>), (int)lds)) return rc;
-    int64_t tiles = (n + 255) / 256;
-    const int grid_max = m->tune_grid > 0 ? m->tune_grid : 256;           // launch option carried by the descriptor
-    unsigned grid = (unsigned)(tiles < grid_max ? tiles : grid_max);
-    hipLaunchKernelGGL((k_mlp_bf16<NPROD, VEC, SAVE>), dim3(grid), dim3(512), lds, tir_stream(stream), m->packed, feat, feat_stride, aux,
-                       aux_map, aux_mod, out, n, n_dev, m->out_dim, m->act, h1, h2);
-    TIR_CHECK_LAUNCH();
-    return TIR_OK;
-}
-
-template <int NPROD>
-static int launch_bf16(const TirMlp* m, const float* feat, int32_t feat_stride, const float* aux, const int32_t* aux_map, int32_t aux_mod,
-                       float* out, int64_t n, const int32_t* n_dev, void* stream) {
-    int rc = check_mlp(m);
-    if (rc) return rc;
-    if (n < 0 || feat_stride < F || (n > 0 && (!feat || !aux || !out))) return TIR_ERR_ARG;
-    if (n == 0) return TIR_OK;
-    // 16-byte aligned rows of >= 28 floats take the dwordx4 row loads
-    const bool vec = (feat_stride % 4 == 0) && feat_stride >= F + 1 && (reinterpret_cast<uintptr_t>(feat) % 16 == 0);
-    return vec ? launch_bf16_v<NPROD, true, false>(m, feat, feat_stride, aux, aux_map, aux_mod, out, n, n_dev, stream)
-               : launch_bf16_v<NPROD, false, false>(m, feat, feat_stride, aux, aux_map, aux_mod, out, n, n_dev, stream);
+// the bf16-operand decoders: NPROD = 1 (plain bf16) or 3 (split-bf16 hi + lo) products per MFMA step
+template <int NPROD, bool SAVE>
+static int mlp_fwd_bf16(const TirMlp* m, const float* feat, int32_t feat_stride, const float* aux, const int32_t* aux_map, int32_t aux_mod,
+                        float* out, float* h1, float* h2, int64_t n, const int32_t* n_dev, void* stream) {
+    const auto go = [&] {
+        const dim3 g(decoder_grid(n, 256, m->tune_grid)), b(512);
+        hipStream_t s = tir_stream(stream);
+        return rows_vec(feat, feat_stride) ? tir_launch(k_mlp_bf16<NPROD, true, SAVE>, BF_BYTES, g, b, BF_BYTES, s, TIR_MLP_ARGS, h1, h2)
+                                           : tir_launch(k_mlp_bf16<NPROD, false, SAVE>, BF_BYTES, g, b, BF_BYTES, s, TIR_MLP_ARGS, h1, h2);
+    };
+    if constexpr (SAVE) return with_decoder_rows(m, n, feat_stride, {}, {feat, aux, out, h1, h2}, {}, go);
+    else return with_decoder_rows(m, n, feat_stride, {}, {feat, aux, out}, {}, go);
 }
 
 extern "C" int tir_mlp_train_fwd_bf16x3(const TirMlp* m, const float* feat, int32_t feat_stride, const float* aux,
                                         const int32_t* aux_map, int32_t aux_mod, float* out, float* h1, float* h2,
                                         int64_t n, const int32_t* n_dev, void* stream) {
-    int rc = check_mlp(m);
-    if (rc) return rc;
-    if (n < 0 || feat_stride < F || (n > 0 && (!feat || !aux || !out || !h1 || !h2))) return TIR_ERR_ARG;
-    if (n == 0) return TIR_OK;
-    const bool vec = (feat_stride % 4 == 0) && feat_stride >= F + 1 && (reinterpret_cast<uintptr_t>(feat) % 16 == 0);
-    return vec ? launch_bf16_v<3, true, true>(m, feat, feat_stride, aux, aux_map, aux_mod, out, n, n_dev, stream, h1, h2)
-               : launch_bf16_v<3, false, true>(m, feat, feat_stride, aux, aux_map, aux_mod, out, n, n_dev, stream, h1, h2);
+    return mlp_fwd_bf16<3, true>(m, feat, feat_stride, aux, aux_map, aux_mod, out, h1, h2, n, n_dev, stream);
 }
 
 extern "C" int tir_mlp_fwd_bf16x3(const TirMlp* m, const float* feat, int32_t feat_stride, const float* aux, const int32_t* aux_map, int32_t aux_mod,
                                   float* out, int64_t n, const int32_t* n_dev, void* stream) {
-    return launch_bf16<3>(m, feat, feat_stride, aux, aux_map, aux_mod, out, n, n_dev, stream);
+    return mlp_fwd_bf16<3, false>(m, feat, feat_stride, aux, aux_map, aux_mod, out, nullptr, nullptr, n, n_dev, stream);
 }
 
+extern "C" int tir_mlp_fwd_bf16(const TirMlp* m, const float* feat, int32_t feat_stride, const float* aux, const int32_t* aux_map, int32_t aux_mod,
+                                float* out, int64_t n, const int32_t* n_dev, void* stream) {
+    return mlp_fwd_bf16<1, false>(m, feat, feat_stride, aux, aux_map, aux_mod, out, nullptr, nullptr, n, n_dev, stream);
+}
+
+extern "C" int tir_mlp_fwd_valu(const TirMlp* m, const float* feat, int32_t feat_stride, const float* aux, const int32_t* aux_map, int32_t aux_mod,
+                                float* out, int64_t n, const int32_t* n_dev, void* stream) {
+    return with_decoder_rows(m, n, feat_stride, {}, {feat, aux, out}, {}, [&] {
+        return tir_launch(k_mlp_valu, 0, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, tir_stream(stream), TIR_MLP_ARGS);
+    });
+}
+#undef TIR_MLP_ARGS
+
+extern "C" int tir_mlp_inputs(const TirMlp* m, const float* feat, int32_t feat_stride, const float* aux,
+                              const int32_t* aux_map, int32_t aux_mod, float* x, int64_t n, void* stream) {
+    return with_decoder_rows(m, n, feat_stride, {}, {feat, aux, x}, {}, [&] {
+        return tir_launch(k_mlp_inputs, 0, dim3((unsigned)((n + 7) / 8)), dim3(8 * (XPAD / 4)), 0, tir_stream(stream), feat, feat_stride, aux,
+                          aux_map, aux_mod, x, n);
+    });
+}
+
+// up to 4 decoders over the same n rows in one launch.  Per job, in this order: the descriptor, the row pointers, the alignment;
+// the n == 0 return only after every job was looked at (the per-job codes interleave, so tir_with_rows does not apply).
 template <bool SAVE>
 static int launch_multi(const TirMlp* const* mlps, const float* const* feats, int32_t feat_stride, const float* const* auxs,
                         const int32_t* const* aux_maps, float* const* outs, float* const* h1s, float* const* h2s,
                         int32_t n_jobs, int64_t n, const int32_t* n_dev, void* stream, const float* const* tables = nullptr) {
-    if (n_jobs < 1 || n_jobs > 4 || !mlps || !feats || !auxs || !outs || n < 0) return TIR_ERR_ARG;
+    if (n_jobs < 1 || n_jobs > 4 || tir_any_null({mlps, feats, auxs, outs}) || n < 0) return TIR_ERR_ARG;
     if (SAVE && (!h1s || !h2s)) return TIR_ERR_ARG;
-    if (feat_stride % 4 != 0 || feat_stride < F + 1) return TIR_ERR_ARG;          // rows must take the dwordx4 loads
+    if (!stride_vec(feat_stride)) return TIR_ERR_ARG;                            // rows must take the dwordx4 loads
     TirMlpJobs jobs;
     jobs.n_jobs = n_jobs;
     for (int i = 0; i < n_jobs; ++i) {
-        int rc = check_mlp(mlps[i]);
-        if (rc) return rc;
+        if (int rc = check_mlp(mlps[i])) return rc;
         const float* tab = (!SAVE && tables) ? tables[i] : nullptr;
         if (n > 0 && (!feats[i] || (!auxs[i] && !tab) || !outs[i])) return TIR_ERR_ARG;
         if (SAVE && n > 0 && (!h1s[i] || !h2s[i])) return TIR_ERR_ARG;
-        if (reinterpret_cast<uintptr_t>(feats[i]) % 16 != 0 || reinterpret_cast<uintptr_t>(tab) % 16 != 0) return TIR_ERR_ARG;
+        if (!tir_aligned16({feats[i], tab})) return TIR_ERR_ARG;
         jobs.j[i] = TirMlpJob{mlps[i]->packed, feats[i], auxs[i], aux_maps ? aux_maps[i] : nullptr, outs[i], mlps[i]->out_dim,
                               mlps[i]->act, SAVE ? h1s[i] : nullptr, SAVE ? h2s[i] : nullptr, tab};
     }
     if (n == 0) return TIR_OK;
-    if (int rc = tir_allow_dynamic_lds(reinterpret_cast<const void*>(k_mlp_bf16_multi<3, SAVE>), (int)BF_BYTES)) return rc;
-    const int64_t tiles = (n + 255) / 256;
-    int per = 256 / n_jobs;
-    if (tiles < per) per = (int)tiles;
-    hipLaunchKernelGGL((k_mlp_bf16_multi<3, SAVE>), dim3((unsigned)(per * n_jobs)), dim3(512), (size_t)BF_BYTES, tir_stream(stream),
-                       jobs, feat_stride, n, n_dev);
-    TIR_CHECK_LAUNCH();
-    return TIR_OK;
+    return tir_launch(k_mlp_bf16_multi<3, SAVE>, BF_BYTES, dim3(tir_job_split((n + 255) / 256, 256, n_jobs)), dim3(512), (size_t)BF_BYTES,
+                      tir_stream(stream), jobs, feat_stride, n, n_dev);
 }
 
 extern "C" int tir_mlp_fwd_multi_bf16x3(const TirMlp* const* mlps, const float* const* feats, int32_t feat_stride,
@@ -2579,136 +2598,6 @@ extern "C" int tir_mlp_fwd_multi_auxtab_bf16x3(const TirMlp* const* mlps, const 
     return launch_multi<false>(mlps, feats, feat_stride, auxs, aux_maps, outs, nullptr, nullptr, n_jobs, n, n_dev, stream, tables);
 }
 
-extern "C" int tir_mlp_aux_table(const TirMlp* m, const float* aux, int64_t n_aux, float* table, void* stream) {
-    int rc = check_mlp(m);
-    if (rc) return rc;
-    if (n_aux < 0 || (n_aux > 0 && (!aux || !table))) return TIR_ERR_ARG;
-    if (n_aux == 0) return TIR_OK;
-    const int64_t total = n_aux * HID;
-    hipLaunchKernelGGL(k_mlp_aux_table, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, tir_stream(stream), m->packed, aux, n_aux,
-                       table);
-    TIR_CHECK_LAUNCH();
-    return TIR_OK;
-}
-
-template <bool SAVE>
-static int launch_auxtab(const TirMlp* m, const float* feat, int32_t feat_stride, const float* table, const int32_t* aux_map,
-                         int32_t aux_mod, float* out, float* h1, float* h2, int64_t n, const int32_t* n_dev, void* stream) {
-    int rc = check_mlp(m);
-    if (rc) return rc;
-    if (n < 0 || feat_stride < F || (n > 0 && (!feat || !table || !out || (SAVE && (!h1 || !h2))))) return TIR_ERR_ARG;
-    if (reinterpret_cast<uintptr_t>(table) % 16 != 0) return TIR_ERR_ARG;
-    if (n == 0) return TIR_OK;
-    const bool vec = (feat_stride % 4 == 0) && feat_stride >= F + 1 && (reinterpret_cast<uintptr_t>(feat) % 16 == 0);
-    const void* kfn = vec ? reinterpret_cast<const void*>(k_mlp_bf16_auxt<true, SAVE>) : reinterpret_cast<const void*>(k_mlp_bf16_auxt<false, SAVE>);
-    if (int r2 = tir_allow_dynamic_lds(kfn, (int)BFA_BYTES)) return r2;
-    const int64_t tiles = (n + 255) / 256;
-    const int grid_max = m->tune_grid > 0 ? m->tune_grid : 256;
-    const unsigned grid = (unsigned)(tiles < grid_max ? tiles : grid_max);
-    if (vec) hipLaunchKernelGGL((k_mlp_bf16_auxt<true, SAVE>), dim3(grid), dim3(512), (size_t)BFA_BYTES, tir_stream(stream), m->packed,
-                                feat, feat_stride, table, aux_map, aux_mod, out, n, n_dev, m->out_dim, m->act, h1, h2);
-    else     hipLaunchKernelGGL((k_mlp_bf16_auxt<false, SAVE>), dim3(grid), dim3(512), (size_t)BFA_BYTES, tir_stream(stream), m->packed,
-                                feat, feat_stride, table, aux_map, aux_mod, out, n, n_dev, m->out_dim, m->act, h1, h2);
-    TIR_CHECK_LAUNCH();
-    return TIR_OK;
-}
-
-extern "C" int tir_mlp_fwd_auxtab_bf16x3(const TirMlp* m, const float* feat, int32_t feat_stride, const float* table,
-                                         const int32_t* aux_map, int32_t aux_mod, float* out, int64_t n, const int32_t* n_dev,
-                                         void* stream) {
-    return launch_auxtab<false>(m, feat, feat_stride, table, aux_map, aux_mod, out, nullptr, nullptr, n, n_dev, stream);
-}
-
-extern "C" int tir_mlp_fwd_auxtab_f16(const TirMlp* m, const float* feat, int32_t feat_stride, const float* table,
-                                      const int32_t* aux_map, int32_t aux_mod, float* out, int64_t n, const int32_t* n_dev,
-                                      void* stream) {
-    int rc = check_mlp(m);
-    if (rc) return rc;
-    if (n < 0 || feat_stride < F || (n > 0 && (!feat || !table || !out))) return TIR_ERR_ARG;
-    if (reinterpret_cast<uintptr_t>(table) % 16 != 0) return TIR_ERR_ARG;
-    if (n == 0) return TIR_OK;
-    const bool vec = (feat_stride % 4 == 0) && feat_stride >= F + 1 && (reinterpret_cast<uintptr_t>(feat) % 16 == 0);
-    const void* kfn = vec ? reinterpret_cast<const void*>(k_mlp_f16_auxt<true>) : reinterpret_cast<const void*>(k_mlp_f16_auxt<false>);
-    if (int r2 = tir_allow_dynamic_lds(kfn, (int)FH_BYTES)) return r2;
-    const int64_t tiles = (n + 255) / 256;
-    const int grid_max = m->tune_grid > 0 ? m->tune_grid : 256;
-    const unsigned grid = (unsigned)(tiles < grid_max ? tiles : grid_max);
-    if (vec) hipLaunchKernelGGL((k_mlp_f16_auxt<true>), dim3(grid), dim3(512), (size_t)FH_BYTES, tir_stream(stream), m->packed, feat,
-                                feat_stride, table, aux_map, aux_mod, out, n, n_dev, m->out_dim, m->act);
-    else     hipLaunchKernelGGL((k_mlp_f16_auxt<false>), dim3(grid), dim3(512), (size_t)FH_BYTES, tir_stream(stream), m->packed, feat,
-                                feat_stride, table, aux_map, aux_mod, out, n, n_dev, m->out_dim, m->act);
-    TIR_CHECK_LAUNCH();
-    return TIR_OK;
-}
-
-extern "C" int tir_indirect_fused_fwd(const TirField* f, const TirFieldHalf* fh, const TirMlp* m, const float* xyz,
-                                      const int32_t* light_idx, const int32_t* rec_map, int32_t idx_div, int32_t aux_mod,
-                                      const float* table, float* out, int64_t n, const int32_t* n_dev, void* stream) {
-    if (!f || !fh) return TIR_ERR_ARG;
-    int rc = check_mlp(m);
-    if (rc) return rc;
-    for (int i = 0; i < 3; ++i)
-        if (f->grid[i] < 2 || !fh->aplane[i] || !fh->aline[i] || reinterpret_cast<uintptr_t>(fh->aplane[i]) % 16 != 0 ||
-            reinterpret_cast<uintptr_t>(fh->aline[i]) % 16 != 0) return TIR_ERR_ARG;
-    if (!f->basis_t || !f->light_mean || !f->light_line) return TIR_ERR_ARG;
-    if (f->n_acomp != 48 || f->app_dim != F || !tir_app_index_ok(f)) return TIR_ERR_UNSUPPORTED;
-    if (n < 0 || (n > 0 && (!xyz || !light_idx || !table || !out))) return TIR_ERR_ARG;
-    if (reinterpret_cast<uintptr_t>(table) % 16 != 0) return TIR_ERR_ARG;
-    if (n == 0) return TIR_OK;
-    if (n >= (int64_t)1 << 31 || idx_div < 0 || aux_mod < 0) return TIR_ERR_UNSUPPORTED;       // 32-bit record / ray arithmetic in the kernel
-    const int lt_rows = f->n_lights <= 16 ? f->n_lights : 0;
-    constexpr int NW = 12; constexpr bool PACK = true;
-    const size_t lds = (size_t)FH_BYTES + FUS_WH_BYTES + (size_t)(lt_rows + 1) * 144 * sizeof(float) + (size_t)NW * 32 * FUS_XH * 2;
-    if (int r2 = tir_allow_dynamic_lds(reinterpret_cast<const void*>(k_indirect_fused<NW, PACK>), (int)lds)) return r2;
-    const int64_t tiles = (n + NW * 32 - 1) / (NW * 32);
-    const int grid_max = m->tune_grid > 0 ? m->tune_grid : 256;
-    const unsigned grid = (unsigned)(tiles < grid_max ? tiles : grid_max);
-    hipLaunchKernelGGL((k_indirect_fused<NW, PACK>), dim3(grid), dim3(NW * 64), lds, tir_stream(stream), *f, *fh, m->packed, xyz, light_idx, rec_map,
-                       idx_div, aux_mod, table, out, n, n_dev, m->out_dim, m->act, lt_rows);
-    TIR_CHECK_LAUNCH();
-    return TIR_OK;
-}
-
-extern "C" int tir_indirect_fused_hp_fwd(const TirField* f, const TirMlp* m, const float* xyz, const int32_t* light_idx,
-                                         const int32_t* rec_map, int32_t idx_div, int32_t aux_mod, const float* table, float* out,
-                                         int64_t n, const int32_t* n_dev, void* stream) {
-    if (!f) return TIR_ERR_ARG;
-    int rc = check_mlp(m);
-    if (rc) return rc;
-    for (int i = 0; i < 3; ++i)
-        if (f->grid[i] < 2 || !f->aplane[i] || !f->aline[i] || reinterpret_cast<uintptr_t>(f->aplane[i]) % 16 != 0 ||
-            reinterpret_cast<uintptr_t>(f->aline[i]) % 16 != 0) return TIR_ERR_ARG;
-    if (!f->basis_t || !f->light_line) return TIR_ERR_ARG;
-    if (f->n_acomp != 48 || f->app_dim != F || !tir_app_index_ok(f)) return TIR_ERR_UNSUPPORTED;
-    for (int i = 0; i < 3; ++i)           // 32-bit byte offsets on the 24-bit multiplier: row bytes < 2^24, plane bytes < 2^32
-        for (int j = i + 1; j < 3; ++j)
-            if ((int64_t)f->grid[i] * HP_TB >= (1 << 24) || (int64_t)f->grid[j] * HP_TB >= (1 << 24) ||
-                (int64_t)f->grid[i] * f->grid[j] * HP_TB >= ((int64_t)1 << 32)) return TIR_ERR_UNSUPPORTED;
-    if (n < 0 || (n > 0 && (!xyz || !light_idx || !table || !out))) return TIR_ERR_ARG;
-    if (reinterpret_cast<uintptr_t>(table) % 16 != 0) return TIR_ERR_ARG;
-    if (n == 0) return TIR_OK;
-    if (n >= (int64_t)1 << 31 || idx_div < 0 || aux_mod < 0) return TIR_ERR_UNSUPPORTED;       // 32-bit record / ray arithmetic in the kernel
-    if (f->n_lights < 1 || f->n_lights > 8) return TIR_ERR_UNSUPPORTED;        // every light row is staged in LDS (576 B each; 8 rows: 158.2 KB in all)
-    const int lt_rows = f->n_lights;
-    constexpr int NW = 8;
-    const size_t lds = (size_t)FH_BYTES + (size_t)F8_FLOATS * 4 + 2 * (size_t)FUS_WH_BYTES + (size_t)lt_rows * 144 * sizeof(float) +
-                       (size_t)NW * HP_X_HALVES * 2;
-    if (int r2 = tir_allow_dynamic_lds(reinterpret_cast<const void*>(k_indirect_fused_hp<NW>), (int)lds)) return r2;
-    const int64_t tiles = (n + NW * 32 - 1) / (NW * 32);
-    const int grid_max = m->tune_grid > 0 ? m->tune_grid : 256;
-    const unsigned grid = (unsigned)(tiles < grid_max ? tiles : grid_max);
-    hipLaunchKernelGGL((k_indirect_fused_hp<NW>), dim3(grid), dim3(NW * 64), lds, tir_stream(stream), *f, m->packed, xyz, light_idx, rec_map,
-                       idx_div, aux_mod, table, out, n, n_dev, m->out_dim, m->act, lt_rows);
-    TIR_CHECK_LAUNCH();
-    return TIR_OK;
-}
-
-extern "C" int tir_mlp_train_fwd_auxtab_bf16x3(const TirMlp* m, const float* feat, int32_t feat_stride, const float* table,
-                                               const int32_t* aux_map, int32_t aux_mod, float* out, float* h1, float* h2,
-                                               int64_t n, const int32_t* n_dev, void* stream) {
-    return launch_auxtab<true>(m, feat, feat_stride, table, aux_map, aux_mod, out, h1, h2, n, n_dev, stream);
-}
-
 extern "C" int tir_mlp_train_fwd_multi_bf16x3(const TirMlp* const* mlps, const float* const* feats, int32_t feat_stride,
                                               const float* const* auxs, const int32_t* const* aux_maps, float* const* outs,
                                               float* const* h1s, float* const* h2s, int32_t n_jobs, int64_t n,
@@ -2716,113 +2605,151 @@ extern "C" int tir_mlp_train_fwd_multi_bf16x3(const TirMlp* const* mlps, const f
     return launch_multi<true>(mlps, feats, feat_stride, auxs, aux_maps, outs, h1s, h2s, n_jobs, n, n_dev, stream);
 }
 
-extern "C" int tir_mlp_fwd_bf16(const TirMlp* m, const float* feat, int32_t feat_stride, const float* aux, const int32_t* aux_map, int32_t aux_mod,
-                                float* out, int64_t n, const int32_t* n_dev, void* stream) {
-    return launch_bf16<1>(m, feat, feat_stride, aux, aux_map, aux_mod, out, n, n_dev, stream);
+extern "C" int tir_mlp_aux_table(const TirMlp* m, const float* aux, int64_t n_aux, float* table, void* stream) {
+    if (int rc = check_mlp(m)) return rc;
+    return tir_with_rows(n_aux, {aux, table}, {}, [&] {                          // (aux rows, no feature rows: no stride to test)
+        return tir_launch(k_mlp_aux_table, 0, dim3((unsigned)((n_aux * HID + 255) / 256)), dim3(256), 0, tir_stream(stream), m->packed, aux,
+                          n_aux, table);
+    });
 }
 
-extern "C" int tir_mlp_fwd_valu(const TirMlp* m, const float* feat, int32_t feat_stride, const float* aux, const int32_t* aux_map, int32_t aux_mod,
-                                float* out, int64_t n, const int32_t* n_dev, void* stream) {
-    int rc = check_mlp(m);
-    if (rc) return rc;
-    if (n < 0 || feat_stride < F || (n > 0 && (!feat || !aux || !out))) return TIR_ERR_ARG;
-    if (n == 0) return TIR_OK;
-    hipLaunchKernelGGL(k_mlp_valu, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, tir_stream(stream), m->packed,
-                       feat, feat_stride, aux, aux_map, aux_mod, out, n, n_dev, m->out_dim, m->act);
-    TIR_CHECK_LAUNCH();
-    return TIR_OK;
+#define TIR_AUXT_ARGS m->packed, feat, feat_stride, table, aux_map, aux_mod, out, n, n_dev, m->out_dim, m->act
+// the decoders that read layer 1's aux part from a table (tir_mlp_aux_table): split-bf16 (optionally SAVE) or fp16 operands
+template <bool F16, bool SAVE>
+static int mlp_fwd_auxtab(const TirMlp* m, const float* feat, int32_t feat_stride, const float* table, const int32_t* aux_map,
+                          int32_t aux_mod, float* out, float* h1, float* h2, int64_t n, const int32_t* n_dev, void* stream) {
+    const auto go = [&] {
+        const bool vec = rows_vec(feat, feat_stride);
+        const dim3 g(decoder_grid(n, 256, m->tune_grid)), b(512);
+        hipStream_t s = tir_stream(stream);
+        if constexpr (F16)
+            return vec ? tir_launch(k_mlp_f16_auxt<true>, FH_BYTES, g, b, FH_BYTES, s, TIR_AUXT_ARGS)
+                       : tir_launch(k_mlp_f16_auxt<false>, FH_BYTES, g, b, FH_BYTES, s, TIR_AUXT_ARGS);
+        else
+            return vec ? tir_launch(k_mlp_bf16_auxt<true, SAVE>, BFA_BYTES, g, b, BFA_BYTES, s, TIR_AUXT_ARGS, h1, h2)
+                       : tir_launch(k_mlp_bf16_auxt<false, SAVE>, BFA_BYTES, g, b, BFA_BYTES, s, TIR_AUXT_ARGS, h1, h2);
+    };
+    if constexpr (SAVE) return with_decoder_rows(m, n, feat_stride, {}, {feat, table, out, h1, h2}, {table}, go);
+    else return with_decoder_rows(m, n, feat_stride, {}, {feat, table, out}, {table}, go);
 }
 
-extern "C" int tir_mlp_inputs(const TirMlp* m, const float* feat, int32_t feat_stride, const float* aux,
-                              const int32_t* aux_map, int32_t aux_mod, float* x, int64_t n, void* stream) {
-    int rc = check_mlp(m);
-    if (rc) return rc;
-    if (n < 0 || feat_stride < F || (n > 0 && (!feat || !aux || !x))) return TIR_ERR_ARG;
-    if (n == 0) return TIR_OK;
-    hipLaunchKernelGGL(k_mlp_inputs, dim3((unsigned)((n + 7) / 8)), dim3(8 * (XPAD / 4)), 0, tir_stream(stream), feat,
-                       feat_stride, aux, aux_map, aux_mod, x, n);
-    TIR_CHECK_LAUNCH();
-    return TIR_OK;
+#undef TIR_AUXT_ARGS
+
+extern "C" int tir_mlp_fwd_auxtab_bf16x3(const TirMlp* m, const float* feat, int32_t feat_stride, const float* table,
+                                         const int32_t* aux_map, int32_t aux_mod, float* out, int64_t n, const int32_t* n_dev,
+                                         void* stream) {
+    return mlp_fwd_auxtab<false, false>(m, feat, feat_stride, table, aux_map, aux_mod, out, nullptr, nullptr, n, n_dev, stream);
+}
+
+extern "C" int tir_mlp_fwd_auxtab_f16(const TirMlp* m, const float* feat, int32_t feat_stride, const float* table,
+                                      const int32_t* aux_map, int32_t aux_mod, float* out, int64_t n, const int32_t* n_dev,
+                                      void* stream) {
+    return mlp_fwd_auxtab<true, false>(m, feat, feat_stride, table, aux_map, aux_mod, out, nullptr, nullptr, n, n_dev, stream);
+}
+
+extern "C" int tir_mlp_train_fwd_auxtab_bf16x3(const TirMlp* m, const float* feat, int32_t feat_stride, const float* table,
+                                               const int32_t* aux_map, int32_t aux_mod, float* out, float* h1, float* h2,
+                                               int64_t n, const int32_t* n_dev, void* stream) {
+    return mlp_fwd_auxtab<false, true>(m, feat, feat_stride, table, aux_map, aux_mod, out, h1, h2, n, n_dev, stream);
+}
+
+extern "C" int tir_indirect_fused_fwd(const TirField* f, const TirFieldHalf* fh, const TirMlp* m, const float* xyz,
+                                      const int32_t* light_idx, const int32_t* rec_map, int32_t idx_div, int32_t aux_mod,
+                                      const float* table, float* out, int64_t n, const int32_t* n_dev, void* stream) {
+    if (!f || !fh) return TIR_ERR_ARG;
+    if (int rc = check_mlp(m)) return rc;
+    if (int rc = tir_check_app_field(f, TirAppNeeds().fp16_tables(fh).aligned().element_index32().width(48).app_dim_is(F).no_feature_rows(), 0)) return rc;
+    return tir_with_rows(n, {xyz, light_idx, table, out}, {table}, [&] {
+        if (!fused_index_ok(n, idx_div, aux_mod)) return (int)TIR_ERR_UNSUPPORTED;
+        const int lt_rows = f->n_lights <= 16 ? f->n_lights : 0;
+        constexpr int NW = 12; constexpr bool PACK = true;
+        const size_t lds = (size_t)FH_BYTES + FUS_WH_BYTES + (size_t)(lt_rows + 1) * 144 * sizeof(float) + (size_t)NW * 32 * FUS_XH * 2;
+        return tir_launch(k_indirect_fused<NW, PACK>, (int)lds, dim3(decoder_grid(n, NW * 32, m->tune_grid)), dim3(NW * 64), lds,
+                          tir_stream(stream), *f, *fh, m->packed, xyz, light_idx, rec_map, idx_div, aux_mod, table, out, n, n_dev,
+                          m->out_dim, m->act, lt_rows);
+    });
+}
+
+extern "C" int tir_indirect_fused_hp_fwd(const TirField* f, const TirMlp* m, const float* xyz, const int32_t* light_idx,
+                                         const int32_t* rec_map, int32_t idx_div, int32_t aux_mod, const float* table, float* out,
+                                         int64_t n, const int32_t* n_dev, void* stream) {
+    if (!f) return TIR_ERR_ARG;
+    if (int rc = check_mlp(m)) return rc;
+    if (int rc = tir_check_app_field(f, TirAppNeeds().aligned().no_light_mean().element_index32().width(48).app_dim_is(F).no_feature_rows(), 0)) return rc;
+    for (int i = 0; i < 3; ++i)           // 32-bit byte offsets on the 24-bit multiplier: row bytes < 2^24, plane bytes < 2^32
+        for (int j = i + 1; j < 3; ++j)
+            if ((int64_t)f->grid[i] * HP_TB >= (1 << 24) || (int64_t)f->grid[j] * HP_TB >= (1 << 24) ||
+                (int64_t)f->grid[i] * f->grid[j] * HP_TB >= ((int64_t)1 << 32)) return TIR_ERR_UNSUPPORTED;
+    return tir_with_rows(n, {xyz, light_idx, table, out}, {table}, [&] {
+        if (!fused_index_ok(n, idx_div, aux_mod)) return (int)TIR_ERR_UNSUPPORTED;
+        if (f->n_lights < 1 || f->n_lights > 8) return (int)TIR_ERR_UNSUPPORTED;        // every light row is staged in LDS (576 B each; 8 rows: 158.2 KB in all)
+        const int lt_rows = f->n_lights;
+        constexpr int NW = 8;
+        const size_t lds = (size_t)FH_BYTES + (size_t)F8_FLOATS * 4 + 2 * (size_t)FUS_WH_BYTES + (size_t)lt_rows * 144 * sizeof(float) +
+                           (size_t)NW * HP_X_HALVES * 2;
+        return tir_launch(k_indirect_fused_hp<NW>, (int)lds, dim3(decoder_grid(n, NW * 32, m->tune_grid)), dim3(NW * 64), lds,
+                          tir_stream(stream), *f, m->packed, xyz, light_idx, rec_map, idx_div, aux_mod, table, out, n, n_dev, m->out_dim,
+                          m->act, lt_rows);
+    });
 }
 
 extern "C" int64_t tir_mlp_bwd_packed_floats(int32_t feat_dim, int32_t pe, int32_t hidden, int32_t out_dim) {
-    if (feat_dim != F || pe != PE || hidden != HID || out_dim < 1 || out_dim > 4) return TIR_ERR_UNSUPPORTED;
-    return BWD_TOTAL_FLOATS;
+    return mlp_shape_built(feat_dim, pe, hidden, out_dim) ? (int64_t)BWD_TOTAL_FLOATS : (int64_t)TIR_ERR_UNSUPPORTED;
 }
 
 extern "C" int tir_pack_mlp_bwd(const float* w0, const float* w1, const float* w2, int32_t feat_dim, int32_t pe,
                                 int32_t hidden, int32_t out_dim, float* packed, void* stream) {
-    if (!w0 || !w1 || !w2 || !packed) return TIR_ERR_ARG;
-    if (feat_dim != F || pe != PE || hidden != HID || out_dim < 1 || out_dim > 4) return TIR_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(k_pack_mlp_bwd, dim3((BWD_TOTAL_FLOATS + 255) / 256), dim3(256), 0, tir_stream(stream), w0, w1, w2,
-                       out_dim, packed);
-    TIR_CHECK_LAUNCH();
-    return TIR_OK;
+    if (tir_any_null({w0, w1, w2, packed})) return TIR_ERR_ARG;
+    if (!mlp_shape_built(feat_dim, pe, hidden, out_dim)) return TIR_ERR_UNSUPPORTED;
+    return tir_launch(k_pack_mlp_bwd, 0, dim3((BWD_TOTAL_FLOATS + 255) / 256), dim3(256), 0, tir_stream(stream), w0, w1, w2, out_dim, packed);
+}
+
+// the decoder backward on fp32 (k_mlp_bwd) or split-bf16 (k_mlp_bwd_bf16) operands: same rows, same arguments
+template <typename Kernel>
+static int mlp_bwd(Kernel kernel, size_t lds, const TirMlp* m, const float* packed_bwd, const float* feat, int32_t feat_stride,
+                   const float* out, const float* g_out, const float* h1, const float* h2, int64_t n, float* g_feat, float* dz1,
+                   float* dz2, float* dz3, void* stream) {
+    // (the row pointers were tested behind the n == 0 return here and in front of it in the forward entries: no call can tell the
+    //  two apart, both leave an empty call's row pointers untested; packed_bwd is wanted even by an empty call: kept as found)
+    return with_decoder_rows(m, n, feat_stride, {packed_bwd}, {feat, out, g_out, h1, h2, g_feat, dz1, dz2, dz3}, {}, [&] {
+        return tir_launch(kernel, (int)lds, dim3(decoder_grid(n, 256, NO_TUNE_GRID)), dim3(512), lds, tir_stream(stream), packed_bwd, feat,
+                          feat_stride, out, g_out, h1, h2, n, m->out_dim, m->act, g_feat, dz1, dz2, dz3);
+    });
 }
 
 extern "C" int tir_mlp_bwd(const TirMlp* m, const float* packed_bwd, const float* feat, int32_t feat_stride,
                            const float* out, const float* g_out, const float* h1, const float* h2, int64_t n,
                            float* g_feat, float* dz1, float* dz2, float* dz3, void* stream) {
-    int rc = check_mlp(m);
-    if (rc) return rc;
-    if (!packed_bwd || n < 0 || feat_stride < F) return TIR_ERR_ARG;
-    if (n == 0) return TIR_OK;
-    if (!feat || !out || !g_out || !h1 || !h2 || !g_feat || !dz1 || !dz2 || !dz3) return TIR_ERR_ARG;
-    const size_t lds = (size_t)BWD_FLOATS * sizeof(float);
-    if (int rc = tir_allow_dynamic_lds(reinterpret_cast<const void*>(k_mlp_bwd), (int)lds)) return rc;
-    int64_t tiles = (n + 255) / 256;
-    unsigned grid = (unsigned)(tiles < 256 ? tiles : 256);
-    hipLaunchKernelGGL(k_mlp_bwd, dim3(grid), dim3(512), lds, tir_stream(stream), packed_bwd, feat, feat_stride, out,
-                       g_out, h1, h2, n, m->out_dim, m->act, g_feat, dz1, dz2, dz3);
-    TIR_CHECK_LAUNCH();
-    return TIR_OK;
+    return mlp_bwd(k_mlp_bwd, (size_t)BWD_FLOATS * sizeof(float), m, packed_bwd, feat, feat_stride, out, g_out, h1, h2, n, g_feat, dz1, dz2,
+                   dz3, stream);
+}
+
+extern "C" int tir_mlp_bwd_bf16x3(const TirMlp* m, const float* packed_bwd, const float* feat, int32_t feat_stride,
+                           const float* out, const float* g_out, const float* h1, const float* h2, int64_t n,
+                           float* g_feat, float* dz1, float* dz2, float* dz3, void* stream) {
+    return mlp_bwd(k_mlp_bwd_bf16, (size_t)BWD_BF_LDS_BYTES, m, packed_bwd, feat, feat_stride, out, g_out, h1, h2, n, g_feat, dz1, dz2, dz3,
+                   stream);
 }
 
 extern "C" int tir_mlp_bwd_multi_bf16x3(const TirMlp* const* mlps, const float* const* packed_bwds, const float* const* feats,
                                        int32_t feat_stride, const float* const* outs, const float* const* g_outs,
                                        const float* const* h1s, const float* const* h2s, int32_t n_jobs, int64_t n,
                                        float* const* g_feats, float* const* dz1s, float* const* dz2s, float* const* dz3s, void* stream) {
-    if (n_jobs < 1 || n_jobs > 4 || !mlps || !packed_bwds || !feats || !outs || !g_outs || !h1s || !h2s || !g_feats || !dz1s || !dz2s ||
-        !dz3s || n < 0 || feat_stride < F)
+    if (n_jobs < 1 || n_jobs > 4 || tir_any_null({mlps, packed_bwds, feats, outs, g_outs, h1s, h2s, g_feats, dz1s, dz2s, dz3s}) || n < 0 ||
+        feat_stride < F)
         return TIR_ERR_ARG;
     TirMlpBwdJobs jobs;
     jobs.n_jobs = n_jobs;
-    for (int i = 0; i < n_jobs; ++i) {
-        int rc = check_mlp(mlps[i]);
-        if (rc) return rc;
+    for (int i = 0; i < n_jobs; ++i) {                      // per job: the descriptor, then the pointers (see launch_multi)
+        if (int rc = check_mlp(mlps[i])) return rc;
         if (!packed_bwds[i]) return TIR_ERR_ARG;
-        if (n > 0 && (!feats[i] || !outs[i] || !g_outs[i] || !h1s[i] || !h2s[i] || !g_feats[i] || !dz1s[i] || !dz2s[i] || !dz3s[i]))
-            return TIR_ERR_ARG;
+        if (n > 0 && tir_any_null({feats[i], outs[i], g_outs[i], h1s[i], h2s[i], g_feats[i], dz1s[i], dz2s[i], dz3s[i]})) return TIR_ERR_ARG;
         jobs.j[i] = TirMlpBwdJob{packed_bwds[i], feats[i], outs[i], g_outs[i], h1s[i], h2s[i], g_feats[i], dz1s[i], dz2s[i], dz3s[i],
                                  mlps[i]->out_dim, mlps[i]->act};
     }
     if (n == 0) return TIR_OK;
-    const size_t lds = (size_t)BWD_BF_LDS_BYTES;
-    if (int rc = tir_allow_dynamic_lds(reinterpret_cast<const void*>(k_mlp_bwd_bf16_multi), (int)lds)) return rc;
-    const int64_t tiles = (n + 255) / 256;
-    int per = 256 / n_jobs;
-    if (tiles < per) per = (int)tiles;
-    hipLaunchKernelGGL(k_mlp_bwd_bf16_multi, dim3((unsigned)(per * n_jobs)), dim3(512), lds, tir_stream(stream), jobs, feat_stride, n);
-    TIR_CHECK_LAUNCH();
-    return TIR_OK;
-}
-
-extern "C" int tir_mlp_bwd_bf16x3(const TirMlp* m, const float* packed_bwd, const float* feat, int32_t feat_stride,
-                           const float* out, const float* g_out, const float* h1, const float* h2, int64_t n,
-                           float* g_feat, float* dz1, float* dz2, float* dz3, void* stream) {
-    int rc = check_mlp(m);
-    if (rc) return rc;
-    if (!packed_bwd || n < 0 || feat_stride < F) return TIR_ERR_ARG;
-    if (n == 0) return TIR_OK;
-    if (!feat || !out || !g_out || !h1 || !h2 || !g_feat || !dz1 || !dz2 || !dz3) return TIR_ERR_ARG;
-    const size_t lds = (size_t)BWD_BF_LDS_BYTES;
-    if (int rc = tir_allow_dynamic_lds(reinterpret_cast<const void*>(k_mlp_bwd_bf16), (int)lds)) return rc;
-    int64_t tiles = (n + 255) / 256;
-    unsigned grid = (unsigned)(tiles < 256 ? tiles : 256);
-    hipLaunchKernelGGL(k_mlp_bwd_bf16, dim3(grid), dim3(512), lds, tir_stream(stream), packed_bwd, feat, feat_stride, out,
-                       g_out, h1, h2, n, m->out_dim, m->act, g_feat, dz1, dz2, dz3);
-    TIR_CHECK_LAUNCH();
-    return TIR_OK;
+    return tir_launch(k_mlp_bwd_bf16_multi, BWD_BF_LDS_BYTES, dim3(tir_job_split((n + 255) / 256, 256, n_jobs)), dim3(512),
+                      (size_t)BWD_BF_LDS_BYTES, tir_stream(stream), jobs, feat_stride, n);
 }
 
 extern "C" int tir_mlp_wgrad_multi(const float* const* dz1s, const float* const* dz2s, const float* const* dz3s,
@@ -2832,14 +2759,12 @@ extern "C" int tir_mlp_wgrad_multi(const float* const* dz1s, const float* const*
                                    float* const* dW2s, float* const* db2s, int32_t n_jobs, int64_t n, int32_t max_workgroups,
                                    void* stream) {
     if (n_jobs < 1 || n_jobs > 4 || n < 0 || feat_stride < F || max_workgroups < 0) return TIR_ERR_ARG;
-    if (!dz1s || !dz2s || !dz3s || !h1s || !h2s || !feats || !auxs || !dW0s || !db0s || !dW1s || !db1s || !dW2s || !db2s)
-        return TIR_ERR_ARG;
-    if (n == 0) return TIR_OK;
+    if (tir_any_null({dz1s, dz2s, dz3s, h1s, h2s, feats, auxs, dW0s, db0s, dW1s, db1s, dW2s, db2s})) return TIR_ERR_ARG;
+    if (n == 0) return TIR_OK;                               // (before the per-job pointers, which an empty call may leave null)
     TirWgradJobs jobs;
     jobs.n_jobs = n_jobs;
     for (int i = 0; i < n_jobs; ++i) {
-        if (!dz1s[i] || !dz2s[i] || !dz3s[i] || !h1s[i] || !h2s[i] || !feats[i] || !auxs[i] || !dW0s[i] || !db0s[i] ||
-            !dW1s[i] || !db1s[i] || !dW2s[i] || !db2s[i])
+        if (tir_any_null({dz1s[i], dz2s[i], dz3s[i], h1s[i], h2s[i], feats[i], auxs[i], dW0s[i], db0s[i], dW1s[i], db1s[i], dW2s[i], db2s[i]}))
             return TIR_ERR_ARG;
         jobs.j[i] = TirWgradJob{dz1s[i], dz2s[i], dz3s[i], h1s[i], h2s[i], feats[i], auxs[i], aux_maps ? aux_maps[i] : nullptr,
                                 dW0s[i], db0s[i], dW1s[i], db1s[i], dW2s[i], db2s[i]};
@@ -2848,21 +2773,11 @@ extern "C" int tir_mlp_wgrad_multi(const float* const* dz1s, const float* const*
     // the launch ends.  These products are leaves of the backward (they run on a second stream beside the chain that feeds
     // the optimizer): max_workgroups (0 = 256) lets the caller leave CUs to that chain.
     const int total = max_workgroups > 0 ? (max_workgroups < 256 ? max_workgroups : 256) : 256;
-    int per = total / n_jobs;                                // the grid split between the jobs
-    if (per < 1) per = 1;
-    const int64_t steps = (n + 15) / 16;
-    if (steps < per) per = (int)steps;
+    const dim3 g(tir_job_split((n + 15) / 16, total, n_jobs)), b(1024);          // 16-row steps
     bool vec_ok = !(feat_stride & 3) && feat_stride >= 32 && n < ((int64_t)1 << 31);
     for (int i = 0; i < n_jobs && vec_ok; ++i)                                  // the staged kernel fetches rows as float4
-        for (const float* q : {dz1s[i], dz2s[i], dz3s[i], h1s[i], h2s[i], feats[i]})
-            if (reinterpret_cast<uintptr_t>(q) % 16 != 0) vec_ok = false;
-    if (!vec_ok) {                                                              // rows not float4-addressable: the direct-load kernel
-        hipLaunchKernelGGL(k_mlp_wgrad, dim3((unsigned)(per * n_jobs)), dim3(1024), 0, tir_stream(stream), jobs, feat_stride, n);
-    } else {
-        if (int rc = tir_allow_dynamic_lds(reinterpret_cast<const void*>(k_mlp_wgrad_lds), WL_LDS_BYTES)) return rc;
-        hipLaunchKernelGGL(k_mlp_wgrad_lds, dim3((unsigned)(per * n_jobs)), dim3(1024), WL_LDS_BYTES, tir_stream(stream), jobs,
-                           feat_stride, n);
-    }
-    TIR_CHECK_LAUNCH();
-    return TIR_OK;
+        vec_ok = tir_aligned16({dz1s[i], dz2s[i], dz3s[i], h1s[i], h2s[i], feats[i]});
+    if (!vec_ok)                                                                // rows not float4-addressable: the direct-load kernel
+        return tir_launch(k_mlp_wgrad, 0, g, b, 0, tir_stream(stream), jobs, feat_stride, n);
+    return tir_launch(k_mlp_wgrad_lds, WL_LDS_BYTES, g, b, (size_t)WL_LDS_BYTES, tir_stream(stream), jobs, feat_stride, n);
 }

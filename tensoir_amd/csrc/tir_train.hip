@@ -1477,38 +1477,28 @@ static int launch_app_bwd(const TirField* f, const TirFieldGrad* g, const float*
     const int64_t per_cu = (lds <= 80 * 1024) ? 2 : 1;           // persistent blocks amortise the LDS zero / flush
     if (blocks > 256 * per_cu) blocks = 256 * per_cu;
     dim3 grid((unsigned)blocks), blk(threads);
-    if (int rc = tir_allow_dynamic_lds(reinterpret_cast<const void*>(k_vm_app_bwd<C4, true, true>), 160 * 1024)) return rc;
-    if (int rc = tir_allow_dynamic_lds(reinterpret_cast<const void*>(k_vm_app_bwd<C4, true, false>), 160 * 1024)) return rc;
-    if (int rc = tir_allow_dynamic_lds(reinterpret_cast<const void*>(k_vm_app_bwd<C4, false, true>), 160 * 1024)) return rc;
-    if (g_rad && g_int) hipLaunchKernelGGL((k_vm_app_bwd<C4, true, true>), grid, blk, lds, s, *f, *g, xyz, li, map, n, y_rad, y_int, line_lds);
-    else if (g_rad)     hipLaunchKernelGGL((k_vm_app_bwd<C4, true, false>), grid, blk, lds, s, *f, *g, xyz, li, map, n, y_rad, y_int, line_lds);
-    else                hipLaunchKernelGGL((k_vm_app_bwd<C4, false, true>), grid, blk, lds, s, *f, *g, xyz, li, map, n, y_rad, y_int, line_lds);
-    return TIR_OK;
+    int rc;
+    const auto k = tir_rad_intr_kernel(g_rad, g_int, TIR_APP_LDS_LIMIT, rc,
+                                       [](auto R, auto I) { return k_vm_app_bwd<C4, decltype(R)::value, decltype(I)::value>; });
+    if (rc) return rc;
+    return tir_launch(k, 0, grid, blk, lds, s, *f, *g, xyz, li, map, n, y_rad, y_int, line_lds);
 }
 
 extern "C" int tir_vm_app_bwd(const TirField* f, const TirFieldGrad* g, const float* xyz,
                               const int32_t* light_idx, const int32_t* idx_map, const float* g_rad,
                               const float* g_int, int32_t stride, int64_t n, float* y_rad, float* y_int,
                               void* stream) {
-    int rc = check_grad_field(f, g, false, true);
-    if (rc) return rc;
-    if (!f->basis_t || !f->light_mean || !f->light_line || !g->light_line || !g->light_mean) return TIR_ERR_ARG;
-    if (f->app_dim < 1 || f->app_dim > 27) return TIR_ERR_UNSUPPORTED;
-    if (stride < f->app_dim) return TIR_ERR_ARG;
-    if (n < 0 || (n > 0 && !xyz) || (!g_rad && !g_int) || (g_rad && !light_idx)) return TIR_ERR_ARG;
+    if (int rc = check_grad_field(f, g, false, true)) return rc;
+    if (!g->light_line || !g->light_mean) return TIR_ERR_ARG;
+    // the forward gather's field, with no upper bound on the stride of the cotangent rows
+    if (int rc = tir_check_app_field(f, TirAppNeeds().stride_unbounded(), stride)) return rc;
+    if ((!g_rad && !g_int) || (g_rad && !light_idx)) return TIR_ERR_ARG;
     if ((g_rad && !y_rad) || (g_int && !y_int)) return TIR_ERR_ARG;      // the y buffers double as the dY workspace
-    if (n == 0) return TIR_OK;
-    hipStream_t s = tir_stream(stream);
-    switch (f->n_acomp) {
-        case 48: rc = launch_app_bwd<12>(f, g, xyz, light_idx, idx_map, g_rad, g_int, stride, n, y_rad, y_int, s); break;
-        case 24: rc = launch_app_bwd<6>(f, g, xyz, light_idx, idx_map, g_rad, g_int, stride, n, y_rad, y_int, s); break;
-        case 16: rc = launch_app_bwd<4>(f, g, xyz, light_idx, idx_map, g_rad, g_int, stride, n, y_rad, y_int, s); break;
-        case 96: rc = launch_app_bwd<24>(f, g, xyz, light_idx, idx_map, g_rad, g_int, stride, n, y_rad, y_int, s); break;
-        default: return TIR_ERR_UNSUPPORTED;
-    }
-    if (rc) return rc;
-    TIR_CHECK_LAUNCH();
-    return TIR_OK;
+    return tir_with_rows(n, {xyz}, {}, [&] {
+        return tir_dispatch_c4<12, 6, 4, 24>(f->n_acomp, [&](auto c4) {
+            return launch_app_bwd<decltype(c4)::value>(f, g, xyz, light_idx, idx_map, g_rad, g_int, stride, n, y_rad, y_int, tir_stream(stream));
+        });
+    });
 }
 
 static int gemm_tn_launch(bool bf16, const float* A, int32_t lda, int32_t M, const float* B, int32_t ldb, int32_t N,
