@@ -967,4 +967,45 @@ __device__ __forceinline__ XcdRange xcd_range(long long n_items, int per, bool o
     return xcd_range_at(n_items, per, on, (int)blockIdx.x, (int)gridDim.x);
 }
 
+// acc[q] = fmaf(rec_w[i], rec_rgb[3 i + q], acc[q]) for i = b .. e-1 in index order: the indirect radiance of one secondary ray
+// from its records (models/relight_utils.py:832), the one chain that k_shade_integrate and k_accumulate_records share bit for bit.
+// The loads of a group of G records are issued before the first of the group's fmafs, so a lane pays one memory round trip per
+// group, not per record; the fmafs run in the old order.  Only records of [b, e) are read (the last segment may end at the end of
+// the allocation): whole groups first, then the 1 .. G-1 records that remain as ONE more round -- G-1 loads whose indices stop at
+// e-1 (the surplus ones repeat the last record and are not added), because one by one those records cost up to G-1 round trips,
+// as many as all the whole groups of a long segment together.  A segment starts at any record, so rec_rgb + 3 b is dword-aligned
+// only: plain float loads, which the compiler widens to the multi-dword loads the hardware takes at that alignment.
+template <int G>
+__device__ __forceinline__ void record_sum(const float* __restrict__ rec_w, const float* __restrict__ rec_rgb, int b, int e,
+                                           float (&acc)[3]) {
+    int i = b;
+    for (; e - i >= G; i += G) {
+        float w[G], c[G][3];
+#pragma unroll
+        for (int j = 0; j < G; ++j) {
+            w[j] = rec_w[i + j];
+            c[j][0] = rec_rgb[3 * (size_t)(i + j)]; c[j][1] = rec_rgb[3 * (size_t)(i + j) + 1]; c[j][2] = rec_rgb[3 * (size_t)(i + j) + 2];
+        }
+#pragma unroll
+        for (int j = 0; j < G; ++j) {
+            acc[0] = fmaf(w[j], c[j][0], acc[0]); acc[1] = fmaf(w[j], c[j][1], acc[1]); acc[2] = fmaf(w[j], c[j][2], acc[2]);
+        }
+    }
+    if (i < e) {
+        float w[G - 1], c[G - 1][3];
+#pragma unroll
+        for (int j = 0; j < G - 1; ++j) {
+            const size_t k = (size_t)min(i + j, e - 1);
+            w[j] = rec_w[k];
+            c[j][0] = rec_rgb[3 * k]; c[j][1] = rec_rgb[3 * k + 1]; c[j][2] = rec_rgb[3 * k + 2];
+        }
+#pragma unroll
+        for (int j = 0; j < G - 1; ++j)
+            if (i + j < e) {
+                acc[0] = fmaf(w[j], c[j][0], acc[0]); acc[1] = fmaf(w[j], c[j][1], acc[1]); acc[2] = fmaf(w[j], c[j][2], acc[2]);
+            }
+    }
+}
+constexpr int RECORD_GROUP = 8;        // records per wait of record_sum
+
 }  // namespace tir

@@ -89,16 +89,31 @@ struct TirMarchExtras {
 
 __device__ __forceinline__ void block_exclusive_scan_capped(const int32_t* __restrict__ counts, int32_t* __restrict__ offsets,
                                                              int n, int cap, int32_t* __restrict__ total_out) {
-    // all 256 threads of the calling block; chunked, carry in LDS (same arithmetic as k_exclusive_scan)
+    // all 256 threads of the calling block (the whole GPU waits for it); the same integer sums as k_exclusive_scan.  A thread owns
+    // SCAN_PER consecutive counts: their write-through loads are all issued before the first use (an index past the end repeats
+    // the last count's address and is zeroed after the load: a conditional load would bring its own wait), then the thread's own
+    // exclusive prefixes, ONE block scan of the 256 thread totals, and its offsets.  n = 4096 is one round of loads, one wave scan
+    // and three barriers; larger n goes round with the carry in LDS.
+    constexpr int SCAN_PER = 16;
     __shared__ int32_t wsum[4];
     __shared__ int32_t carry_s;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     if (tid == 0) carry_s = 0;
     __syncthreads();
-    for (int base = 0; base < n; base += 256) {
-        const int i = base + tid;
-        const int32_t v = (i < n) ? __hip_atomic_load(counts + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
-        int32_t incl = v;
+    for (int base = 0; base < n; base += 256 * SCAN_PER) {
+        const int i0 = base + SCAN_PER * tid;
+        int32_t v[SCAN_PER];
+#pragma unroll
+        for (int j = 0; j < SCAN_PER; ++j)
+            v[j] = __hip_atomic_load(counts + min(i0 + j, n - 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        int32_t sum = 0;
+#pragma unroll
+        for (int j = 0; j < SCAN_PER; ++j) {        // v[j] becomes the exclusive prefix inside the thread's run
+            const int32_t x = (i0 + j < n) ? v[j] : 0;
+            v[j] = sum;
+            sum += x;
+        }
+        int32_t incl = sum;
 #pragma unroll
         for (int d = 1; d < 64; d <<= 1) {
             int32_t o = __shfl_up(incl, d, 64);
@@ -109,7 +124,10 @@ __device__ __forceinline__ void block_exclusive_scan_capped(const int32_t* __res
         int32_t woff = 0;
         for (int q = 0; q < wv; ++q) woff += wsum[q];
         const int32_t carry = carry_s;
-        if (i < n) offsets[i] = min(carry + woff + incl - v, cap);
+        const int32_t first = carry + woff + incl - sum;
+#pragma unroll
+        for (int j = 0; j < SCAN_PER; ++j)
+            if (i0 + j < n) offsets[i0 + j] = min(first + v[j], cap);
         __syncthreads();
         if (tid == 255) carry_s = carry + woff + incl;
         __syncthreads();
@@ -1078,15 +1096,10 @@ k_accumulate_records(const int32_t* __restrict__ off, const int32_t* __restrict_
                      float* __restrict__ indirect) {
     int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= n) return;
-    float c0 = 0, c1 = 0, c2 = 0;
+    float c[3] = {0.f, 0.f, 0.f};
     const int b = off[p], e = b + cnt[p];
-    for (int i = b; i < e; ++i) {
-        float w = rec_w[i];
-        c0 = fmaf(w, rec_rgb[3 * (size_t)i], c0);
-        c1 = fmaf(w, rec_rgb[3 * (size_t)i + 1], c1);
-        c2 = fmaf(w, rec_rgb[3 * (size_t)i + 2], c2);
-    }
-    indirect[3 * p] = c0; indirect[3 * p + 1] = c1; indirect[3 * p + 2] = c2;
+    record_sum<RECORD_GROUP>(rec_w, rec_rgb, b, e, c);
+    indirect[3 * p] = c[0]; indirect[3 * p + 1] = c[1]; indirect[3 * p + 2] = c[2];
 }
 
 extern "C" int tir_accumulate_records(const int32_t* ray_rec_off, const int32_t* ray_rec_cnt,

@@ -158,7 +158,9 @@ k_shade_setup(const float* __restrict__ maps, const float* __restrict__ rays, co
 }
 
 // ---- K8: one wave per surface point, lanes over light directions -----------------------------------
-__global__ void __launch_bounds__(256)
+// Four waves per SIMD (at most 128 VGPRs): the 4096 waves of a 4096-ray step are then resident at once; without the bound the
+// record groups take 132 registers.
+__global__ void __launch_bounds__(256, 4)
 k_shade_integrate(const float* __restrict__ maps, const float* __restrict__ rays, const float* __restrict__ dirs,
                   const int32_t* __restrict__ light_idx, const float* __restrict__ vis,
                   const float* __restrict__ indirect, const float* __restrict__ env,
@@ -185,31 +187,46 @@ k_shade_integrate(const float* __restrict__ maps, const float* __restrict__ rays
     li = min(max(li, 0), n_lights - 1);
     const float* envl = env + (size_t)li * D * 3;
     float c[3] = {0.f, 0.f, 0.f};
-    for (int d = lane; d < D; d += 64) {
-        const float lx = dirs[3 * d], ly = dirs[3 * d + 1], lz = dirs[3 * d + 2];
-        const float cosine = fmaxf(lx * mp[4] + ly * mp[5] + lz * mp[6], 0.f);
-        float spec[3];
-        ggx_dir(s, lx, ly, lz, spec);
-        const size_t md = (size_t)m * D + d;
-        const float v = vis[md];
-        const float wd = equal_area ? 1.0f : weight_d[d];
-        float ind[3] = {0.f, 0.f, 0.f};
-        if (indirect) { ind[0] = indirect[3 * md]; ind[1] = indirect[3 * md + 1]; ind[2] = indirect[3 * md + 2]; }
-        else if (rec_off) {        // indirect radiance straight from the ray's records, in sample order (models/relight_utils.py:832)
-            const int b = rec_off[md], e = b + rec_cnt[md];
-            for (int i = b; i < e; ++i) {
-                const float w = rec_w[i];
-                ind[0] = fmaf(w, rec_rgb[3 * (size_t)i], ind[0]);
-                ind[1] = fmaf(w, rec_rgb[3 * (size_t)i + 1], ind[1]);
-                ind[2] = fmaf(w, rec_rgb[3 * (size_t)i + 2], ind[2]);
-            }
+    const bool from_records = !indirect && rec_off;
+    // A lane's directions d = lane, lane + 64, ... two per round (D = 128: all of them in one): everything the two read per
+    // direction -- the direction, its weight and radiance, the pair's visibility and record range -- is loaded before anything
+    // waits for one of them (a missing second direction repeats the first one's addresses: a conditional load would bring its
+    // own wait).  The directions are then summed in ascending order, as before.
+    for (int d0 = lane; d0 < D; d0 += 128) {
+        const bool two = d0 + 64 < D;
+        float l2[2][3], e2[2][3], w2[2], v2[2];
+        int b2[2] = {0, 0}, n2[2] = {0, 0};
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const int d = (u && two) ? d0 + 64 : d0;
+            const size_t md = (size_t)m * D + d;
+#pragma unroll
+            for (int q = 0; q < 3; ++q) { l2[u][q] = dirs[3 * d + q]; e2[u][q] = envl[3 * d + q]; }
+            w2[u] = equal_area ? 1.0f : weight_d[d];
+            v2[u] = vis[md];
+            if (from_records) { b2[u] = rec_off[md]; n2[u] = rec_cnt[md]; }
         }
 #pragma unroll
-        for (int q = 0; q < 3; ++q) {
-            float light = v * envl[3 * d + q] + ind[q];                                       // :462
-            float brdf = s.alb_pi[q] + spec[q];                                               // :455
-            if (equal_area) c[q] += 4.0f * 3.14159265358979323846f * brdf * light * cosine;   // :470-471
-            else c[q] += brdf * light * cosine * wd;                                          // :474-475
+        for (int u = 0; u < 2; ++u) {
+            if (u && !two) break;
+            const float lx = l2[u][0], ly = l2[u][1], lz = l2[u][2];
+            const float cosine = fmaxf(lx * mp[4] + ly * mp[5] + lz * mp[6], 0.f);
+            float spec[3];
+            ggx_dir(s, lx, ly, lz, spec);
+            const size_t md = (size_t)m * D + d0 + 64 * u;
+            const float v = v2[u];
+            const float wd = w2[u];
+            float ind[3] = {0.f, 0.f, 0.f};
+            if (indirect) { ind[0] = indirect[3 * md]; ind[1] = indirect[3 * md + 1]; ind[2] = indirect[3 * md + 2]; }
+            // indirect radiance straight from the ray's records, in sample order (models/relight_utils.py:832)
+            else if (rec_off) record_sum<RECORD_GROUP>(rec_w, rec_rgb, b2[u], b2[u] + n2[u], ind);
+#pragma unroll
+            for (int q = 0; q < 3; ++q) {
+                float light = v * e2[u][q] + ind[q];                                              // :462
+                float brdf = s.alb_pi[q] + spec[q];                                               // :455
+                if (equal_area) c[q] += 4.0f * 3.14159265358979323846f * brdf * light * cosine;   // :470-471
+                else c[q] += brdf * light * cosine * wd;                                          // :474-475
+            }
         }
     }
 #pragma unroll
