@@ -1107,6 +1107,38 @@ int tir_light_gbuffer_shadowed(const float* gbuf, const float* view, const float
                                const uint32_t* maps, int64_t M, int32_t D, int32_t S, float bias_const, float bias_slope, float fresnel,
                                int32_t flags, float* out, void* stream);
 
+/* ---- Image metrics of the evaluation loop (tensoir_amd/metrics.py; restated in numpy by tests/metrics_reference.py).
+ * tir_ssim: the reference's rgb_ssim (utils.py:93-139) for N image pairs.  img0, img1 [N][H][W][C] fp32 on the device, channel
+ *   last, 1 <= C <= 4.  taps: n_taps doubles in HOST memory, read during the call (they travel with the launch); the filtered value
+ *   of z at output (i, j) is  sum_k taps[k] (sum_l taps[l] z[i + k][j + l])  over the n_taps x n_taps window whose first pixel is
+ *   (i, j) ("valid" filtering: the map is [N][H - n_taps + 1][W - n_taps + 1][C]).
+ *   Arithmetic: x x, y y and x y are fp32 products, each rounded on its own (the reference squares fp32 images in fp32); they and
+ *   x, y are widened to double, and every sum is a double sum: over l first, then over k, each in ascending order (products and
+ *   sums may be fused).  With the filtered m0, m1, e00, e11, e01, every step rounded on its own:
+ *     mu00 = m0 m0; mu11 = m1 m1; mu01 = m0 m1; s00 = max(0, e00 - mu00); s11 = max(0, e11 - mu11); s01 = e01 - mu01;
+ *     s01 = sign(s01) min(sqrt(s00 s11), |s01|);  value = ((2 mu01 + c1) (2 s01 + c2)) / ((mu00 + mu11 + c1) (s00 + s11 + c2)).
+ *   map (may be null): every value, double.  mean [N], double, written on the device: the sum of the image's values / their count.
+ *   One workgroup per TIR_SSIM_TILE x TIR_SSIM_TILE tile of the map.  The mean is a fixed-order sum: per-workgroup partials in
+ *   `workspace`, added in tile order by the workgroup that finishes the image last.  No floating-point atomics: two calls give
+ *   identical bits, and an image's results do not depend on what else is in the batch.  workspace: tir_ssim_workspace(...) doubles
+ *   (8-byte aligned) the entry owns during the call; it may hold anything.  Nothing is allocated and the host does not wait.
+ * tir_image_error: a, b [N][P][C] fp32, mask null or [N][P] uint8 (a pixel counts where its byte is not 0) -> out [N][3] double:
+ *   {pixels counted, sum over them and their C channels of (a - b)^2 formed in double, sum over them of the angle in degrees}.  The
+ *   angle is acos(clamp((a0 b0 + a1 b1) + a2 b2, -1, 1)) 180 / pi in double for C = 3 and angular != 0, else the third number is
+ *   0; nothing is normalised.  The same tail: TIR_IMAGE_ERROR_SHARE pixels per workgroup, at most 256 workgroups per image.
+ * Both validate on the host before any device work: a negative size, n_taps outside [1, TIR_SSIM_MAX_TAPS] or larger than H or W,
+ *   and with N > 0 a null pointer (map and mask may be null; a, b too when P = 0) -> TIR_ERR_ARG; C outside [1, 4], or more than
+ *   2^31 workgroups -> TIR_ERR_UNSUPPORTED (the workspace sizes return the same codes).  N = 0 does nothing. */
+#define TIR_SSIM_TILE 16
+#define TIR_SSIM_MAX_TAPS 31
+#define TIR_IMAGE_ERROR_SHARE 2048
+int64_t tir_ssim_workspace(int64_t N, int32_t H, int32_t W, int32_t C, int32_t n_taps);
+int tir_ssim(const float* img0, const float* img1, int64_t N, int32_t H, int32_t W, int32_t C, const double* taps, int32_t n_taps,
+             double c1, double c2, double* map, double* workspace, double* mean, void* stream);
+int64_t tir_image_error_workspace(int64_t N, int64_t P);
+int tir_image_error(const float* a, const float* b, const uint8_t* mask, int64_t N, int64_t P, int32_t C, int32_t angular,
+                    double* workspace, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

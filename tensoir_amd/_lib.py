@@ -182,6 +182,10 @@ SIGNATURES = {
     "tir_shadow_maps": (C.c_int, [P, I64, P, I64, P, I32, I32, P, P, I32, P, P]),
     "tir_shadow_lookup": (C.c_int, [P, P, P, P, P, I64, I32, I32, F32, F32, P, P]),
     "tir_light_gbuffer_shadowed": (C.c_int, [P, P, P, P, P, P, I64, I32, I32, F32, F32, F32, I32, P, P]),
+    "tir_ssim_workspace": (I64, [I64, I32, I32, I32, I32]),
+    "tir_ssim": (C.c_int, [P, P, I64, I32, I32, I32, P, I32, C.c_double, C.c_double, P, P, P, P]),
+    "tir_image_error_workspace": (I64, [I64, I64]),
+    "tir_image_error": (C.c_int, [P, P, P, I64, I64, I32, I32, P, P, P]),
 }
 
 _lib = None

@@ -1963,3 +1963,53 @@ def light_gbuffer_shadowed(gbuf, view, cells, pts, frames, maps, bias, fresnel=0
           gbuf.numel() // RASTER_ROW, cells.shape[0], maps.shape[1], float(bias[0]), float(bias[1]), float(fresnel), flags, _ptr(out),
           _stream())
     return out
+
+
+# ---- image metrics (tensoir_amd/metrics.py) -----------------------------------------------------------------------
+SSIM_TILE = 16                   # TIR_SSIM_TILE: the side of the output tile one workgroup of tir_ssim computes
+SSIM_MAX_TAPS = 31               # TIR_SSIM_MAX_TAPS
+IMAGE_ERROR_SHARE = 2048         # TIR_IMAGE_ERROR_SHARE: pixels per workgroup of tir_image_error (at most 256 workgroups per image)
+
+
+def _workspace(doubles, dev):
+    if doubles < 0:
+        check(int(doubles), "metrics workspace")
+    return torch.empty((int(doubles),), dtype=torch.float64, device=dev)
+
+
+def ssim(img0, img1, taps, c1, c2, return_map=False):
+    """tir_ssim: img0, img1 [N, H, W, C] f32 on the device (1 <= C <= 4), taps: a float64 numpy vector of 1..SSIM_MAX_TAPS filter
+    weights (host) -> mean [N] float64 on the device, and with return_map also the map [N, H - n + 1, W - n + 1, C] float64.  fp32
+    products, double sums, a fixed-order mean (see the header); the host does not wait."""
+    img0, img1 = f32(img0, "img0"), f32(img1, "img1")
+    if img0.dim() != 4 or img0.shape != img1.shape or img0.device != img1.device:
+        raise ValueError(f"ssim: two [N, H, W, C] images of one shape on one device, got {tuple(img0.shape)} and {tuple(img1.shape)}")
+    taps = np.ascontiguousarray(taps, dtype=np.float64).reshape(-1)
+    N, H, W, Cn = img0.shape
+    n = taps.shape[0]
+    ws = _workspace(lib().tir_ssim_workspace(N, H, W, Cn, n), img0.device)          # the library words a refusal of the shape
+    mean = torch.empty((N,), dtype=torch.float64, device=img0.device)
+    smap = torch.empty((N, H - n + 1, W - n + 1, Cn), dtype=torch.float64, device=img0.device) if return_map else None
+    with torch.cuda.device(img0.device):
+        _call("tir_ssim", _ptr(img0), _ptr(img1), N, H, W, Cn, C.c_void_p(taps.ctypes.data), n, float(c1), float(c2), _ptr(smap), _ptr(ws),
+              _ptr(mean), _stream())
+    return (mean, smap) if return_map else mean
+
+
+def image_error(a, b, mask=None, angular=False):
+    """tir_image_error: a, b [N, P, C] f32 on the device, mask None or [N, P] uint8 / bool -> [N, 3] float64 on the device:
+    {pixels counted, sum of (a - b)^2 over them and their channels, sum of acos(clamp(a . b, -1, 1)) in degrees (C = 3 with
+    angular, else 0)}.  Nothing is normalised; fixed-order sums; the host does not wait."""
+    a, b = f32(a, "a"), f32(b, "b")
+    if a.dim() != 3 or a.shape != b.shape or a.device != b.device:
+        raise ValueError(f"image_error: two [N, P, C] images of one shape on one device, got {tuple(a.shape)} and {tuple(b.shape)}")
+    N, P, Cn = a.shape
+    if mask is not None:
+        mask = _req(mask.view(torch.uint8) if mask.dtype == torch.bool else mask, torch.uint8, "mask")
+        if mask.shape != (N, P) or mask.device != a.device:
+            raise ValueError("image_error: mask is [N, P] on the images' device")
+    ws = _workspace(lib().tir_image_error_workspace(N, P), a.device)
+    out = torch.zeros((N, 3), dtype=torch.float64, device=a.device)
+    with torch.cuda.device(a.device):
+        _call("tir_image_error", _ptr(a), _ptr(b), _ptr(mask), N, P, Cn, int(bool(angular)), _ptr(ws), _ptr(out), _stream())
+    return out

@@ -287,7 +287,7 @@ def _mean(values):
 
 @torch.no_grad()
 def compare_asset(model, path, cameras=None, H=200, W=200, focal=None, n_views=8, grid=None, args=None, chunk=16384, light=None,
-                  light_rows=16, write_views=None, shadows=False, shadow_size=256, shadow_pixels=4096):
+                  light_rows=16, write_views=None, shadows=False, shadow_size=256, shadow_pixels=4096, ssim=False):
     """Render the field (Renderer_TensoIR_train under its own first light -- no novel illumination --, no white background,
     `chunk` rays per call) and the asset at `path` (render_glb, mapped to field coordinates with the lattice `grid`, default the
     model's gridSize) from the same cameras.  The renderer decodes albedo, roughness and normals only with is_relight=True, which
@@ -316,6 +316,9 @@ def compare_asset(model, path, cameras=None, H=200, W=200, focal=None, n_views=8
                       second_near, second_far) > 0.5 means lit.  Counted over the pairs that contribute on the asset side (n.L >
                       1e-6); nan when there are none.  Every other number is what it is without shadows: relit_psnr stays the
                       unshadowed comparison.
+    ssim (default False: the report is exactly the one above) adds
+      albedo_ssim     metrics.ssim (the reference's rgb_ssim, max_val 1) of the field's albedo_map against the asset's albedo over
+                      the whole frame, both set to 0 outside the pixels in both silhouettes: the one structural number of the report
     write_views (a directory, with light): every view's two images as view_KK_field.png / view_KK_asset.png, and with shadows
     the asset under its own shadows as view_KK_asset_shadowed.png.
     cameras: [n, 3, 4]; default orbit_cameras(model.aabb, n_views) at the middle of the model's near / far range, with a focal
@@ -374,6 +377,10 @@ def compare_asset(model, path, cameras=None, H=200, W=200, focal=None, n_views=8
             v["depth_rmse"] = float((((ret["depth_map"].reshape(H, W)[both] - a["depth"][both]).double() / step) ** 2).mean().sqrt())
         else:
             v.update({k: float("nan") for k in ("albedo_psnr", "roughness_rmse", "normal_deg", "depth_rmse")})
+        if ssim:
+            from . import metrics
+            keep = both[..., None].to(torch.float32)
+            v["albedo_ssim"] = float(metrics.ssim(ret["albedo_map"].reshape(H, W, 3) * keep, a["albedo"] * keep))
         if cells is not None:
             lit = []
             v["relit_psnr"] = relit_psnr(field_gbuffer(ret, H * W), gbuf.view(-1, ops.RASTER_ROW), (-rays[:, 3:6]).contiguous(), cells,
@@ -391,6 +398,6 @@ def compare_asset(model, path, cameras=None, H=200, W=200, focal=None, n_views=8
                 _write_view(os.path.join(write_views, f"view_{k:02d}_asset_shadowed.png"), img[:, 0:3].reshape(H, W, 3))
         views.append(v)
     keys = ("iou", "pixels", "albedo_psnr", "roughness_rmse", "normal_deg", "depth_rmse") + (() if cells is None else ("relit_psnr",)) + \
-           (() if smaps is None else ("shadow_agreement",))
+           (() if smaps is None else ("shadow_agreement",)) + (("albedo_ssim",) if ssim else ())
     mean = {k: _mean([v[k] for v in views if math.isfinite(v[k])]) for k in keys}
     return {"views": views, "mean": mean, "H": int(H), "W": int(W), "focal": float(focal), "n_views": len(views)}

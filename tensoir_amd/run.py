@@ -64,6 +64,8 @@ def install(reference_root: str):
         from tensoir_amd import optim
         torch.optim.Adam = optim.LauncherAdam       # the script's optimizer: one launch; anything unsupported: torch's own step
         done["torch.optim"] = ["Adam"]
+    if _rebind_metrics(reference_root):
+        done["utils"] = ["rgb_ssim"]
     # The training rays stay resident in HBM (batches are gathered on the device: only the 32 KB index tensor crosses PCIe per
     # step) whenever the ray table fits -- TENSOIR_DEVICE_DATASET = auto (default: rays + colours + light indices below a quarter
     # of the free HBM; 100 views of 800 x 800 are 2.6 GB of 288), 1 (always), 0 (the script's host tensors)
@@ -83,6 +85,37 @@ def install(reference_root: str):
         done["tensoir_amd.dist"] = ["LAUNCHER_DP"]
     _allow_numpy_in_checkpoints()
     return done
+
+
+def _rebind_metrics(reference_root: str) -> bool:
+    """The evaluation loops call utils.rgb_ssim four times per test view (renderer.py:305-321): five separable filters per channel
+    through scipy on one host thread.  With a GPU (and unless TENSOIR_HOST_METRICS=1) the reference's utils.rgb_ssim, and the same
+    function object wherever an already imported reference module holds it (renderer does `from utils import *`), become
+    metrics.rgb_ssim.  A `utils` that does not come from reference_root is left alone.  -> whether anything was rebound."""
+    import torch
+    if not torch.cuda.is_available() or os.environ.get("TENSOIR_HOST_METRICS", "0") == "1":
+        return False
+    try:
+        utils = importlib.import_module("utils")
+    except ImportError:
+        return False
+    root = os.path.join(os.path.realpath(reference_root), "")
+
+    def under(m):
+        try:
+            return os.path.realpath(getattr(m, "__file__", None) or os.sep).startswith(root)
+        except Exception:                           # a lazy module that fails to load on attribute access is not the reference's
+            return False
+    old = getattr(utils, "rgb_ssim", None)
+    if not under(utils) or old is None:
+        return False
+    from tensoir_amd import metrics
+    for m in list(sys.modules.values()):
+        if m is not None and under(m):
+            for name, value in list(vars(m).items()):
+                if value is old:
+                    setattr(m, name, metrics.rgb_ssim)
+    return True
 
 
 def _local_rank(argv=None) -> int:
