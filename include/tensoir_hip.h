@@ -1139,6 +1139,42 @@ int64_t tir_image_error_workspace(int64_t N, int64_t P);
 int tir_image_error(const float* a, const float* b, const uint8_t* mask, int64_t N, int64_t P, int32_t C, int32_t angular,
                     double* workspace, double* out, void* stream);
 
+/* ---- Total-variation regulariser of the VM planes (tensoir_amd/regularisers.py; restated in float64 by
+ * tests/regulariser_reference.py): the reference's TVLoss (utils.py:143-162) over up to TIR_TV_MAX_PLANES planes, one launch forward
+ * and one launch backward for the whole list.
+ * planes, C, H, W, coef (and grads): arrays of n_planes entries in HOST memory, read during the call (they travel with the launch).
+ *   Plane p is fp32 [1, C, H, W] in channel-last storage, [H][W][C] in device memory, H >= 2 and W >= 2, fewer than 2^31 elements.
+ *   With  Sh = sum (x[h+1][w][c] - x[h][w][c])^2,  Sw = sum (x[h][w+1][c] - x[h][w][c])^2,  nh = C (H - 1) W,  nw = C H (W - 1):
+ * tir_tv_fwd:  sums [n_planes][2] double = {Sh, Sw} per plane, and  loss (fp32) = sum_p coef[p] 2 (Sh_p / nh_p + Sw_p / nw_p).
+ *   Arithmetic: the subtraction and the square are fp32 operations, each rounded on its own (the reference squares fp32
+ *   differences in fp32); every term is widened to double and every sum is a double sum in a fixed order: a workgroup owns a
+ *   contiguous share of one plane's floats (TIR_TV_SHARE of them, or more where the plane would otherwise get more than
+ *   TIR_TV_FWD_GROUPS workgroups: a function of the plane's size alone) and leaves two double partials in `workspace`; the
+ *   workgroup that draws the launch's last ticket adds each plane's partials in an order fixed by the plane's workgroup count,
+ *   forms the loss in double in the order written above, plane by plane (no step fused with another), and rounds it once.  No floating-point atomics: two calls give identical bits, and a
+ *   plane's sums do not depend on what else is in the call.  workspace: tir_tv_workspace(...) doubles (8-byte aligned) the entry
+ *   owns during the call; it may hold anything.  Nothing is allocated and the host does not wait.
+ * tir_tv_bwd:  grads[p] (same storage as plane p; null: the plane is skipped) receives, for the upstream gradient *g (ONE fp32 on
+ *   the DEVICE, read by the kernel: the host never sees it),
+ *     grad[h][w][c] = sh (dmh - dph) + sw (dmw - dpw),   sh = g ah,  sw = g aw   (fp32, each product rounded on its own),
+ *     ah = fp32(4 coef[p] / nh),  aw = fp32(4 coef[p] / nw)   (formed in double on the host, rounded once),
+ *     dph = x[h+1] - x[h] (0 on the last row),  dmh = x[h] - x[h-1] (0 on the first row),  dpw, dmw the same along W,
+ *   every difference an fp32 subtraction rounded on its own; the final expression is fp32 and may fuse.  The stencil is recomputed
+ *   from the plane; every element of grads[p] is written exactly once (no memset, no atomics).  grads[p] must not overlap a plane.
+ * Both take 16-byte loads and stores on a plane with C % 4 == 0 whose tensors are 16-byte aligned, scalar ones otherwise.
+ * Validation on the host before any device work: n_planes outside [0, TIR_TV_MAX_PLANES] -> TIR_ERR_ARG; n_planes = 0 does
+ *   nothing (TIR_OK; the workspace size is 1); then a null C / H / W, C < 1, H < 2 or W < 2 -> TIR_ERR_ARG; a null planes, coef,
+ *   workspace, sums, loss, g, grads or planes[p] -> TIR_ERR_ARG; a plane of 2^31 elements or more (which also keeps the launch far below 2^31
+ *   workgroups) -> TIR_ERR_UNSUPPORTED (tir_tv_workspace returns the same codes). */
+#define TIR_TV_MAX_PLANES 8
+#define TIR_TV_SHARE 8192
+#define TIR_TV_FWD_GROUPS 128
+int64_t tir_tv_workspace(int32_t n_planes, const int32_t* C, const int32_t* H, const int32_t* W);
+int tir_tv_fwd(const float* const* planes, const int32_t* C, const int32_t* H, const int32_t* W, const double* coef, int32_t n_planes,
+               double* workspace, double* sums, float* loss, void* stream);
+int tir_tv_bwd(const float* const* planes, const int32_t* C, const int32_t* H, const int32_t* W, const double* coef, int32_t n_planes,
+               const float* g, float* const* grads, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

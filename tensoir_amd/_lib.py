@@ -186,6 +186,9 @@ SIGNATURES = {
     "tir_ssim": (C.c_int, [P, P, I64, I32, I32, I32, P, I32, C.c_double, C.c_double, P, P, P, P]),
     "tir_image_error_workspace": (I64, [I64, I64]),
     "tir_image_error": (C.c_int, [P, P, P, I64, I64, I32, I32, P, P, P]),
+    "tir_tv_workspace": (I64, [I32, P, P, P]),
+    "tir_tv_fwd": (C.c_int, [P, P, P, P, P, I32, P, P, P, P]),
+    "tir_tv_bwd": (C.c_int, [P, P, P, P, P, I32, P, P, P]),
 }
 
 _lib = None

@@ -1008,4 +1008,33 @@ __device__ __forceinline__ void record_sum(const float* __restrict__ rec_w, cons
 }
 constexpr int RECORD_GROUP = 8;        // records per wait of record_sum
 
+// ---- the deterministic tail of the reducing kernels (tir_metrics.hip, tir_regularise.hip): per-workgroup double partials, one
+// ticket per result, and the workgroup that draws the last ticket adds the partials in index order -- no floating-point atomics.
+// Workgroups of TIR_TAIL_THREADS threads (four waves).  The entry point arms the tickets with a hipMemsetAsync.
+#define TIR_TAIL_THREADS 256
+
+// Sum over the workgroup in a fixed order: xor tree inside each wave, then the four waves left to right.  Every thread calls it;
+// thread 0 holds the result.  s4: 4 doubles of LDS.
+__device__ __forceinline__ double block_sum(double v, double* s4) {
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
+    __syncthreads();                                     // s4 may still be read from the previous call
+    if ((threadIdx.x & 63) == 0) s4[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return (s4[0] + s4[1]) + (s4[2] + s4[3]);
+}
+
+// Thread 0 has published this workgroup's K partials with write-through stores; it draws the image's ticket.  -> true in
+// every thread of the workgroup that drew the last of `per_image` tickets; that workgroup re-arms the ticket.
+__device__ __forceinline__ bool last_of_image(int32_t* ticket, int per_image, int* s_last) {
+    if (threadIdx.x == 0) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // the partials have landed
+        const int t = __hip_atomic_fetch_add(ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        *s_last = (t == per_image - 1);
+        if (*s_last) __hip_atomic_store(ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    __syncthreads();
+    return *s_last != 0;
+}
+
 }  // namespace tir

@@ -10,35 +10,14 @@
 // adds that image's partials in index order -- no floating-point atomics; a result depends on nothing but its own image.
 #include "tir_common.hpp"
 
-#define TIR_METRIC_THREADS 256
+#define TIR_METRIC_THREADS TIR_TAIL_THREADS
 static_assert(TIR_SSIM_TILE * TIR_SSIM_TILE == TIR_METRIC_THREADS && TIR_SSIM_TILE == 16, "k_ssim: one output per thread, rows of 16");
 
 namespace {
 
-// ---- the deterministic tail ---------------------------------------------------------------------------------------------------
-// Sum over the workgroup in a fixed order: xor tree inside each wave, then the four waves left to right.  Every thread calls it;
-// thread 0 holds the result.  s4: 4 doubles of LDS.
-__device__ __forceinline__ double block_sum(double v, double* s4) {
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
-    __syncthreads();                                     // s4 may still be read from the previous call
-    if ((threadIdx.x & 63) == 0) s4[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (s4[0] + s4[1]) + (s4[2] + s4[3]);
-}
-
-// Thread 0 has published this workgroup's K partials with write-through stores (below); it draws the image's ticket.  -> true in
-// every thread of the workgroup that drew the last of `per_image` tickets; that workgroup re-arms the ticket.
-__device__ __forceinline__ bool last_of_image(int32_t* ticket, int per_image, int* s_last) {
-    if (threadIdx.x == 0) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // the partials have landed
-        const int t = __hip_atomic_fetch_add(ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        *s_last = (t == per_image - 1);
-        if (*s_last) __hip_atomic_store(ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    __syncthreads();
-    return *s_last != 0;
-}
+// ---- the deterministic tail: tir_common.hpp (shared with tir_regularise.hip) ------------------------------------------------------
+using tir::block_sum;
+using tir::last_of_image;
 
 // partial[i * stride] for i in [0, n) added by thread in strides of the workgroup, four loads in flight per wait, then block_sum
 __device__ __forceinline__ double sum_partials(const double* partial, int n, int stride, double* s4) {

@@ -3,8 +3,8 @@
 Same class names, constructor kwargs, parameter names/shapes (reference checkpoints load unchanged)
 and method signatures as ``models/tensoRF_rotated_lights.py`` + ``models/tensorBase_rotated_lights.py``;
 every per-sample computation is dispatched to libtensoir_hip.so (see tensoir_amd/ops.py).  What stays
-in PyTorch is what SURVEY.md section 8 leaves there: parameter containers, regularisers,
-up-sampling / shrinking, checkpoint I/O.
+in PyTorch is what SURVEY.md section 8 leaves there: parameter containers, the L1 and orthogonality regularisers,
+up-sampling / shrinking, checkpoint I/O (the total-variation regulariser: tensoir_amd/regularisers.py).
 """
 from __future__ import annotations
 
@@ -17,7 +17,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import capacity, indirect, ops
+from . import capacity, indirect, ops, regularisers
 from ._lib import TensoirHipError, TirField
 
 MAT_MODE = [[0, 1], [0, 2], [1, 2]]
@@ -58,12 +58,7 @@ def channel_last(t):
     return t.permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)
 
 
-def is_channel_last(p):
-    if p.dim() != 4 or p.shape[0] != 1 or p.dtype != torch.float32:
-        return False
-    _, c, h, w = p.shape
-    _, sc, sh, sw = p.stride()
-    return (c == 1 or sc == 1) and (w == 1 or sw == c) and (h == 1 or sh == w * c)
+is_channel_last = ops.is_channel_last      # [1, C, H, W] float32 stored as [H][W][C]: one definition, next to the kernels that need it
 
 
 def _wants_grad(what, *tensors):
@@ -577,10 +572,13 @@ class TensorVMSplit(nn.Module):
         return _DensityL1Fn.apply(*ts)
 
     def TV_loss_density(self, reg):
-        return sum((reg(plane) * 1e-2 for plane in self.density_plane), 0)
+        """:80-84: sum over the three density planes of reg(plane) * 1e-2.  A regularisers.TVLoss on GPU planes is one launch forward
+        and one backward for the three planes (regularisers.model_tv); any other callable is called plane by plane."""
+        return regularisers.model_tv(self.density_plane, reg)
 
     def TV_loss_app(self, reg):
-        return sum((reg(plane) * 1e-2 for plane in self.app_plane), 0)
+        """:87-91: the same over the three appearance planes."""
+        return regularisers.model_tv(self.app_plane, reg)
 
     # ---- packed shadow of the parameters -----------------------------------------------------------
     def _field_params(self):

@@ -2013,3 +2013,98 @@ def image_error(a, b, mask=None, angular=False):
     with torch.cuda.device(a.device):
         _call("tir_image_error", _ptr(a), _ptr(b), _ptr(mask), N, P, Cn, int(bool(angular)), _ptr(ws), _ptr(out), _stream())
     return out
+
+
+# ---- total-variation regulariser (tensoir_amd/regularisers.py) ----------------------------------------------------
+TV_MAX_PLANES = 8                # TIR_TV_MAX_PLANES: planes per launch
+TV_SHARE = 8192                  # TIR_TV_SHARE: floats of one plane per workgroup of tir_tv_bwd, and of tir_tv_fwd on a small plane
+TV_FWD_GROUPS = 128              # TIR_TV_FWD_GROUPS: tir_tv_fwd gives a plane at most this many workgroups (larger shares beyond)
+
+
+def is_channel_last(t):
+    """A [1, C, H, W] float32 tensor stored as [H][W][C] in memory -- the layout the kernels gather from (field_model.channel_last
+    makes one; a unit dimension's stride is free)."""
+    if t.dim() != 4 or t.shape[0] != 1 or t.dtype != torch.float32:
+        return False
+    _, c, h, w = t.shape
+    _, sc, sh, sw = t.stride()
+    return (c == 1 or sc == 1) and (w == 1 or sw == c) and (h == 1 or sh == w * c)
+
+
+def _on_device(t, dtype, name):
+    """_req's checks without its .contiguous(): a channel-last plane is not contiguous in torch's default format, and a copy of it
+    would be a plane-sized launch and allocation per call -- the planes are read in place."""
+    if not torch.is_tensor(t):
+        raise TypeError(f"{name}: expected a tensor")
+    if not t.is_cuda:
+        raise _lib.TensoirHipError(f"{name}: tensor must live on the GPU (got {t.device}); tensoir_amd has no CPU path")
+    if t.dtype != dtype:
+        raise TypeError(f"{name}: expected {dtype}, got {t.dtype}")
+
+
+class _TvCall:
+    """The one place the TV entry points' arguments are validated and laid out: planes -> the host arrays of a call."""
+
+    def __init__(self, planes, coefs, what):
+        planes = list(planes)
+        n = len(planes)
+        if n > TV_MAX_PLANES or len(coefs) != n:
+            raise ValueError(f"{what}: at most {TV_MAX_PLANES} planes and one coefficient per plane, got {n} and {len(coefs)}")
+        for i, t in enumerate(planes):
+            _on_device(t, torch.float32, f"{what}: plane {i}")
+            if not is_channel_last(t) or t.shape[2] < 2 or t.shape[3] < 2 or t.device != planes[0].device:
+                raise ValueError(f"{what}: plane {i} must be [1, C, H >= 2, W >= 2] in channel-last storage on one device, got "
+                                 f"{tuple(t.shape)} with strides {tuple(t.stride())} on {t.device}")
+        self.n, self.planes = n, planes
+        self.device = planes[0].device if n else None
+        self.ptrs = (C.c_void_p * n)(*[t.data_ptr() for t in planes])
+        self.C = (C.c_int32 * n)(*[t.shape[1] for t in planes])
+        self.H = (C.c_int32 * n)(*[t.shape[2] for t in planes])
+        self.W = (C.c_int32 * n)(*[t.shape[3] for t in planes])
+        self.coef = (C.c_double * n)(*[float(c) for c in coefs])
+
+
+def tv_forward(planes, coefs):
+    """tir_tv_fwd: planes, a list of at most TV_MAX_PLANES float32 [1, C, H, W] device tensors in channel-last storage (H, W >= 2),
+    coefs one host float per plane -> (loss, a 0-dim float32 = sum_p coefs[p] 2 (Sh_p / nh_p + Sw_p / nw_p), sums [n, 2] float64 =
+    {Sh_p, Sw_p}), both on the device.  One launch; fp32 differences and squares, double sums in a fixed order (see the header);
+    the host does not wait."""
+    call = _TvCall(planes, coefs, "tv_forward")
+    if call.n == 0:
+        raise ValueError("tv_forward: no planes")
+    ws = _workspace(lib().tir_tv_workspace(call.n, call.C, call.H, call.W), call.device)
+    sums = torch.empty((call.n, 2), dtype=torch.float64, device=call.device)
+    loss = torch.empty((), dtype=torch.float32, device=call.device)
+    with torch.cuda.device(call.device):
+        _call("tir_tv_fwd", call.ptrs, call.C, call.H, call.W, call.coef, call.n, _ptr(ws), _ptr(sums), _ptr(loss), _stream())
+    return loss, sums
+
+
+def tv_backward(planes, coefs, g, needs=None, out=None):
+    """tir_tv_bwd: the gradient of tv_forward's loss times the DEVICE scalar g (float32, one element; never read on the host) for
+    every plane p with needs[p] (default: all) -> a list with a channel-last [1, C, H, W] tensor per wanted plane and None for the
+    others.  out: optional list of channel-last tensors to write into (None entries are skipped like needs[p] = False).  One
+    launch; every element of a wanted gradient is written, nothing else is touched."""
+    call = _TvCall(planes, coefs, "tv_backward")
+    g = _req(g, torch.float32, "tv_backward: g")
+    if g.numel() != 1 or (call.n and g.device != call.device):
+        raise ValueError(f"tv_backward: g is one float32 on the planes' device, got {tuple(g.shape)} on {g.device}")
+    if out is None:
+        needs = [True] * call.n if needs is None else list(needs)
+        if len(needs) != call.n:
+            raise ValueError("tv_backward: one flag per plane")
+        out = [torch.empty((1, t.shape[2], t.shape[3], t.shape[1]), dtype=torch.float32, device=t.device).permute(0, 3, 1, 2)
+               if want else None for t, want in zip(call.planes, needs)]
+    else:
+        out = list(out)
+        if len(out) != call.n:
+            raise ValueError("tv_backward: one output (or None) per plane")
+        for i, (o, t) in enumerate(zip(out, call.planes)):
+            if o is not None and (not torch.is_tensor(o) or o.shape != t.shape or o.device != t.device or not is_channel_last(o)):
+                raise ValueError(f"tv_backward: out[{i}] must be a channel-last float32 tensor of plane {i}'s shape and device")
+    if call.n == 0 or all(o is None for o in out):
+        return out
+    grads = (C.c_void_p * call.n)(*[None if o is None else o.data_ptr() for o in out])
+    with torch.cuda.device(call.device):
+        _call("tir_tv_bwd", call.ptrs, call.C, call.H, call.W, call.coef, call.n, _ptr(g), grads, _stream())
+    return out

@@ -66,6 +66,8 @@ def install(reference_root: str):
         done["torch.optim"] = ["Adam"]
     if _rebind_metrics(reference_root):
         done["utils"] = ["rgb_ssim"]
+    if _rebind_tv(reference_root):
+        done.setdefault("utils", []).append("TVLoss")
     # The training rays stay resident in HBM (batches are gathered on the device: only the 32 KB index tensor crosses PCIe per
     # step) whenever the ray table fits -- TENSOIR_DEVICE_DATASET = auto (default: rays + colours + light indices below a quarter
     # of the free HBM; 100 views of 800 x 800 are 2.6 GB of 288), 1 (always), 0 (the script's host tensors)
@@ -87,17 +89,13 @@ def install(reference_root: str):
     return done
 
 
-def _rebind_metrics(reference_root: str) -> bool:
-    """The evaluation loops call utils.rgb_ssim four times per test view (renderer.py:305-321): five separable filters per channel
-    through scipy on one host thread.  With a GPU (and unless TENSOIR_HOST_METRICS=1) the reference's utils.rgb_ssim, and the same
-    function object wherever an already imported reference module holds it (renderer does `from utils import *`), become
-    metrics.rgb_ssim.  A `utils` that does not come from reference_root is left alone.  -> whether anything was rebound."""
-    import torch
-    if not torch.cuda.is_available() or os.environ.get("TENSOIR_HOST_METRICS", "0") == "1":
-        return False
+def _rebind_reference_object(reference_root: str, module: str, name: str, new) -> bool:
+    """`module`.`name` of the reference, and the same object wherever an already imported reference module holds it (the scripts
+    and renderer do `from utils import *`), become `new`.  A module counts as the reference's when its file lies under
+    reference_root: a `module` from anywhere else is left alone.  -> whether anything was rebound."""
     try:
-        utils = importlib.import_module("utils")
-    except ImportError:
+        mod = importlib.import_module(module)
+    except Exception:                               # absent, or a `module` from elsewhere that fails on import: nothing of the reference's
         return False
     root = os.path.join(os.path.realpath(reference_root), "")
 
@@ -106,16 +104,38 @@ def _rebind_metrics(reference_root: str) -> bool:
             return os.path.realpath(getattr(m, "__file__", None) or os.sep).startswith(root)
         except Exception:                           # a lazy module that fails to load on attribute access is not the reference's
             return False
-    old = getattr(utils, "rgb_ssim", None)
-    if not under(utils) or old is None:
+    old = getattr(mod, name, None)
+    if not under(mod) or old is None:
         return False
-    from tensoir_amd import metrics
     for m in list(sys.modules.values()):
         if m is not None and under(m):
-            for name, value in list(vars(m).items()):
+            for key, value in list(vars(m).items()):
                 if value is old:
-                    setattr(m, name, metrics.rgb_ssim)
+                    setattr(m, key, new)
     return True
+
+
+def _rebind_metrics(reference_root: str) -> bool:
+    """The evaluation loops call utils.rgb_ssim four times per test view (renderer.py:305-321): five separable filters per channel
+    through scipy on one host thread.  With a GPU (and unless TENSOIR_HOST_METRICS=1) the reference's utils.rgb_ssim, and the same
+    function object wherever an already imported reference module holds it (renderer does `from utils import *`), become
+    metrics.rgb_ssim.  A `utils` that does not come from reference_root is left alone.  -> whether anything was rebound."""
+    import torch
+    if not torch.cuda.is_available() or os.environ.get("TENSOIR_HOST_METRICS", "0") == "1":
+        return False
+    from tensoir_amd import metrics
+    return _rebind_reference_object(reference_root, "utils", "rgb_ssim", metrics.rgb_ssim)
+
+
+def _rebind_tv(reference_root: str) -> bool:
+    """The training scripts build `tvreg = TVLoss()` from utils (train_tensoIR.py:222) and hand it to TV_loss_density / TV_loss_app in
+    every iteration up to the first alpha-mask update.  Unless TENSOIR_TORCH_TV=1 the reference's utils.TVLoss, wherever a reference
+    module holds it, becomes regularisers.TVLoss: the model methods then take one launch per call.  No GPU is needed
+    for the rebinding: on host tensors the class evaluates the reference's expression.  -> whether anything was rebound."""
+    if os.environ.get("TENSOIR_TORCH_TV", "0") == "1":
+        return False
+    from tensoir_amd import regularisers
+    return _rebind_reference_object(reference_root, "utils", "TVLoss", regularisers.TVLoss)
 
 
 def _local_rank(argv=None) -> int:
