@@ -629,7 +629,8 @@ int tir_march_primary_train_fwd(const TirField* f, const float* rays, const floa
 /* Backward of tir_composite_primary (models/tensorBase_rotated_lights.py:973-1031).
  * g_maps [B][20]: d loss / d out_maps.  Outputs (written, not accumulated): per-record gradients g_rgb [A][3],
  * g_brdf [A][4] (w.r.t. the raw sigmoid outputs), g_brdf_jit [A][4], g_pred [A][3], g_der [A][3] (NULL where the
- * forward input was NULL); g_weight [B][S] dense, MUST be zero-filled by the caller -- receives the record
+ * forward input was NULL; zeros where the input was given but the branch does not use it: everything but rgb with
+ * is_relight == 0, derived_normal without pred_normal); g_weight [B][S] dense, MUST be zero-filled by the caller -- receives the record
  * part of d loss / d weight at (ray, rec_k); g_acc [B], g_depth [B]: gradients of the dense sums
  * acc = sum w, depth = sum w z. */
 int tir_composite_primary_bwd(const float* rays, const int32_t* offsets, const int32_t* rec_k,

@@ -464,6 +464,14 @@ k_composite_primary_bwd(const float* __restrict__ rays, const int32_t* __restric
 #pragma unroll
             for (int q = 0; q < 3; ++q) { gw = fmaf(rgb[3 * (size_t)i + q], gc[q], gw); g_rgb[3 * (size_t)i + q] = w * gc[q]; }
         }
+        // inputs the forward was given but did not use on this branch: their gradient is zero, and it is written (the outputs
+        // are not accumulated into, so the caller does not clear them)
+        if (g_der && der_n && !(is_relight && pred_n)) { g_der[3 * (size_t)i] = 0.f; g_der[3 * (size_t)i + 1] = 0.f; g_der[3 * (size_t)i + 2] = 0.f; }
+        if (!is_relight) {
+            if (g_brdf && brdf) { g_brdf[4 * (size_t)i] = 0.f; g_brdf[4 * (size_t)i + 1] = 0.f; g_brdf[4 * (size_t)i + 2] = 0.f; g_brdf[4 * (size_t)i + 3] = 0.f; }
+            if (g_brdf_jit && brdf_jit) { g_brdf_jit[4 * (size_t)i] = 0.f; g_brdf_jit[4 * (size_t)i + 1] = 0.f; g_brdf_jit[4 * (size_t)i + 2] = 0.f; g_brdf_jit[4 * (size_t)i + 3] = 0.f; }
+            if (g_pred && pred_n) { g_pred[3 * (size_t)i] = 0.f; g_pred[3 * (size_t)i + 1] = 0.f; g_pred[3 * (size_t)i + 2] = 0.f; }
+        }
         if (is_relight) {
             float a3[3] = {0, 0, 0}, rg = 0.f;
             float gb[4] = {0, 0, 0, 0}, gbj[4] = {0, 0, 0, 0};

@@ -762,16 +762,22 @@ def exclusive_scan_capped(counts, cap):
     return off, total
 
 
-def compact_primary(field: TirField, rays, ray_jitter, weight, offsets, total):
+def compact_primary(field: TirField, rays, ray_jitter, weight, offsets, total, out=None):
+    """out: caller-owned (rec_ray, rec_k, rec_w, rec_xyz) of at least offsets[-1] records, written in place of fresh buffers."""
     rays = f32(rays, "rays", 6)
     B, S = weight.shape
     dev = rays.device
     if ray_jitter is not None:
         ray_jitter = f32(ray_jitter, "ray_jitter").view(-1)
-    rec_ray = torch.empty((total,), dtype=torch.int32, device=dev)
-    rec_k = torch.empty((total,), dtype=torch.int32, device=dev)
-    rec_w = torch.empty((total,), dtype=torch.float32, device=dev)
-    rec_xyz = torch.empty((total, 3), dtype=torch.float32, device=dev)
+    if out is not None:
+        rec_ray, rec_k, rec_w, rec_xyz = i32(out[0], "rec_ray"), i32(out[1], "rec_k"), f32(out[2], "rec_w"), f32(out[3], "rec_xyz", 3)
+        if min(rec_ray.numel(), rec_k.numel(), rec_w.numel(), rec_xyz.shape[0]) < total:
+            raise ValueError("compact_primary: out buffers hold fewer than `total` records")
+    else:
+        rec_ray = torch.empty((total,), dtype=torch.int32, device=dev)
+        rec_k = torch.empty((total,), dtype=torch.int32, device=dev)
+        rec_w = torch.empty((total,), dtype=torch.float32, device=dev)
+        rec_xyz = torch.empty((total, 3), dtype=torch.float32, device=dev)
     if total > 0:
         _call("tir_compact_primary", C.byref(field), _ptr(rays), _ptr(ray_jitter), _ptr(weight),
                                         _ptr(offsets), B, S, _ptr(rec_ray), _ptr(rec_k), _ptr(rec_w),
@@ -794,9 +800,10 @@ def composite_primary(rays, offsets, rec_w, rgb, brdf, brdf_jit, pred_n, der_n, 
 # ---- secondary march ------------------------------------------------------------------------------
 def march_secondary(field: TirField, origins, dirs, z_vals, n_rays, org_map=None, dir_map=None,
                     active=None, t_stop=0.0, want_records=False, rec_cap=0, want_nerfactor=True, n_dirs=0,
-                    ray_ids=None, n_ids_dev=None, vis=None, rec_cnt=None, counter=None):
-    """ray_ids / n_ids_dev: march only the listed pair ids (tir_march_secondary_ids_fwd); vis / rec_cnt: pre-filled
-    per-pair buffers (shade_setup_compact wrote the masked pairs' zeros into them)."""
+                    ray_ids=None, n_ids_dev=None, vis=None, rec_cnt=None, counter=None, oma=None, rec=None):
+    """ray_ids / n_ids_dev: march only the listed pair ids (tir_march_secondary_ids_fwd); vis / rec_cnt / oma: pre-filled
+    per-pair buffers (shade_setup_compact wrote the masked pairs' zeros into them); rec: the caller's record buffers (the dict
+    this returns: counter, ray, w, xyz, off, cnt), which may be longer than rec_cap."""
     origins = f32(origins, "origins", 3)
     dirs = f32(dirs, "dirs", 3)
     z_vals = f32(z_vals, "z_vals").view(-1)
@@ -808,9 +815,15 @@ def march_secondary(field: TirField, origins, dirs, z_vals, n_rays, org_map=None
         active = _req(active, torch.uint8, "active")
     if vis is None:
         vis = torch.empty((n_rays,), dtype=torch.float32, device=dev)
-    oma = torch.empty((n_rays,), dtype=torch.float32, device=dev) if want_nerfactor else None
-    rec = None
-    if want_records:
+    if oma is None:
+        oma = torch.empty((n_rays,), dtype=torch.float32, device=dev) if want_nerfactor else None
+    if not want_records:
+        rec = None
+    elif rec is not None:
+        if min(rec["ray"].numel(), rec["w"].numel(), rec["xyz"].shape[0]) < rec_cap or min(rec["off"].numel(), rec["cnt"].numel()) < n_rays:
+            raise ValueError("march_secondary: rec buffers smaller than rec_cap records / n_rays rays")
+        rec = dict(rec, cap=rec_cap)
+    else:
         rec = {
             # [total, written prefix]; `counter`: a caller-owned pair that is already zero on the device
             "counter": counter if counter is not None else torch.zeros((2,), dtype=torch.int32, device=dev),
