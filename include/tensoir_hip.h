@@ -1176,6 +1176,37 @@ int tir_tv_fwd(const float* const* planes, const int32_t* C, const int32_t* H, c
 int tir_tv_bwd(const float* const* planes, const int32_t* C, const int32_t* H, const int32_t* W, const double* coef, int32_t n_planes,
                const float* g, float* const* grads, void* stream);
 
+/* ---- Guided a-trous denoiser of relit views (tensoir_amd/denoise.py, relight.relight_view; restated in float64 by
+ * tests/denoise_reference.py): the edge-avoiding wavelet filter of Dammertz et al. 2010, guided by the noise-free maps of the
+ * primary pass.
+ * tir_denoise_guide: maps [n][20] (the primary pass's map rows: depth 3, normal 4:7, albedo 7:10, roughness 10, acc 14) and
+ *   rays [n][6] -> rows [row0, row0 + n) of guide [..][TIR_DENOISE_GUIDE] fp32, 16-byte aligned:
+ *     {pos.xyz = o + depth d (one fused multiply-add per component), valid = acc > acc_thres ? 1 : 0,
+ *      n.xyz = normal / max(|normal|, fp32(1e-6)) (|normal| = sqrt of the fp32 sum of squares), roughness, albedo.rgb, 0}.
+ *   One launch; no other row of guide is touched.
+ * tir_atrous_level: one level, out of place.  color_in, color_out [H W][K] fp32, the image row-major, K = 3 n_maps in
+ *   3..TIR_ATROUS_MAX_K (the rows relight_chunk writes: every map of a view is filtered by one launch); guide [H W][12] as above,
+ *   a pixel is valid where its fourth float exceeds 0.5.  An invalid pixel copies its input.  For a valid pixel p, over the taps
+ *   q = p + step (i, j), i, j in -2..2, that lie inside the image and are valid:
+ *     h   = k[|i|] k[|j|],  k = (3/8, 1/4, 1/16)
+ *     a   = max(0, 1 - n_p.n_q) inv_sn + |(x_q - x_p).n_p| inv_sp + |alb_p - alb_q|^2 inv_sa2 + (r_p - r_q)^2 inv_sr2
+ *     w_m = h exp(-(a + |c_p^m - c_q^m|^2 inv_sc2))  per map m      (inv_sc2 = 0: the colour term is off, one weight for all maps)
+ *     out_p^m = sum_q w_m c_q^m / sum_q w_m                          (the centre tap has w = 9/64: the denominator is never 0)
+ *   fp32 throughout, formed as c_p + sum_q w_m (c_q - c_p) / sum_q w_m with the centre tap's weight taken as 9/64 exactly: a
+ *   pixel without a valid neighbour and a constant image are returned bit for bit.  The taps are added in the fixed order j,
+ *   then i, one fused multiply-add per channel; no atomics and nothing
+ *   that depends on the launch shape: two calls give identical bits, and a map's result does not depend on the other maps of the
+ *   call (a K = 15 call equals five K = 3 calls bit for bit).  A step beyond the image's longer side leaves the centre tap.
+ * Both validate on the host before any device work: n < 0, row0 < 0, H or W < 1, K no multiple of 3 or outside 3..24, step < 1,
+ *   a negative or non-finite inv_*, a null pointer (n = 0 is asked for none and does nothing), color_in == color_out, a guide that
+ *   is not 16-byte aligned -> TIR_ERR_ARG; an image of 2^31 pixels or a side of 2^29 or more -> TIR_ERR_UNSUPPORTED.  Nothing is
+ *   allocated and the host does not wait. */
+#define TIR_DENOISE_GUIDE 12
+#define TIR_ATROUS_MAX_K 24
+int tir_denoise_guide(const float* maps, const float* rays, int64_t n, float acc_thres, float* guide, int64_t row0, void* stream);
+int tir_atrous_level(const float* color_in, float* color_out, const float* guide, int32_t H, int32_t W, int32_t K, int32_t step,
+                     float inv_sn, float inv_sp, float inv_sa2, float inv_sr2, float inv_sc2, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

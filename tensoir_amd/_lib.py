@@ -189,6 +189,8 @@ SIGNATURES = {
     "tir_tv_workspace": (I64, [I32, P, P, P]),
     "tir_tv_fwd": (C.c_int, [P, P, P, P, P, I32, P, P, P, P]),
     "tir_tv_bwd": (C.c_int, [P, P, P, P, P, I32, P, P, P]),
+    "tir_denoise_guide": (C.c_int, [P, P, I64, F32, P, I64, P]),
+    "tir_atrous_level": (C.c_int, [P, P, P, I32, I32, I32, I32, F32, F32, F32, F32, F32, P]),
 }
 
 _lib = None

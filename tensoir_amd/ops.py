@@ -2121,3 +2121,47 @@ def tv_backward(planes, coefs, g, needs=None, out=None):
     with torch.cuda.device(call.device):
         _call("tir_tv_bwd", call.ptrs, call.C, call.H, call.W, call.coef, call.n, _ptr(g), grads, _stream())
     return out
+
+
+# ---- guided a-trous denoiser (tensoir_amd/denoise.py) -------------------------------------------------------------
+DENOISE_GUIDE = 12               # TIR_DENOISE_GUIDE: floats of a guide row {pos.xyz, valid, n.xyz, roughness, albedo.rgb, 0}
+ATROUS_MAX_K = 24                # TIR_ATROUS_MAX_K: colour floats per pixel of one tir_atrous_level launch (eight maps)
+
+
+def denoise_guide(maps, rays, guide, row0, acc_thres=0.5):
+    """tir_denoise_guide: maps [B, 20] (the primary pass's map rows) and rays [B, 6] -> rows [row0, row0 + B) of guide [N, 12]
+    (or [H, W, 12]), written in place: {o + depth d, acc > acc_thres, the normalised normal, roughness, albedo, 0}.  One launch;
+    the host does not wait.  Returns guide."""
+    maps, rays = f32(maps, "maps", MAP_STRIDE), f32(rays, "rays", 6)
+    _req(guide, torch.float32, "guide", DENOISE_GUIDE)
+    B, row0 = maps.shape[0], int(row0)
+    if maps.dim() != 2 or rays.dim() != 2 or rays.shape[0] != B or not guide.is_contiguous():
+        raise ValueError(f"denoise_guide: maps [B, 20], rays [B, 6] and a contiguous guide, got {tuple(maps.shape)}, {tuple(rays.shape)}")
+    if row0 < 0 or row0 + B > guide.numel() // DENOISE_GUIDE or maps.device != guide.device or rays.device != guide.device:
+        raise ValueError(f"denoise_guide: rows [{row0}, {row0 + B}) must lie in a guide of {guide.numel() // DENOISE_GUIDE} rows "
+                         "on the device of maps and rays")
+    with torch.cuda.device(guide.device):
+        _call("tir_denoise_guide", _ptr(maps), _ptr(rays), B, float(acc_thres), _ptr(guide), row0, _stream())
+    return guide
+
+
+def atrous_level(color_in, color_out, guide, H, W, step, inv_sn, inv_sp, inv_sa2, inv_sr2, inv_sc2=0.0):
+    """tir_atrous_level: one level of the guided a-trous filter, out of place.  color_in, color_out [H * W, K] f32 (any shape of
+    H * W * K contiguous floats; K = 3 n_maps, 3..ATROUS_MAX_K), guide [H * W, 12] -> color_out.  step >= 1: the distance between
+    taps; inv_*: 1 / sigma_n, 1 / sigma_p, 1 / sigma_a^2, 1 / sigma_r^2, 1 / sigma_c^2 (0: no colour term).  fp32, a fixed
+    order of taps (see the header); the host does not wait."""
+    color_in, guide = f32(color_in, "color_in"), f32(guide, "guide", DENOISE_GUIDE)
+    _req(color_out, torch.float32, "color_out")
+    H, W = int(H), int(W)
+    if H < 1 or W < 1 or color_in.numel() % (H * W) or not color_out.is_contiguous():
+        raise ValueError(f"atrous_level: color_in holds {color_in.numel()} floats, no multiple of {H} x {W}; color_out is contiguous")
+    K = color_in.numel() // (H * W)
+    if color_out.numel() != color_in.numel() or guide.numel() != H * W * DENOISE_GUIDE:
+        raise ValueError(f"atrous_level: color_out takes {H * W * K} floats and guide {H * W} rows, got {color_out.numel()} and "
+                         f"{guide.numel() // DENOISE_GUIDE}")
+    if color_out.device != color_in.device or guide.device != color_in.device:
+        raise ValueError("atrous_level: color_in, color_out and guide live on one device")
+    with torch.cuda.device(color_in.device):
+        _call("tir_atrous_level", _ptr(color_in), _ptr(color_out), _ptr(guide), H, W, K, int(step), float(inv_sn), float(inv_sp),
+              float(inv_sa2), float(inv_sr2), float(inv_sc2), _stream())
+    return color_out

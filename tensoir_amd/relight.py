@@ -582,3 +582,67 @@ def relight_chunk(tensoIR, env, light_names, rays, light_idx, num_samples=512, n
                                          num_samples, nSample, vis_near, vis_far, m_dev=c["n_hit"])
         ops.env_compose(env.hdr_rgbs[name], rays, c["slot"], rgb, out, 3 * i)
     return out, prim, c
+
+
+# columns of a [B, 20] map row that tir_denoise_guide reads, as positions in TensorVMSplit.unpack_maps' tuple -> (column, width)
+_GUIDE_COLUMNS = {1: (3, 1), 2: (4, 3), 3: (7, 3), 4: (10, 1), 6: (14, 1)}
+
+
+def _map_rows(prim, B):
+    """[B, 20] map rows for tir_denoise_guide from the primary-pass tuple relight_chunk hands back.  unpack_maps returns column
+    views of one contiguous [B, 20] tensor: where depth, normal, albedo, roughness and acc still lie at their columns of one such
+    block (strides and addresses checked), that block is read in place; otherwise (a forward that returns copies) the rows are
+    assembled from those columns, the others zero -- the kernel reads no other column."""
+    cols = {i: prim[i] for i in _GUIDE_COLUMNS}
+    base = cols[1].data_ptr() - 4 * _GUIDE_COLUMNS[1][0]
+    in_place = B > 0 and all(t.dtype == torch.float32 and t.stride(0) == MAP_STRIDE and (t.dim() == 1 or t.stride(1) == 1)
+                             and t.data_ptr() == base + 4 * c for t, (c, _) in ((cols[i], _GUIDE_COLUMNS[i]) for i in cols))
+    first = cols[1].storage_offset() - _GUIDE_COLUMNS[1][0]            # element of the storage at which row 0 would begin
+    if in_place and first >= 0 and cols[1].untyped_storage().nbytes() >= 4 * (first + B * MAP_STRIDE):
+        return torch.as_strided(cols[1], (B, MAP_STRIDE), (MAP_STRIDE, 1), first)
+    maps = torch.zeros((B, MAP_STRIDE), dtype=torch.float32, device=cols[1].device)
+    for i, (c, w) in _GUIDE_COLUMNS.items():
+        maps[:, c:c + w] = cols[i].reshape(B, w)
+    return maps
+
+
+@torch.no_grad()
+def relight_view(tensoIR, env, light_names, rays, H, W, light_idx=None, num_samples=512, chunk=4096, nSample=96, vis_near=0.05,
+                 vis_far=1.5, denoise=None):
+    """A whole H x W view relit under every map of `light_names`: relight_chunk over chunks of `chunk` rays (rays [H * W, 6],
+    row-major; light_idx [H * W] or [H * W, 1], default zeros) into one [H * W, 3 n_maps] buffer, the denoiser's guide rows packed
+    next to it (tir_denoise_guide, one launch per chunk), and with denoise = a tensoir_amd.denoise.AtrousConfig the guided
+    a-trous filter over all maps together (cfg.levels launches).  The loop adds no host synchronisation to relight_chunk's.
+    -> {"rgb": [n_maps, H, W, 3], "raw": the image before the filter (the same tensor when denoise is None), "guide": [H, W, 12],
+    "acc": [H, W]}.  Rows mean what relight_chunk documents: hit rows hold the clamped sRGB relit colour, background rows
+    (acc <= 0.5: not valid in the guide) the raw environment lookup, which the filter neither changes nor reads.
+    num_samples: importance samples per surface point and map -- with the filter, 16 to 64 instead of 512.
+    Single process: the multi-rank gather of the benchmark keeps its own loop."""
+    from . import denoise as dn
+    H, W, chunk = int(H), int(W), int(chunk)
+    names = list(light_names)
+    if H < 1 or W < 1 or chunk < 1 or rays.dim() != 2 or tuple(rays.shape) != (H * W, 6):
+        raise ValueError(f"relight_view: rays is [H * W, 6] = [{H * W}, 6] and chunk >= 1, got {tuple(rays.shape)} and chunk {chunk}")
+    if not 1 <= len(names) <= ops.ATROUS_MAX_K // 3:
+        raise ValueError(f"relight_view: 1 to {ops.ATROUS_MAX_K // 3} environment maps, got {len(names)}")
+    if denoise is not None and not isinstance(denoise, dn.AtrousConfig):
+        raise TypeError(f"relight_view: denoise is None or an AtrousConfig, got {type(denoise).__name__}")
+    if not rays.is_cuda:
+        raise ops._lib.TensoirHipError("relight_view: rays must live on the GPU; tensoir_amd has no CPU path")
+    dev, n = rays.device, H * W
+    inv = None if denoise is None else denoise.inverses(tensoIR.aabb)        # refused before the view is rendered
+    rays = rays.to(torch.float32).contiguous()
+    lidx = (torch.zeros((n, 1), dtype=torch.int32, device=dev) if light_idx is None
+            else ops.to_device(light_idx.reshape(n, 1), dev, torch.int32).contiguous())
+    rows = torch.empty((n, 3 * len(names)), dtype=torch.float32, device=dev)
+    guide = torch.empty((n, ops.DENOISE_GUIDE), dtype=torch.float32, device=dev)
+    acc = torch.empty((n,), dtype=torch.float32, device=dev)
+    for r0 in range(0, n, chunk):
+        r1 = min(r0 + chunk, n)
+        _, prim, _ = relight_chunk(tensoIR, env, names, rays[r0:r1], lidx[r0:r1], num_samples, nSample, vis_near, vis_far, out=rows[r0:r1])
+        ops.denoise_guide(_map_rows(prim, r1 - r0), rays[r0:r1], guide, r0, 0.5)      # valid = relight_chunk's own acc > 0.5
+        acc[r0:r1] = prim[6]
+    image = lambda t: t.view(H, W, len(names), 3).permute(2, 0, 1, 3).contiguous()
+    raw = image(rows)
+    rgb = raw if denoise is None else image(dn.filter_rows(rows, guide, H, W, denoise.levels, inv))
+    return {"rgb": rgb, "raw": raw, "guide": guide.view(H, W, ops.DENOISE_GUIDE), "acc": acc.view(H, W)}
