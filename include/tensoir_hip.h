@@ -239,7 +239,10 @@ int tir_vm_app_fwd_valu(const TirField* f, const float* xyz, const int32_t* ligh
  *      (models/tensorBase_rotated_lights.py:12-17, :136-146, :198-208).
  *      input row = [feat, aux, PE(feat), PE(aux)]; aux row p is aux[aux_map ? aux_map[p] : p];
  *      feat rows are feat_stride floats apart (>= feat_dim).  aux_mod > 0: the aux row index is taken modulo
- *      aux_mod (pair id -> direction).  n_dev: as tir_vm_app_fwd. */
+ *      aux_mod (pair id -> direction).  n_dev: as tir_vm_app_fwd.
+ *      Columns >= feat_dim of a feature row never reach a result: they may hold anything (NaN included) in every decoder
+ *      entry from here to tir_mlp_bwd_multi_bf16x3, forward, tir_mlp_inputs and backward-data alike; the row loads that
+ *      fetch column 27 (16-byte aligned rows, stride % 4 == 0) discard it (tests/test_gpu_decoder_kernels.py). */
 int tir_mlp_fwd(const TirMlp* m, const float* feat, int32_t feat_stride, const float* aux,
                 const int32_t* aux_map, int32_t aux_mod, float* out, int64_t n, const int32_t* n_dev,
         void* stream);

@@ -123,6 +123,13 @@ def lib():
 
 
 _NAN, _INF = float("nan"), float("inf")
+
+
+def _case_id(change):
+    """A case's id with the host addresses written as P and P+4: an id must not change with where _KEEP happens to live."""
+    return repr(change).replace(str(P + 4), "P+4").replace(str(P), "P")
+
+
 # tir_atrous_level(color_in, color_out, guide, H, W, K, step, inv_sn, inv_sp, inv_sa2, inv_sr2, inv_sc2, stream)
 _GOOD_LEVEL = dict(color_in=P, color_out=Q, guide=P, H=4, W=4, K=3, step=1, inv_sn=20.0, inv_sp=50.0, inv_sa2=100.0, inv_sr2=100.0,
                    inv_sc2=4.0, stream=None)
@@ -138,7 +145,7 @@ _LEVEL_CASES = [
 ]
 
 
-@pytest.mark.parametrize("change,want", _LEVEL_CASES, ids=[repr(c) for c, _ in _LEVEL_CASES])
+@pytest.mark.parametrize("change,want", _LEVEL_CASES, ids=[_case_id(c) for c, _ in _LEVEL_CASES])
 def test_atrous_level_refuses_before_any_device_work(lib, change, want):
     assert lib.tir_atrous_level(*{**_GOOD_LEVEL, **change}.values()) == want
 
@@ -152,7 +159,7 @@ _GUIDE_CASES = [
 ]
 
 
-@pytest.mark.parametrize("change,want", _GUIDE_CASES, ids=[repr(c) for c, _ in _GUIDE_CASES])
+@pytest.mark.parametrize("change,want", _GUIDE_CASES, ids=[_case_id(c) for c, _ in _GUIDE_CASES])
 def test_denoise_guide_refuses_before_any_device_work(lib, change, want):
     assert lib.tir_denoise_guide(*{**_GOOD_GUIDE, **change}.values()) == want
 
