@@ -601,6 +601,38 @@ int tir_relight_importance_cells_packed_n(const float* normal, const float* albe
 int tir_env_compose(const float* env_rgb, int32_t H, int32_t W, const float* dirs, int32_t dir_stride, int64_t n,
                     const int32_t* slot, const float* fg_rgb, float* out, int32_t out_stride, void* stream);
 
+/* Relighting with multiple importance sampling of the map and the BRDF lobes.  N = n_l + n_b pairs per surface
+ * point, Philox counter of pair (m, j) = m*N + j (four uniforms u0..u3), combined under the balance heuristic.
+ * tir_env_mis_setup: pairs j < n_l draw a cell as tir_env_sample_setup_list does (same tables, guide tables and uniforms u0, u1:
+ *   with n_b = 0 the cells are tir_env_sample_setup's at Ns = N) and place the direction uniformly in the cell's (polar, azimuth)
+ *   rectangle, theta = (row + u2) pi / H, az = pi - (col + u3) 2 pi / W, w = (cos az sin theta, sin az sin theta, cos theta);
+ *   density p_l(w) = P_cell H W / (2 pi^2 sin theta(w)).  Pairs j >= n_l draw from a one-sample mixture: for u0 < lobe_select a
+ *   cosine-weighted direction about the unit raw normal (cos = sqrt(1 - u1), phi = 2 pi u2), otherwise a half vector about the
+ *   flipped normal Nf of GGX_specular from D(h) (Nf.h), cos = sqrt((1 - u1) / (1 + (alpha2 - 1) u1)), phi = 2 pi u2, alpha2 =
+ *   rough^4, reflected as w = 2 (v.h) h - v, v = safe_l2_normalize(-rays_d); density p_b(w) = s max(n.w, 0) / pi +
+ *   (1 - s) D(Nf.h) max(Nf.h, 0) / (4 v.h) with h = normalize(v + w); their cell is row = floor(acos(z) H / pi), col =
+ *   floor((pi - atan2(y, x)) W / (2 pi)), clamped to the table.
+ *   env_cell: the [H*W][8] records of tir_relight_importance_cells_packed (cell_stride 8) or the [H*W][3] direction table
+ *   (cell_stride 3, then env_pdf [H*W] = hdr_pdf_return is required); row_sin [H]: the sin(theta) table pdf_return was divided
+ *   by, so that pdf_return * row_sin[row] = P_cell H W / (2 pi^2).  normal / rays_d [M][3], rough [M].
+ *   Outputs: dirs [M][N][3], cell [M][N], pdf_mix [M][N] = (n_l p_l + n_b p_b) / N, vis [M][N] (0 written on inactive pairs; the
+ *   march -- tir_march_secondary_ids_fwd on `dirs` with ray_ids = pair_ids, n_ids_dev = n_active -- fills the rest), pair_ids
+ *   [M*N] = ids of the active pairs (blocks of `block_pairs` consecutive pairs, 256 ... 32768, in pair order within a block),
+ *   n_active [1] (zero on entry).  A pair is inactive when normal.w <= 1e-6 or, for a lobe sample, v.h <= 0: pdf_mix = 1 there.
+ *   m_dev [1] or NULL: device-side point count, as in tir_env_sample_setup_list_n.
+ * tir_relight_mis: out [M][3] = (1 / N) sum_j (albedo / pi + GGX(w_j)) vis_j L[cell_j] (normal.w_j) / pdf_mix_j, L from the
+ *   env_cell records (16-byte aligned); linear = 0: clamped to [0, 1] and sRGB-encoded, linear = 1: the raw mean. */
+int tir_env_mis_setup(const float* row_cdf, const float* col_cdf, int32_t H, int32_t W, const float* env_cell,
+                      int32_t cell_stride, const float* env_pdf, const float* row_sin, const float* normal,
+                      const float* rays_d, const float* rough, int32_t M, int32_t n_l, int32_t n_b, float lobe_select,
+                      uint64_t seed, uint64_t offset, int32_t block_pairs, const int32_t* row_guide,
+                      const uint16_t* col_guide, int32_t guide_rows, int32_t guide_cols, float* dirs, int32_t* cell,
+                      float* pdf_mix, float* vis, int32_t* pair_ids, int32_t* n_active, const int32_t* m_dev, void* stream);
+int tir_relight_mis(const float* normal, const float* albedo, const float* rough, const float* fresnel,
+                    const float* rays_d, const float* dirs, const int32_t* cell, const float* pdf_mix,
+                    const float* env_cell, const float* vis, int32_t M, int32_t N, int32_t linear, float* out_rgb,
+                    const int32_t* m_dev, void* stream);
+
 /* GGX_specular alone (models/relight_utils.py:17-50): normal/v [M][3], l [M][D][3],
  * rough/fresnel [M][3] -> spec [M][D][3]. */
 int tir_ggx_specular(const float* normal, const float* v, const float* l, const float* rough,

@@ -456,6 +456,205 @@ k_relight_importance_cells(const float* __restrict__ normal, const float* __rest
     }
 }
 
+// ---- multiple importance sampling of the map and the BRDF lobes -------------------------------------------------------
+// Two strategies per surface point, combined under the balance heuristic: n_l directions from the map's own distribution, placed
+// uniformly inside the drawn cell's (polar, azimuth) rectangle, and n_b from a one-sample mixture of a cosine lobe about the unit
+// raw normal and the GGX half-vector distribution D(h) (Nf . h) about the flipped normal of make_surface.  Every pair carries an
+// explicit direction, the cell that contains it and pdf_mix = (n_l p_l + n_b p_b) / N, both densities per solid angle.
+
+// an orthonormal pair (t, b) perpendicular to the unit vector a, without a branch (Duff et al. 2017)
+__device__ __forceinline__ void mis_frame(const float a[3], float t[3], float b[3]) {
+    const float sg = copysignf(1.0f, a[2]);
+    const float p = -1.0f / (sg + a[2]);
+    const float q = a[0] * a[1] * p;
+    t[0] = 1.0f + sg * a[0] * a[0] * p; t[1] = sg * q; t[2] = -sg * a[0];
+    b[0] = q; b[1] = sg + a[1] * a[1] * p; b[2] = -a[1];
+}
+
+// density per solid angle of the direction w under the GGX lobe sampler: D(Nf . h) max(Nf . h, 0) / (4 v . h), h = normalize(v + w);
+// Nf / V / alpha2 = make_surface's.  (The mixture: p_b = s max(n . w, 0) / pi + (1 - s) x this.)
+__device__ __forceinline__ float mis_pdf_lobe(const Surface& s, float wx, float wy, float wz) {
+    float hx = wx + s.V[0], hy = wy + s.V[1], hz = wz + s.V[2];
+    normalize3(hx, hy, hz, 1e-12f);
+    const float noh = fmaxf(s.N[0] * hx + s.N[1] * hy + s.N[2] * hz, 0.f);
+    const float voh = s.V[0] * hx + s.V[1] * hy + s.V[2] * hz;
+    // 1 - (Nf . h)^2 as |Nf x h|^2: the difference cancels where the lobe peaks (alpha2 = 1e-4 at roughness 0.1)
+    const float cx = s.N[1] * hz - s.N[2] * hy, cy = s.N[2] * hx - s.N[0] * hz, cw = s.N[0] * hy - s.N[1] * hx;
+    const float t = (cx * cx + cy * cy + cw * cw) + s.alpha2[0] * noh * noh;
+    return voh > 0.f ? (s.alpha2[0] * 0.31830988618379067154f / (t * t)) * noh / (4.f * voh) : 0.f;
+}
+
+// One pair per thread-iteration, a block owns `block_pairs` consecutive pairs (as k_env_sample_list).  The Philox counter of pair
+// (m, j) is m N + j; j < n_l are the light samples, whose cell search is k_env_sample_list's (same tables, same uniforms u0, u1:
+// with n_b = 0 the cells are tir_env_sample_setup's at Ns = N).  A BRDF sample's cell is found by inverting the direction table.
+// p_l = P_cell H W / (2 pi^2 sin theta(w)) comes from the cell's pdf_return (which holds P_cell H W / (2 pi^2 row_sin[row])) times
+// row_sin[row] -- the table pdf_return was divided by -- over the direction's own sin theta.  Pairs with n . w <= 1e-6 (raw normal:
+// the existing cosine mask) or, for a lobe sample, v . h <= 0 are inactive: vis = 0, pdf_mix = 1 (never a 0 / 0 in the integration),
+// not listed.  The list: wave ballots, their counts per (iteration, wave) in LDS, one scan by wave 0, ONE reservation atomic per
+// block, ids written in pair order within the block.
+__global__ void __launch_bounds__(256)
+k_env_mis_setup(const float* __restrict__ row_cdf, const float* __restrict__ col_cdf, int H, int W, const float* __restrict__ env_cell,
+                int cell_stride, const float* __restrict__ env_pdf, const float* __restrict__ row_sin, const float* __restrict__ normal,
+                const float* __restrict__ rays_d, const float* __restrict__ rough, int M, int n_l, int n_b, float sel,
+                unsigned long long seed, unsigned long long offset, int block_pairs, const int32_t* __restrict__ row_guide,
+                const uint16_t* __restrict__ col_guide, int g_rows, int g_cols, float* __restrict__ dirs, int32_t* __restrict__ cell,
+                float* __restrict__ pdf_mix, float* __restrict__ vis, int32_t* __restrict__ pair_ids, int32_t* __restrict__ n_active,
+                const int32_t* __restrict__ m_dev) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char mis_flag[];      // [block_pairs] 1 = active
+    __shared__ int s_cnt[512];                                                    // per (iteration, wave): 4 * block_pairs / 256 <= 512
+    __shared__ int s_base;
+    if (m_dev) M = min(M, max(*m_dev, 0));
+    const int N = n_l + n_b;
+    const int64_t n = (int64_t)M * N;
+    const int64_t base = (int64_t)blockIdx.x * block_pairs;
+    if (base >= n) return;                        // (block-uniform)
+    const int cnt = (int)min((int64_t)block_pairs, n - base);
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int iters = (cnt + 255) >> 8;
+    const float PI = 3.14159265358979323846f;
+    for (int it = 0; it < iters; ++it) {
+        const int j = (it << 8) + threadIdx.x;
+        bool act = false;
+        if (j < cnt) {
+            const int64_t i = base + j;
+            const int m = (int)(i / N), sj = (int)(i - (int64_t)m * N);
+            float u[4];
+            tir::philox_uniform4(seed, offset, (uint64_t)i, u);
+            const float* nm = normal + 3 * (size_t)m;
+            float view[3] = {-rays_d[3 * (size_t)m], -rays_d[3 * (size_t)m + 1], -rays_d[3 * (size_t)m + 2]};
+            normalize3(view[0], view[1], view[2], 1e-6f);
+            const float rough3[3] = {rough[m], rough[m], rough[m]}, none[3] = {0.f, 0.f, 0.f};
+            const Surface s = make_surface(nm, view, rough3, none, nullptr);
+            float nh[3] = {nm[0], nm[1], nm[2]};
+            normalize3(nh[0], nh[1], nh[2], 1e-12f);
+            float w[3];
+            int row, col;
+            bool ok = true;
+            float lobe = -1.f;                    // the lobe sampler's density of w, where the sampler itself knows it
+            if (sj < n_l) {
+                row = row_guide ? cdf_upper_bound_guided(row_cdf, H, u[0], row_guide, g_rows) : cdf_upper_bound(row_cdf, H, u[0]);
+                col = col_guide ? cdf_upper_bound_guided(col_cdf + (size_t)row * W, W, u[1], col_guide + (size_t)row * (g_cols + 2), g_cols)
+                                : cdf_upper_bound(col_cdf + (size_t)row * W, W, u[1]);
+                // theta = (row + u2) pi / H, az = pi - (col + u3) 2 pi / W: cos az = -cos(2 pi (col + u3) / W), sin az = sin(same)
+                float st, ct, sa, ca;
+                sincospif(((float)row + u[2]) / (float)H, &st, &ct);
+                sincospif(2.0f * ((float)col + u[3]) / (float)W, &sa, &ca);
+                w[0] = -ca * st; w[1] = sa * st; w[2] = ct;
+            } else {
+                float sp, cp, t[3], b[3];
+                sincospif(2.0f * u[2], &sp, &cp);
+                const bool diffuse = u[0] < sel;
+                const float* ax = diffuse ? nh : s.N;
+                // cosine lobe: cos^2 = 1 - u1; half vector: cos^2 = (1 - u1) / (1 + (alpha2 - 1) u1), the denominator formed as
+                // (1 - u1) + alpha2 u1 and sin^2 = alpha2 u1 / the same: no difference of nearly equal numbers at low roughness
+                const float a2 = diffuse ? 1.f : s.alpha2[0];
+                const float den = (1.f - u[1]) + a2 * u[1];
+                const float cz = sqrtf((1.f - u[1]) / den), sz = sqrtf(a2 * u[1] / den);
+                mis_frame(ax, t, b);
+                float d[3];
+#pragma unroll
+                for (int a = 0; a < 3; ++a) d[a] = (sz * cp) * t[a] + (sz * sp) * b[a] + cz * ax[a];
+                if (diffuse) {
+                    w[0] = d[0]; w[1] = d[1]; w[2] = d[2];
+                } else {
+                    const float voh = s.V[0] * d[0] + s.V[1] * d[1] + s.V[2] * d[2];
+                    ok = voh > 0.f;
+                    // the sampled half vector's own density: sin^2 + alpha2 cos^2 = alpha2 / den, so D = den^2 / (pi alpha2) -- no
+                    // trip through the rounded w, whose last bit moves the peak of a narrow lobe by 1e-6 relative
+                    lobe = ok ? (den * den) * (0.31830988618379067154f / a2) * cz / (4.f * voh) : 0.f;
+#pragma unroll
+                    for (int a = 0; a < 3; ++a) w[a] = 2.f * voh * d[a] - s.V[a];
+                }
+                // the cell that contains w: the inverse of the direction table
+                const float th = acosf(fminf(fmaxf(w[2], -1.f), 1.f)), az = atan2f(w[1], w[0]);
+                row = min(max((int)floorf(th * (float)H / PI), 0), H - 1);
+                col = min(max((int)floorf((PI - az) * (float)W / (2.f * PI)), 0), W - 1);
+            }
+            const int c = row * W + col;
+            const float cosine = w[0] * nm[0] + w[1] * nm[1] + w[2] * nm[2];
+            act = ok && cosine > 1e-6f;
+            const float pdf_ret = cell_stride == 8 ? env_cell[8 * (size_t)c + 3] : env_pdf[c];
+            const float sin_w = fmaxf(sqrtf(w[0] * w[0] + w[1] * w[1]), 1e-8f);
+            const float pl = pdf_ret * row_sin[row] / sin_w;
+            if (lobe < 0.f) lobe = mis_pdf_lobe(s, w[0], w[1], w[2]);
+            const float pb = sel * fmaxf(nh[0] * w[0] + nh[1] * w[1] + nh[2] * w[2], 0.f) * 0.31830988618379067154f + (1.f - sel) * lobe;
+            dirs[3 * i] = w[0]; dirs[3 * i + 1] = w[1]; dirs[3 * i + 2] = w[2];
+            cell[i] = c;
+            pdf_mix[i] = act ? ((float)n_l * pl + (float)n_b * pb) / (float)N : 1.0f;
+            if (!act) vis[i] = 0.0f;
+            mis_flag[j] = act ? 1 : 0;
+        }
+        const unsigned long long mask = __ballot(act);
+        if (lane == 0) s_cnt[(it << 2) + wv] = __popcll(mask);
+    }
+    __syncthreads();
+    if (wv == 0) {        // exclusive scan of the 4 * iters counts, 64 at a time
+        int carry = 0;
+        for (int c0 = 0; c0 < (iters << 2); c0 += 64) {
+            const int k = c0 + lane;
+            const int v = k < (iters << 2) ? s_cnt[k] : 0;
+            int incl = v;
+#pragma unroll
+            for (int dd = 1; dd < 64; dd <<= 1) {
+                const int oth = __shfl_up(incl, dd, 64);
+                if (lane >= dd) incl += oth;
+            }
+            if (k < (iters << 2)) s_cnt[k] = carry + incl - v;
+            carry += __shfl(incl, 63, 64);
+        }
+        if (lane == 0) s_base = carry > 0 ? atomicAdd(n_active, carry) : 0;
+    }
+    __syncthreads();
+    const int64_t ob = s_base;
+    for (int it = 0; it < iters; ++it) {
+        const int j = (it << 8) + threadIdx.x;
+        const bool act = j < cnt && mis_flag[j];
+        const unsigned long long mask = __ballot(act);
+        // (a stale n_active must never turn into a write past the M * N slots: see k_shade_setup)
+        const int64_t slot = ob + s_cnt[(it << 2) + wv] + __popcll(mask & ((1ull << lane) - 1ull));
+        if (act && slot < n) pair_ids[slot] = (int32_t)(base + j);
+    }
+}
+
+// One wave per point, lanes over its N pairs (as k_relight_importance_cells<true>): direction, cell and mixture density come from
+// k_env_mis_setup's buffers, the radiance from the cell's record; sum (albedo / pi + spec) (vis L) cosine / pdf_mix, / N.
+// linear: the raw mean (a test's, an albedo demodulation's input); otherwise clamp to [0, 1] and sRGB.
+__global__ void __launch_bounds__(256)
+k_relight_mis(const float* __restrict__ normal, const float* __restrict__ albedo, const float* __restrict__ rough,
+              const float* __restrict__ fresnel, const float* __restrict__ rays_d, const float* __restrict__ dirs,
+              const int32_t* __restrict__ cell, const float* __restrict__ pdf_mix, const float* __restrict__ env_cell,
+              const float* __restrict__ vis, int M, int N, int linear, float* __restrict__ out, const int32_t* __restrict__ m_dev) {
+    const int lane = threadIdx.x & 63;
+    const int m = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (m_dev) M = min(M, max(*m_dev, 0));
+    if (m >= M) return;
+    float view[3] = {-rays_d[3 * (size_t)m], -rays_d[3 * (size_t)m + 1], -rays_d[3 * (size_t)m + 2]};
+    normalize3(view[0], view[1], view[2], 1e-6f);
+    const float rough3[3] = {rough[m], rough[m], rough[m]};
+    const float* nm = normal + 3 * (size_t)m;
+    Surface s = make_surface(nm, view, rough3, fresnel + 3 * (size_t)m, albedo + 3 * (size_t)m);
+    float c[3] = {0.f, 0.f, 0.f};
+    for (int j = lane; j < N; j += 64) {
+        const size_t mj = (size_t)m * N + j;
+        const float4 b = *reinterpret_cast<const float4*>(env_cell + 8 * (size_t)cell[mj] + 4);
+        const float lx = dirs[3 * mj], ly = dirs[3 * mj + 1], lz = dirs[3 * mj + 2];
+        const float v = vis[mj], pdf = pdf_mix[mj];
+        const float er[3] = {b.x, b.y, b.z};
+        const float cosine = lx * nm[0] + ly * nm[1] + lz * nm[2];
+        float spec[3];
+        ggx_dir(s, lx, ly, lz, spec);
+#pragma unroll
+        for (int q = 0; q < 3; ++q)
+            c[q] += (s.alb_pi[q] + spec[q]) * (v * er[q]) * cosine / pdf;
+    }
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+        float t = group_sum<64>(c[q]) / (float)N;
+        if (!linear) t = linear2srgb(fminf(fmaxf(t, 0.f), 1.f));
+        if (lane == 0) out[3 * (size_t)m + q] = t;
+    }
+}
+
 // Environment_Light.get_light (models/relight_utils.py:191-205): bilinear lookup of the map at a direction,
 // F.grid_sample(align_corners=True, zero padding) of qx = -theta / pi, qy = 2 (acos(z) - 1e-6) / pi - 1
 __global__ void __launch_bounds__(256)
@@ -955,6 +1154,52 @@ extern "C" int tir_relight_importance_cells_packed(const float* normal, const fl
                                                    const float* env_cell, const float* vis, int32_t M, int32_t Ns,
                                                    float* out_rgb, void* stream) {
     return tir_relight_importance_cells_packed_n(normal, albedo, rough, fresnel, rays_d, cell, env_cell, vis, M, Ns, out_rgb, nullptr, stream);
+}
+
+extern "C" int tir_env_mis_setup(const float* row_cdf, const float* col_cdf, int32_t H, int32_t W, const float* env_cell,
+                                 int32_t cell_stride, const float* env_pdf, const float* row_sin, const float* normal,
+                                 const float* rays_d, const float* rough, int32_t M, int32_t n_l, int32_t n_b, float lobe_select,
+                                 uint64_t seed, uint64_t offset, int32_t block_pairs, const int32_t* row_guide,
+                                 const uint16_t* col_guide, int32_t guide_rows, int32_t guide_cols, float* dirs, int32_t* cell,
+                                 float* pdf_mix, float* vis, int32_t* pair_ids, int32_t* n_active, const int32_t* m_dev, void* stream) {
+    if (M < 0 || H <= 0 || W <= 0 || n_l < 0 || n_b < 0 || (int64_t)n_l + n_b < 1) return TIR_ERR_ARG;
+    if (!(lobe_select >= 0.f && lobe_select <= 1.f)) return TIR_ERR_ARG;                       // (a NaN too)
+    if (cell_stride != 3 && cell_stride != 8) return TIR_ERR_ARG;
+    if ((row_guide == nullptr) != (col_guide == nullptr)) return TIR_ERR_ARG;
+    if (row_guide) {        // as tir_env_sample_setup_list_n
+        if (guide_rows <= 0 || guide_cols <= 0 || (guide_rows & (guide_rows - 1)) || (guide_cols & (guide_cols - 1))) return TIR_ERR_ARG;
+        if (W > 65535 || guide_rows > (1 << 20) || guide_cols > (1 << 20)) return TIR_ERR_UNSUPPORTED;
+    }
+    // the LDS layout: one flag byte per pair of a block, one count per wave and 256 pairs in a table of 512
+    if (block_pairs < 256 || block_pairs > 32768) return TIR_ERR_UNSUPPORTED;
+    if ((int64_t)n_l + n_b > (1 << 24)) return TIR_ERR_UNSUPPORTED;                           // the counts are used as floats
+    if (!row_cdf || !col_cdf || !env_cell || !row_sin || !normal || !rays_d || !rough || !dirs || !cell || !pdf_mix || !vis ||
+        !pair_ids || !n_active || (cell_stride == 3 && !env_pdf))
+        return TIR_ERR_ARG;
+    if (M == 0) return TIR_OK;
+    const int64_t n = (int64_t)M * ((int64_t)n_l + n_b);
+    if (n >= (int64_t)1 << 31) return TIR_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(k_env_mis_setup, dim3((unsigned)((n + block_pairs - 1) / block_pairs)), dim3(256), (size_t)block_pairs,
+                       tir_stream(stream), row_cdf, col_cdf, H, W, env_cell, cell_stride, env_pdf, row_sin, normal, rays_d, rough, M, n_l,
+                       n_b, lobe_select, (unsigned long long)seed, (unsigned long long)offset, block_pairs, row_guide, col_guide,
+                       guide_rows, guide_cols, dirs, cell, pdf_mix, vis, pair_ids, n_active, m_dev);
+    TIR_CHECK_LAUNCH();
+    return TIR_OK;
+}
+
+extern "C" int tir_relight_mis(const float* normal, const float* albedo, const float* rough, const float* fresnel,
+                               const float* rays_d, const float* dirs, const int32_t* cell, const float* pdf_mix,
+                               const float* env_cell, const float* vis, int32_t M, int32_t N, int32_t linear, float* out_rgb,
+                               const int32_t* m_dev, void* stream) {
+    if (M < 0 || N < 1 || (linear != 0 && linear != 1)) return TIR_ERR_ARG;
+    if (!normal || !albedo || !rough || !fresnel || !rays_d || !dirs || !cell || !pdf_mix || !env_cell || !vis || !out_rgb)
+        return TIR_ERR_ARG;
+    if (reinterpret_cast<uintptr_t>(env_cell) % 16 != 0) return TIR_ERR_ARG;
+    if (M == 0) return TIR_OK;
+    hipLaunchKernelGGL(k_relight_mis, dim3((M + 3) / 4), dim3(256), 0, tir_stream(stream), normal, albedo, rough, fresnel, rays_d,
+                       dirs, cell, pdf_mix, env_cell, vis, M, N, linear, out_rgb, m_dev);
+    TIR_CHECK_LAUNCH();
+    return TIR_OK;
 }
 
 extern "C" int tir_env_lookup(const float* env_rgb, int32_t H, int32_t W, const float* dirs, int64_t n, float* out,

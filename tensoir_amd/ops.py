@@ -1082,6 +1082,72 @@ def relight_importance_cells(normal, albedo, rough, fresnel, rays_d, cell, env_d
     return out
 
 
+def env_mis_setup(row_cdf, col_cdf, env_cell, row_sin, normal, rays_d, rough, n_l, n_b, lobe_select, seed, offset, block_pairs=512,
+                  guide=None, m_dev=None, env_pdf=None, buffers=None):
+    """tir_env_mis_setup: n_l map-distributed directions (jittered inside their cells) and n_b directions from the BRDF mixture
+    (cosine lobe with probability lobe_select, GGX half-vector lobe otherwise) per surface point, N = n_l + n_b.  env_cell: the
+    [H*W, 8] records of pack_env_cells, or the [H*W, 3] direction table together with env_pdf [H*W]; row_sin [H]: the sin(theta)
+    table hdr_pdf_return was divided by.  Returns dirs [M, N, 3], cell [M, N] int32, pdf_mix [M, N] = (n_l p_l + n_b p_b) / N,
+    vis [M, N] (0 where inactive, the rest for the march to fill), pair_ids [M*N] int32, n_active [1] int32 (device).
+    m_dev (int32 device scalar): only the first min(M, m_dev) points exist.  buffers: the caller's (dirs, cell, pdf_mix, vis,
+    pair_ids) to write into instead of fresh ones."""
+    H, W = col_cdf.shape
+    normal, rays_d = f32(normal, "normal", 3), f32(rays_d, "rays_d", 3)
+    M, dev = normal.shape[0], normal.device
+    rough = f32(rough, "roughness").view(-1)
+    n_l, n_b = int(n_l), int(n_b)
+    N = n_l + n_b
+    if n_l < 0 or n_b < 0 or N < 1:
+        raise ValueError(f"env_mis_setup: n_l, n_b >= 0 and n_l + n_b >= 1, got {n_l} and {n_b}")
+    if rays_d.shape[0] != M or rough.numel() != M:
+        raise ValueError(f"env_mis_setup: normal, rays_d and roughness describe the same {M} points")
+    stride = int(env_cell.shape[-1])
+    if stride not in (3, 8) or env_cell.shape[0] != H * W or (stride == 3 and env_pdf is None):
+        raise ValueError(f"env_cell: expected [H*W, 8] cell records or [H*W, 3] directions plus env_pdf, got {tuple(env_cell.shape)}")
+    row_sin = f32(row_sin, "row_sin").view(-1)
+    if row_sin.numel() != H:
+        raise ValueError(f"row_sin: expected {H} rows, got {row_sin.numel()}")
+    if buffers is not None:
+        dirs, cell, pdf_mix, vis, pair_ids = buffers
+        want = ((M, N, 3), torch.float32), ((M, N), torch.int32), ((M, N), torch.float32), ((M, N), torch.float32), ((M * N,), torch.int32)
+        for t, (shape, dt) in zip(buffers, want):
+            if tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous() or t.device != dev:
+                raise ValueError(f"env_mis_setup: buffers are contiguous (dirs, cell, pdf_mix, vis, pair_ids) for {M} points x {N} pairs")
+    else:
+        dirs = torch.empty((M, N, 3), dtype=torch.float32, device=dev)
+        cell = torch.empty((M, N), dtype=torch.int32, device=dev)
+        pdf_mix = torch.empty((M, N), dtype=torch.float32, device=dev)
+        vis = torch.empty((M, N), dtype=torch.float32, device=dev)
+        pair_ids = torch.empty((M * N,), dtype=torch.int32, device=dev)
+    n_active = torch.zeros((1,), dtype=torch.int32, device=dev)
+    _call("tir_env_mis_setup", _ptr(f32(row_cdf, "row_cdf")), _ptr(f32(col_cdf, "col_cdf")), H, W, _ptr(f32(env_cell, "env_cell", stride)),
+          stride, _ptr(None if env_pdf is None else f32(env_pdf, "env_pdf")), _ptr(row_sin), _ptr(normal), _ptr(rays_d), _ptr(rough), M,
+          n_l, n_b, float(lobe_select), int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1), int(block_pairs),
+          *((None, None, 0, 0) if guide is None else (_ptr(_req(guide[0], torch.int32, "row_guide")),
+                                                      _ptr(_req(guide[1], torch.int32, "col_guide")), int(guide[2]), int(guide[3]))),
+          _ptr(dirs), _ptr(cell), _ptr(pdf_mix), _ptr(vis), _ptr(pair_ids), _ptr(n_active), _ptr(m_dev), _stream())
+    return dirs, cell, pdf_mix, vis, pair_ids, n_active
+
+
+def relight_mis(normal, albedo, rough, fresnel, rays_d, dirs, cell, pdf_mix, env_cell, vis, linear=False, m_dev=None):
+    """tir_relight_mis: mean over a point's N pairs of (albedo / pi + GGX) x vis x radiance of the pair's cell x cosine / pdf_mix
+    on env_mis_setup's buffers and the [H*W, 8] cell records -> [M, 3], clamped to [0, 1] and sRGB-encoded, or with linear=True
+    the raw mean.  m_dev (int32 device scalar): only the first min(M, m_dev) points exist (rows beyond: not written)."""
+    normal, albedo = f32(normal, "normal", 3), f32(albedo, "albedo", 3)
+    rough = f32(rough, "roughness").view(-1)
+    fresnel, rays_d = f32(fresnel, "fresnel", 3), f32(rays_d, "rays_d", 3)
+    cell = i32(cell, "cell")
+    M, N = cell.shape
+    dirs = f32(dirs, "dirs", 3).view(M, N, 3)
+    pdf_mix, vis = f32(pdf_mix, "pdf_mix").view(M, N), f32(vis, "vis").view(M, N)
+    if normal.shape[0] != M:
+        raise ValueError(f"relight_mis: cell has {M} rows, normal {normal.shape[0]}")
+    out = torch.empty((M, 3), dtype=torch.float32, device=normal.device)
+    _call("tir_relight_mis", _ptr(normal), _ptr(albedo), _ptr(rough), _ptr(fresnel), _ptr(rays_d), _ptr(dirs), _ptr(cell), _ptr(pdf_mix),
+          _ptr(f32(env_cell, "env_cell", 8)), _ptr(vis), M, N, int(bool(linear)), _ptr(out), _ptr(m_dev), _stream())
+    return out
+
+
 def env_lookup(env_rgb, dirs):
     """Bilinear lookup of an [H, W, 3] map at [n, 3] directions (tir_env_lookup)."""
     env_rgb = f32(env_rgb, "env_rgb", 3)

@@ -347,6 +347,33 @@ def render_with_BRDF(depth_map, normal_map, albedo_map, roughness_map, fresnel_m
     return shade_from_maps(tensoIR, maps, rays, light_idx, sample_method, args, use_linear2srgb)
 
 
+class MisConfig:
+    """Multiple importance sampling of the environment map and the BRDF lobes for the relighting entry points.
+    brdf_fraction: the share of a point's samples drawn from the BRDF mixture, n_b = round(brdf_fraction * num_samples), the other
+    n_l = num_samples - n_b from the map's own distribution (0: the jittered light-only estimator, 1: BRDF only).  lobe_select:
+    the probability with which a BRDF sample comes from the cosine lobe and not the GGX half-vector lobe.  linear: the raw linear
+    mean instead of the clamped, sRGB-encoded colour."""
+
+    __slots__ = ("brdf_fraction", "lobe_select", "linear")
+
+    def __init__(self, brdf_fraction=0.5, lobe_select=0.5, linear=False):
+        for name, v in (("brdf_fraction", brdf_fraction), ("lobe_select", lobe_select)):
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not 0.0 <= float(v) <= 1.0:      # (a NaN fails the comparison)
+                raise ValueError(f"MisConfig: {name} lies in [0, 1], got {v!r}")
+        self.brdf_fraction, self.lobe_select, self.linear = float(brdf_fraction), float(lobe_select), bool(linear)
+
+    def split(self, num_samples):
+        """-> (n_l, n_b) for `num_samples` samples per point."""
+        num_samples = int(num_samples)
+        if num_samples < 1:
+            raise ValueError(f"MisConfig: num_samples >= 1, got {num_samples}")
+        n_b = min(max(int(round(self.brdf_fraction * num_samples)), 0), num_samples)
+        return num_samples - n_b, n_b
+
+    def __repr__(self):
+        return f"MisConfig(brdf_fraction={self.brdf_fraction}, lobe_select={self.lobe_select}, linear={self.linear})"
+
+
 class Environment_Light:
     """models/relight_utils.py:110-205 with the HDR maps handed in as arrays (the reference reads
     ``*.hdr`` files with OpenCV, which is I/O outside the hot path)."""
@@ -354,6 +381,7 @@ class Environment_Light:
     def __init__(self, hdr_path=None, device="cuda", hdr_maps=None):
         self.hdr_rgbs, self.hdr_pdf_sample, self.hdr_pdf_return, self.hdr_dir = {}, {}, {}, {}
         self.hdr_row_cdf, self.hdr_col_cdf, self.hdr_cdf_guide, self._cell_records = {}, {}, {}, {}
+        self.hdr_row_sin = {}
         self._draws = 0
         maps = dict(hdr_maps or {})
         if torch.device(device).type == "cuda" and not torch.cuda.is_available():
@@ -384,6 +412,8 @@ class Environment_Light:
             self.hdr_pdf_sample[name] = pdf.to(device)
             self.hdr_pdf_return[name] = pdf_ret.to(device)
             self.hdr_dir[name] = dirs.to(device)
+            # the sin(theta) table hdr_pdf_return was divided by: pdf_return * row_sin = P_cell H W / (2 pi^2) (tir_env_mis_setup)
+            self.hdr_row_sin[name] = sin_theta.float().to(device).contiguous()
             # inverse-CDF tables of the device sampler (tir_env_sample_setup): row marginal + row-conditional columns,
             # accumulated in fp64 so that the fp32 tables are the correctly rounded prefix sums
             p2 = pdf.view(H, W).double()
@@ -445,6 +475,23 @@ class Environment_Light:
                                            torch.cuda.initial_seed(), self._draws, bins, block_pairs,
                                            self.hdr_cdf_guide.get(light_name), m_dev)
 
+    @torch.no_grad()
+    def sample_mis(self, light_name, normal, rays_d, rough, num_samples, cfg, m_dev=None, block_pairs=512):
+        """Per surface point cfg.split(num_samples) = (n_l, n_b) directions from the map's distribution (jittered inside their cells)
+        and from the BRDF mixture, with their cells and the balance heuristic's mixture density (tir_env_mis_setup; needs the packed
+        cell records).  One draw counter, like sample_cells / sample_cells_listed.  Returns (dirs [M, N, 3], cell [M, N], pdf_mix
+        [M, N], vis [M, N] with the inactive pairs' zeros, pair_ids [M * N], n_active [1] on the device)."""
+        if not isinstance(cfg, MisConfig):
+            raise TypeError(f"sample_mis: cfg is a MisConfig, got {type(cfg).__name__}")
+        rec = self.cell_records(light_name)
+        if rec is None:
+            raise ops._lib.TensoirHipError("multiple importance sampling needs the packed cell records (TENSOIR_ENV_RECORDS != 0)")
+        n_l, n_b = cfg.split(num_samples)
+        self._draws += 1
+        return ops.env_mis_setup(self.hdr_row_cdf[light_name], self.hdr_col_cdf[light_name], rec, self.hdr_row_sin[light_name], normal,
+                                 rays_d, rough, n_l, n_b, cfg.lobe_select, torch.cuda.initial_seed(), self._draws, block_pairs,
+                                 self.hdr_cdf_guide.get(light_name), m_dev)
+
     def cell_records(self, light_name):
         """[H*W, 8] records {direction, pdf_return, radiance, 0} of a map (ops.pack_env_cells), built on first use: the
         integration kernel reads one 32-byte record per sample instead of three tables.  TENSOIR_ENV_RECORDS=0: None."""
@@ -479,6 +526,19 @@ def read_hdr(path):
     return hdr.read_hdr(path)
 
 
+def _org_map(M, Ns, dev):
+    """pair id -> surface point of the dense [M, Ns] pair grid, cached under the key the relighting entry points share."""
+    key = ("orgmap", M, Ns, str(dev))
+    org_map = _CONST_CACHE.get(key)
+    if org_map is None:
+        pair = torch.arange(M * Ns, dtype=torch.int32, device=dev)
+        org_map = torch.div(pair, Ns, rounding_mode="floor").to(torch.int32)
+        if len(_CONST_CACHE) > 64:
+            _CONST_CACHE.clear()
+        _CONST_CACHE[key] = org_map
+    return org_map
+
+
 @torch.no_grad()
 def relight_with_envmap(tensoIR, surface_xyz, normal, albedo, roughness, fresnel, rays_d, light_dir,
                         light_rgb, light_pdf, nSample=96, vis_near=0.05, vis_far=1.5):
@@ -490,17 +550,9 @@ def relight_with_envmap(tensoIR, surface_xyz, normal, albedo, roughness, fresnel
     normal = normal.to(torch.float32).contiguous()
     cosine = torch.einsum("ijk,ik->ij", light_dir, normal)
     active = (cosine > 1e-6).to(torch.uint8).contiguous()
-    key = ("orgmap", M, Ns, str(dev))
-    org_map = _CONST_CACHE.get(key)
-    if org_map is None:
-        pair = torch.arange(M * Ns, dtype=torch.int32, device=dev)
-        org_map = torch.div(pair, Ns, rounding_mode="floor").to(torch.int32)
-        if len(_CONST_CACHE) > 64:
-            _CONST_CACHE.clear()
-        _CONST_CACHE[key] = org_map
     z = _z_table(nSample, vis_near, vis_far, dev)
     vis, _, _ = ops.march_secondary(tensoIR.packed_field_dense(), surface_xyz.to(torch.float32).contiguous(),
-                                    light_dir.view(-1, 3), z, M * Ns, org_map, None, active.view(-1),
+                                    light_dir.view(-1, 3), z, M * Ns, _org_map(M, Ns, dev), None, active.view(-1),
                                     tensoIR.march_t_stop, False, 0, False)
     return ops.relight_importance(normal, albedo, roughness, fresnel, rays_d, light_dir, light_rgb,
                                   light_pdf, vis.view(M, Ns))
@@ -508,18 +560,33 @@ def relight_with_envmap(tensoIR, surface_xyz, normal, albedo, roughness, fresnel
 
 @torch.no_grad()
 def relight_importance_sampled(tensoIR, env, light_name, surface_xyz, normal, albedo, roughness, fresnel, rays_d,
-                               num_samples=512, nSample=96, vis_near=0.05, vis_far=1.5, m_dev=None):
+                               num_samples=512, nSample=96, vis_near=0.05, vis_far=1.5, m_dev=None, mis=None):
     """The loop body of scripts/relight_importance.py:119-170 for one environment map, entirely on the device:
     importance sampling + cosine mask (tir_env_sample_setup) -> visibility march of the unmasked (point, cell) pairs with
     the map's direction table as `dirs` and the cell index as `dir_map` -> BRDF x radiance x cosine / pdf mean -> sRGB
     (tir_relight_importance_cells).  Per sample 5 bytes of bookkeeping instead of the reference's 28 + masks.
     m_dev (int32 device scalar): the arrays have capacity M rows of which only the first m_dev are surface points
-    (ops.surface_compact); rows beyond are neither sampled nor marched, their output rows are left unwritten."""
+    (ops.surface_compact); rows beyond are neither sampled nor marched, their output rows are left unwritten.
+    mis (a MisConfig; None = everything above, launch for launch): map and BRDF sampling combined under the balance heuristic
+     -- tir_env_mis_setup -> the same march on the pairs' explicit directions -> tir_relight_mis; 28 bytes of
+    bookkeeping per sample.  Needs the packed cell records."""
     dev = surface_xyz.device
     normal = normal.to(torch.float32).contiguous()
     M = normal.shape[0]
     if m_dev is not None and (not torch.is_tensor(m_dev) or m_dev.numel() != 1 or m_dev.dtype != torch.int32 or m_dev.device != dev):
         raise ValueError("m_dev: expected one int32 element on the points' device")
+    if mis is not None and not isinstance(mis, MisConfig):
+        raise TypeError(f"mis: None or a MisConfig, got {type(mis).__name__}")
+    if mis is not None and env.cell_records(light_name) is None:
+        raise ops._lib.TensoirHipError("multiple importance sampling needs the packed cell records (TENSOIR_ENV_RECORDS != 0)")
+    if mis is not None and M > 0:
+        dirs, cell, pdf_mix, vis0, pair_ids, n_active = env.sample_mis(light_name, normal, rays_d, roughness, num_samples, mis, m_dev)
+        vis, _, _ = ops.march_secondary(tensoIR.packed_field_dense(), surface_xyz.to(torch.float32).contiguous(), dirs.view(-1, 3),
+                                        _z_table(nSample, vis_near, vis_far, dev), M * num_samples, _org_map(M, num_samples, dev), None,
+                                        None, tensoIR.march_t_stop, False, 0, False, ray_ids=pair_ids, n_ids_dev=n_active,
+                                        vis=vis0.view(-1))
+        return ops.relight_mis(normal, albedo, roughness, fresnel, rays_d, dirs, cell, pdf_mix, env.cell_records(light_name),
+                               vis.view(M, num_samples), linear=mis.linear, m_dev=m_dev)
     if M == 0:
         # A call consumes one draw counter whatever M is (since round 5: the device-compacted chunk call, relight_chunk, cannot know
         # that a chunk is all background, and both routes must draw the same sequence).  Images rendered by rounds <= 4 with the
@@ -538,18 +605,10 @@ def relight_importance_sampled(tensoIR, env, light_name, surface_xyz, normal, al
         cell, vis0, pair_ids, n_active = env.sample_cells_listed(light_name, normal, num_samples, bins, block_pairs, m_dev)
         active = None
         listed = dict(ray_ids=pair_ids, n_ids_dev=n_active, vis=vis0.view(-1))
-    key = ("orgmap", M, num_samples, str(dev))
-    org_map = _CONST_CACHE.get(key)
-    if org_map is None:
-        pair = torch.arange(M * num_samples, dtype=torch.int32, device=dev)
-        org_map = torch.div(pair, num_samples, rounding_mode="floor").to(torch.int32)
-        if len(_CONST_CACHE) > 64:
-            _CONST_CACHE.clear()
-        _CONST_CACHE[key] = org_map
     z = _z_table(nSample, vis_near, vis_far, dev)
     env_dir = env.hdr_dir[light_name].view(-1, 3)
     vis, _, _ = ops.march_secondary(tensoIR.packed_field_dense(), surface_xyz.to(torch.float32).contiguous(), env_dir, z,
-                                    M * num_samples, org_map, cell.view(-1), None if active is None else active.view(-1),
+                                    M * num_samples, _org_map(M, num_samples, dev), cell.view(-1), None if active is None else active.view(-1),
                                     tensoIR.march_t_stop, False, 0, False, **listed)
     return ops.relight_importance_cells(normal, albedo, roughness, fresnel, rays_d, cell, env_dir,
                                         env.hdr_rgbs[light_name].view(-1, 3), env.hdr_pdf_return[light_name].view(-1),
@@ -558,7 +617,7 @@ def relight_importance_sampled(tensoIR, env, light_name, surface_xyz, normal, al
 
 @torch.no_grad()
 def relight_chunk(tensoIR, env, light_names, rays, light_idx, num_samples=512, nSample=96, vis_near=0.05, vis_far=1.5,
-                  N_samples=-1, out=None):
+                  N_samples=-1, out=None, mis=None):
     """One chunk of scripts/relight_importance.py:93-185 for ALL environment maps without a host round trip: primary pass ->
     the acc > 0.5 rows compacted ON THE DEVICE (the script's boolean-mask indexing, :99-113, is a synchronisation per chunk
     plus ~12 indexing launches) -> per map: importance sampling, visibility march and BRDF integration bounded by the
@@ -568,7 +627,8 @@ def relight_chunk(tensoIR, env, light_names, rays, light_idx, num_samples=512, n
     What the caller still applies, as the script does AFTER its loop body (scripts/relight_importance.py:166-176): hit rows hold the
     relit colour already clamped and sRGB-encoded by the integration kernel; BACKGROUND rows hold the raw environment lookup
     (Environment_Light.get_light) -- the script's clamp, tone mapping of the background and its `acc > 0.9` blend of the two
-    (`:172-176`) are the caller's (prim[6] is acc_map)."""
+    (`:172-176`) are the caller's (prim[6] is acc_map).
+    mis: relight_importance_sampled's (a MisConfig: map and BRDF sampling under the balance heuristic; None: as above)."""
     dev = rays.device
     rays = rays.to(torch.float32).contiguous()
     B = rays.shape[0]
@@ -579,7 +639,7 @@ def relight_chunk(tensoIR, env, light_names, rays, light_idx, num_samples=512, n
         out = torch.empty((B, 3 * max(len(names), 1)), dtype=torch.float32, device=dev)
     for i, name in enumerate(names):
         rgb = relight_importance_sampled(tensoIR, env, name, c["surf"], c["normal"], c["albedo"], c["rough"], c["fresnel"], c["rays_d"],
-                                         num_samples, nSample, vis_near, vis_far, m_dev=c["n_hit"])
+                                         num_samples, nSample, vis_near, vis_far, m_dev=c["n_hit"], mis=mis)
         ops.env_compose(env.hdr_rgbs[name], rays, c["slot"], rgb, out, 3 * i)
     return out, prim, c
 
@@ -608,7 +668,7 @@ def _map_rows(prim, B):
 
 @torch.no_grad()
 def relight_view(tensoIR, env, light_names, rays, H, W, light_idx=None, num_samples=512, chunk=4096, nSample=96, vis_near=0.05,
-                 vis_far=1.5, denoise=None):
+                 vis_far=1.5, denoise=None, mis=None):
     """A whole H x W view relit under every map of `light_names`: relight_chunk over chunks of `chunk` rays (rays [H * W, 6],
     row-major; light_idx [H * W] or [H * W, 1], default zeros) into one [H * W, 3 n_maps] buffer, the denoiser's guide rows packed
     next to it (tir_denoise_guide, one launch per chunk), and with denoise = a tensoir_amd.denoise.AtrousConfig the guided
@@ -617,6 +677,7 @@ def relight_view(tensoIR, env, light_names, rays, H, W, light_idx=None, num_samp
     "acc": [H, W]}.  Rows mean what relight_chunk documents: hit rows hold the clamped sRGB relit colour, background rows
     (acc <= 0.5: not valid in the guide) the raw environment lookup, which the filter neither changes nor reads.
     num_samples: importance samples per surface point and map -- with the filter, 16 to 64 instead of 512.
+    mis: relight_importance_sampled's (a MisConfig: map and BRDF sampling under the balance heuristic; None: map only).
     Single process: the multi-rank gather of the benchmark keeps its own loop."""
     from . import denoise as dn
     H, W, chunk = int(H), int(W), int(chunk)
@@ -625,6 +686,8 @@ def relight_view(tensoIR, env, light_names, rays, H, W, light_idx=None, num_samp
         raise ValueError(f"relight_view: rays is [H * W, 6] = [{H * W}, 6] and chunk >= 1, got {tuple(rays.shape)} and chunk {chunk}")
     if not 1 <= len(names) <= ops.ATROUS_MAX_K // 3:
         raise ValueError(f"relight_view: 1 to {ops.ATROUS_MAX_K // 3} environment maps, got {len(names)}")
+    if mis is not None and not isinstance(mis, MisConfig):
+        raise TypeError(f"relight_view: mis is None or a MisConfig, got {type(mis).__name__}")
     if denoise is not None and not isinstance(denoise, dn.AtrousConfig):
         raise TypeError(f"relight_view: denoise is None or an AtrousConfig, got {type(denoise).__name__}")
     if not rays.is_cuda:
@@ -639,7 +702,8 @@ def relight_view(tensoIR, env, light_names, rays, H, W, light_idx=None, num_samp
     acc = torch.empty((n,), dtype=torch.float32, device=dev)
     for r0 in range(0, n, chunk):
         r1 = min(r0 + chunk, n)
-        _, prim, _ = relight_chunk(tensoIR, env, names, rays[r0:r1], lidx[r0:r1], num_samples, nSample, vis_near, vis_far, out=rows[r0:r1])
+        _, prim, _ = relight_chunk(tensoIR, env, names, rays[r0:r1], lidx[r0:r1], num_samples, nSample, vis_near, vis_far, out=rows[r0:r1],
+                                   mis=mis)
         ops.denoise_guide(_map_rows(prim, r1 - r0), rays[r0:r1], guide, r0, 0.5)      # valid = relight_chunk's own acc > 0.5
         acc[r0:r1] = prim[6]
     image = lambda t: t.view(H, W, len(names), 3).permute(2, 0, 1, 3).contiguous()
