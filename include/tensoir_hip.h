@@ -915,6 +915,83 @@ int tir_simplify_emit(const float* verts, int64_t n_verts, const int32_t* faces,
                       const int32_t* offsets, int32_t n_out_verts, int32_t n_out_faces, int64_t* acc, int32_t* keys,
                       float* out_verts, float* out_normals, int32_t* out_faces, void* stream);
 
+/* ---- Surface distance between meshes: area-weighted samples, a uniform grid over a mesh's faces, exact point-to-mesh distance
+ *      (tensoir_amd/csrc/tir_distance.hip; ops.sample_surface / face_grid / point_mesh_distance, mesh.distance).
+ *   verts [V][3] fp32, faces [F][3] int32, V < 2^31, F <= 2^TIR_DISTANCE_MAX_FACES_LOG2.  A face with an index outside [0, V) sets
+ *   TIR_DISTANCE_ERR_FACE_INDEX in the status word of the entry that meets it, has no weight, is listed nowhere and is never
+ *   followed.  Every fp64 operation named below is rounded on its own (nothing is contracted into an FMA).
+ *
+ * a. Samples.  weight of face f: w_f = sqrt(|n|^2), n = (v1 - v0) x (v2 - v0) from the corners converted to fp64, differences,
+ *    products and the sum n_x^2 + n_y^2 + n_z^2 (added in that order) in fp64; a weight that is not finite counts as 0.
+ *    w_max = the largest weight (an integer maximum over the bit patterns: exact).  Integer weight q_f = trunc((w_f / w_max) * 2^s)
+ *    for w_f > 0, else 0, with s the largest integer <= 52 with F * 2^s <= 2^52: the total T = sum q_f stays below 2^53 and is the
+ *    same whatever the order of the sums.  cdf[f] = q_0 + ... + q_f (int64, inclusive).
+ *    Uniforms: hash(seed, i, ch), 64-bit wrapping arithmetic,
+ *        x = seed + 0x9E3779B97F4A7C15 * (3 i + ch + 1);  x ^= x >> 30;  x *= 0xBF58476D1CE4E5B9;  x ^= x >> 27;
+ *        x *= 0x94D049BB133111EB;  x ^= x >> 31;  u = x >> 40 (24 bits);  xi_ch = u * 2^-24 in [0, 1).
+ *    Sample i of n is stratified: pos = ((i + xi_0) / n) * T in fp64 (add, divide, multiply), k = min(trunc(pos), T - 1); its face
+ *    is the first f with cdf[f] > k (a face of integer weight 0 is never drawn).  Its point, in fp32 with xi_1, xi_2 as fp32:
+ *        s = sqrt(xi_1), b0 = 1 - s, b1 = s * (1 - xi_2), b2 = s * xi_2;  point = (b0 v0 + b1 v1) + b2 v2.
+ *    tir_mesh_sample_cdf fills cdf [F] (int64; sums [tir_distance_blocks(F)] int64 is workspace) and status [4] int64 = {T, error
+ *    bits, faces of integer weight 0, the bits of w_max}.  tir_mesh_sample draws n samples from a cdf with T > 0 (with T = 0 every
+ *    face is -1 and every point 0; the caller reads status first).  points [n][3] fp32, face [n] int32.
+ *
+ * b. Grid.  cell[3] > 0, origin[3] (HOST floats, finite), dims[3] in 1 .. TIR_DISTANCE_MAX_DIM (HOST int32).  The cell of a
+ *    coordinate x along an axis is clamp(floor((x - origin) / cell), 0, dim - 1): an fp32 subtract and an fp32 IEEE divide, each
+ *    rounded on its own.  The first and the last cell of an axis therefore reach to infinity; the function is monotone in x.
+ *    A face is listed in every cell from the cell of its bounding box's low corner to that of its high corner.  A face with a
+ *    non-finite corner, or with |n|^2 == 0 (a. above), is degenerate: listed nowhere, counted.
+ *    tir_face_grid_count writes status [4] int64 = {pairs (faces x cells they are listed in), error bits, degenerate faces, listed
+ *    faces} without visiting a cell.  The caller reads it back, REFUSES a total above its budget (nothing is ever truncated) and
+ *    calls tir_face_grid_fill with n_pairs = that total: cursor [cells] int32 (cells = dims_x dims_y dims_z, key =
+ *    (ix * dims_y + iy) * dims_z + iz), counts [tir_distance_blocks(cells)], offsets [that + 1] int32 workspace, pairs [n_pairs]
+ *    int32.  Per-cell counts by integer atomics, block sums, tir_exclusive_scan, first slots, fill.  Afterwards cell key lists
+ *    pairs[cursor[key - 1] .. cursor[key]) (from 0 for key 0), in an order that may differ from run to run.
+ *
+ * c. Distance.  tir_point_mesh_distance: points [n][3] fp32 -> dist [n] fp32 = the Euclidean distance to the nearest point of any
+ *    listed face, face [n] int32 = that face, closest [n][3] fp32 = that point (NULL skips it), tested [n] int32 = point-triangle
+ *    tests made (NULL skips it).  Per face, in fp64 on coordinates relative to corner a (ab = b - a, ac = c - a, ap = p - a), the
+ *    seven regions of the closest point a + v ab + w ac:
+ *        d1 = ab.ap, d2 = ac.ap, bp = ap - ab, d3 = ab.bp, d4 = ac.bp, cp = ap - ac, d5 = ab.cp, d6 = ac.cp,
+ *        vc = d1 d4 - d3 d2, vb = d5 d2 - d1 d6, va = d3 d6 - d5 d4; the first that holds of
+ *        d1 <= 0 and d2 <= 0: (0, 0) | d3 >= 0 and d4 <= d3: (1, 0) | vc <= 0, d1 >= 0, d3 <= 0: (d1 / (d1 - d3), 0) |
+ *        d6 >= 0 and d5 <= d6: (0, 1) | vb <= 0, d2 >= 0, d6 <= 0: (0, d2 / (d2 - d6)) |
+ *        va <= 0, d4 - d3 >= 0, d5 - d6 >= 0: w = (d4 - d3) / ((d4 - d3) + (d5 - d6)), v = 1 - w | else (vb, vc) / (va + vb + vc);
+ *        D = |ap - (v ab + w ac)|^2.  dist = fp32(sqrt(min D)); among faces of equal D the smaller index wins.
+ *    Search: from the cell of the point (clamped into the grid) over shells of growing Chebyshev radius r.  After shell r, every
+ *    unvisited cell lies beyond one of the planes origin + (c - r) cell (if c - r > 0) or origin + (c + r + 1) cell (if c + r + 1 <
+ *    dim) of some axis; b = the smallest distance of the point ITSELF (not of its clamped cell) to those planes, each reduced by
+ *    TIR_DISTANCE_SLACK * cell, which exceeds the rounding of the cell function (two fp32 roundings on an index <= 2^8: 2^-14 of
+ *    a cell).  The search stops only when b > 0 and b^2 > min D, and inside a shell a cell is skipped only when the squared
+ *    distance of the point to the cell's box, widened by the same slack per axis, exceeds min D; so no face that could be as
+ *    near, or tie, is left out: the
+ *    outputs are bit-identical for every grid over the same faces, for every fill order, and for points far outside the grid.
+ *    No listed face: dist = +inf, face = -1, closest = NaN.  A non-finite point: dist = NaN, face = -1, closest = NaN.
+ *
+ * Every entry validates on the host before any device work: a null pointer, a negative count, cell <= 0 (or not finite), a
+ * non-finite origin, dims < 1 -> TIR_ERR_ARG; dims > TIR_DISTANCE_MAX_DIM, V or n or n_pairs > 2^31-1, F > 2^28 ->
+ * TIR_ERR_UNSUPPORTED.  n = 0, F = 0 for the cdf and the count, n_pairs = 0 for the fill return TIR_OK before any device work:
+ * the caller hands those three a zeroed status / cursor, which then stays as it is.  No access leaves the buffers for any
+ * input: slots and list bounds are clamped to n_pairs, listed faces and their indices are checked again by the query. */
+#define TIR_DISTANCE_MAX_FACES_LOG2 28
+#define TIR_DISTANCE_MAX_DIM 256
+#define TIR_DISTANCE_SLACK (1.0 / 8192.0)
+#define TIR_DISTANCE_ERR_FACE_INDEX 1    /* a face index outside [0, V)                                          */
+int64_t tir_distance_blocks(int64_t n);
+int tir_mesh_sample_cdf(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, int64_t* cdf, int64_t* sums,
+                        int64_t* status, void* stream);
+int tir_mesh_sample(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, const int64_t* cdf, int64_t n,
+                    uint64_t seed, float* points, int32_t* face, void* stream);
+int tir_face_grid_count(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, const float* cell,
+                        const float* origin, const int32_t* dims, int64_t* status, void* stream);
+int tir_face_grid_fill(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, const float* cell,
+                       const float* origin, const int32_t* dims, int64_t n_pairs, int32_t* cursor, int32_t* counts,
+                       int32_t* offsets, int32_t* pairs, void* stream);
+int tir_point_mesh_distance(const float* points, int64_t n, const float* verts, int64_t n_verts, const int32_t* faces,
+                            int64_t n_faces, const float* cell, const float* origin, const int32_t* dims, const int32_t* cursor,
+                            const int32_t* pairs, int64_t n_pairs, float* dist, int32_t* face, float* closest, int32_t* tested,
+                            void* stream);
+
 /* ---- per-point bake of materials and direct lighting (tensoir_amd/bake.py).  Point p is marched inward from
  * origins[p] along dirs[p] by tir_march_secondary_fwd with records; the caller decodes every record (BRDF decoder output
  * rec_brdf [A][4] = albedo rgb + raw roughness, shading normal rec_normal [A][3]).

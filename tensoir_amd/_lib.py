@@ -171,6 +171,13 @@ SIGNATURES = {
     "tir_simplify_count": (C.c_int, [P, I64, P, I64, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(I32), P, P, P, P, P, P]),
     "tir_simplify_emit": (C.c_int, [P, I64, P, I64, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(I32), C.c_double, P, P,
                                     I32, I32, P, P, P, P, P, P]),
+    "tir_distance_blocks": (I64, [I64]),
+    "tir_mesh_sample_cdf": (C.c_int, [P, I64, P, I64, P, P, P, P]),
+    "tir_mesh_sample": (C.c_int, [P, I64, P, I64, P, I64, C.c_uint64, P, P, P]),
+    "tir_face_grid_count": (C.c_int, [P, I64, P, I64, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(I32), P, P]),
+    "tir_face_grid_fill": (C.c_int, [P, I64, P, I64, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(I32), I64, P, P, P, P, P]),
+    "tir_point_mesh_distance": (C.c_int, [P, I64, P, I64, P, I64, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(I32), P, P,
+                                          I64, P, P, P, P, P]),
     "tir_bake_composite": (C.c_int, [P, P, P, P, P, P, P, P, P, C.POINTER(C.c_float), I64, I64, P, P]),
     "tir_irradiance_integrate": (C.c_int, [P, P, P, P, P, P, I64, I32, I32, P, P]),
     "tir_atlas_corners": (C.c_int, [P, I64, P, P, I64, I32, I32, I32, P, P, P, P, P, P]),

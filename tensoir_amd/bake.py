@@ -180,6 +180,13 @@ def main(argv=None):
     ap.add_argument("--connectivity", type=int, choices=(6, 26), default=6, help="what joins two lattice points into one component")
     ap.add_argument("--simplify", type=int, default=None, metavar="K", help="reduce the mesh by quadric vertex clustering: one "
                     "vertex per block of K x K x K lattice cells (K >= 2); the attributes are baked at the reduced vertices")
+    ap.add_argument("--simplify-tolerance", type=float, default=None, metavar="T", help="instead of --simplify: take the largest K "
+                    "in 2 .. --simplify-max whose mesh stays within T lattice cells (Hausdorff distance) of the full-resolution one; "
+                    "the search stops at the first K that does not")
+    ap.add_argument("--simplify-max", type=int, default=mesh.SIMPLIFY_MAX, metavar="K", help="the largest K --simplify-tolerance tries")
+    ap.add_argument("--check-distance", type=int, nargs="?", const=262144, default=None, metavar="N", help="after writing OUT (.ply or "
+                    ".glb), read it back and print its surface distance (mesh.distance, N samples per direction, default 262144) "
+                    "to the full-resolution extraction as one JSON line")
     ap.add_argument("--texture-size", type=int, default=None, metavar="N", help="write OUT as a binary glTF (.glb) with an N x N "
                     "texture atlas baked at every texel (base colour, occlusion / roughness / metallic, normal) instead of a PLY "
                     "with per-vertex attributes")
@@ -207,6 +214,11 @@ def main(argv=None):
         ap.error("--write-views writes the images of --check-light")
     if a.check_shadows and a.check_light is None:
         ap.error("--check-shadows shadows the light of --check-light")
+    if a.simplify_tolerance is not None and a.simplify is not None:
+        ap.error("--simplify K and --simplify-tolerance T are mutually exclusive")
+    if a.check_distance is not None and a.check_distance < 0:
+        ap.error("--check-distance N: N >= 0")
+    simp = {"simplify": a.simplify, "simplify_tolerance": a.simplify_tolerance, "simplify_max": a.simplify_max}
     extra = {} if a.envmap is None else {"envmap_h": a.envmap[0], "envmap_w": a.envmap[1]}
     model = load_model(a.ckpt, "cuda", **extra)
     grid = None if a.grid is None else [a.grid] * 3
@@ -214,20 +226,33 @@ def main(argv=None):
     if a.texture_size is not None:
         nv, nf = mesh.export_textured(model, a.out, a.level, grid, a.texture_size, a.color, light_idx=a.light,
                                       keep_largest=a.keep_largest, min_component_voxels=a.min_component_voxels,
-                                      connectivity=a.connectivity, report=report, simplify=a.simplify)
+                                      connectivity=a.connectivity, report=report, **simp)
     else:
         nv, nf = mesh.export_mesh(model, a.out, a.level, grid, attributes=True, color=a.color, light_idx=a.light,
                                   keep_largest=a.keep_largest, min_component_voxels=a.min_component_voxels,
-                                  connectivity=a.connectivity, report=report, simplify=a.simplify)
+                                  connectivity=a.connectivity, report=report, **simp)
     if "table" in report:
         sizes, kept = report["table"]["sizes"].cpu(), report["kept"].cpu()
         print(f"components: dropped {int((~kept).sum())} of {kept.numel()} ({int(sizes[~kept].sum())} of {int(sizes.sum())} voxels)")
     if "full" in report:
-        print(f"simplify {a.simplify}: {report['full'][0]} vertices, {report['full'][1]} faces before")
+        print(f"simplify {report.get('simplify', a.simplify)}: {report['full'][0]} vertices, {report['full'][1]} faces before")
+    if "simplify_error" in report:
+        import json
+        print(json.dumps({"simplify": report["simplify"], "simplify_error": {str(k): v for k, v in report["simplify_error"].items()}}))
     print(f"{a.out}: {nv} vertices, {nf} faces")
     if a.environment is not None:
         mesh.export_environment(model, a.environment, a.environment_size[0], a.environment_size[1], light=a.light)
         print(f"{a.environment}: light {a.light}, {a.environment_size[0]} x {a.environment_size[1]}")
+    if a.check_distance is not None:
+        import json
+        import torch
+        from . import metrics
+        full_v, full_f, _ = mesh.extract_mesh(model, a.level, grid, keep_largest=a.keep_largest,
+                                              min_component_voxels=a.min_component_voxels, connectivity=a.connectivity)
+        if a.texture_size is not None:                     # the writer unwelds: three vertices per face, no index buffer
+            full_v = full_v[full_f.reshape(-1).long()].contiguous()
+            full_f = torch.arange(full_v.shape[0], dtype=torch.int32, device=full_v.device).view(-1, 3)
+        print(json.dumps({"check_distance": metrics.chamfer(a.out, (full_v, full_f), samples=a.check_distance)}))
     if a.check_views is not None:
         import json
         from . import raster

@@ -3,6 +3,7 @@
     from tensoir_amd import metrics
     metrics.ssim(img, gt)                      # the number utils.rgb_ssim(img, gt, 1) gives, from one HIP launch
     metrics.evaluate(model, dataset)           # the reference's test report for a checkpoint, every map kept on the device
+    metrics.chamfer("mesh.ply", "gt.ply")      # Chamfer / Hausdorff distance of two meshes (mesh.distance; tir_distance.hip)
     python -m tensoir_amd.metrics CKPT --config configs/... [--views N]
 
 ssim / psnr / normal_mae take numpy arrays or torch tensors on any device; host inputs are uploaded and host results come back
@@ -126,6 +127,37 @@ def normal_mae(a, b, mask=None):
         raise ValueError("normal_mae: [..., 3] maps")
     cnt, _, ang, _ = _errors(a, b, mask, True)
     return ang / cnt if cnt else float("nan")
+
+
+def _mesh_on_device(m, dev):
+    """(verts, faces) tensors, or the path of a .ply / .glb file as mesh.write_ply / export_mesh / export_textured write them."""
+    from . import mesh
+    if isinstance(m, (str, bytes)) or hasattr(m, "__fspath__"):
+        import os
+        path = os.fspath(m)
+        path = path.decode() if isinstance(path, bytes) else path
+        if path.lower().endswith(".glb"):
+            v = mesh.read_glb(path)["pos"]                            # unwelded: three vertices per face, no index buffer
+            f = np.arange(v.shape[0], dtype=np.int32).reshape(-1, 3)
+        elif path.lower().endswith(".ply"):
+            v, f, _ = mesh.read_ply_attributes(path)
+        else:
+            raise ValueError(f"chamfer: {path!r} is neither a .ply nor a .glb file")
+        m = (v, f)
+    v, f = m
+    v = torch.as_tensor(np.ascontiguousarray(v) if isinstance(v, np.ndarray) else v).to(dev, torch.float32).reshape(-1, 3)
+    f = torch.as_tensor(np.ascontiguousarray(f) if isinstance(f, np.ndarray) else f).to(dev, torch.int32).reshape(-1, 3)
+    return v.contiguous(), f.contiguous()
+
+
+def chamfer(a, b, **kw):
+    """mesh.distance under the name of the geometry figure of inverse-rendering papers: the Chamfer distance of a recovered
+    mesh to a ground-truth one is result["chamfer"] (the sum of the two mean surface distances, in the meshes' coordinates).
+    a, b: (verts, faces) tensors or arrays, or paths to .ply / .glb files; kw: mesh.distance's samples and seed.  Host inputs
+    are uploaded; there is no CPU path."""
+    from . import mesh
+    dev = _device_of(*[x for m in (a, b) if isinstance(m, (tuple, list)) for x in m])
+    return mesh.distance(_mesh_on_device(a, dev), _mesh_on_device(b, dev), **kw)
 
 
 def albedo_scale(pred, gt, mask):

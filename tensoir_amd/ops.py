@@ -1663,6 +1663,186 @@ def simplify_mesh(verts, faces, cell, origin=(0.0, 0.0, 0.0), dims=None, reg=1e-
     return out_v, out_f, out_n, cov
 
 
+# ---- surface distance between meshes (tir_distance.hip) ------------------------------
+DISTANCE_MAX_DIM = 256
+DISTANCE_CELL_FACTOR = 2.0
+_DISTANCE_FACE_INDEX = "a face index lies outside [0, V)"
+
+
+def _mesh_args(verts, faces):
+    verts = f32(verts, "verts", 3).view(-1, 3)
+    faces = i32(faces, "faces").view(-1, 3)
+    if faces.device != verts.device:
+        raise ValueError("faces: expected the device of verts")
+    return verts, faces
+
+
+def sample_surface(verts, faces, n, seed=0):
+    """n area-weighted, stratified samples of a mesh's surface (tir_mesh_sample_cdf + tir_mesh_sample; the definition, hash
+    included: include/tensoir_hip.h).  verts [V, 3] f32 and faces [F, 3] i32 on the GPU -> (points [n, 3] f32, face [n] i32) on
+    verts' device, samples in face order.  The weights are quantised to integers and summed as integers, so the face of every
+    sample is the same on every run and on every device order; faces of integer weight 0 (zero area among them) get no sample.
+    One 32-byte read-back (total, error word, statistics; one sync).  A face index outside [0, V) raises TensoirHipError
+    ("face index"), a mesh without any area TensoirHipError ("degenerate"); an empty `faces` with n > 0 raises ValueError."""
+    verts, faces = _mesh_args(verts, faces)
+    n, seed = int(n), int(seed)
+    if n < 0:
+        raise ValueError("sample_surface: n >= 0")
+    if not 0 <= seed < 2 ** 64:
+        raise ValueError("sample_surface: seed is an unsigned 64-bit integer")
+    V, F = verts.shape[0], faces.shape[0]
+    dev = verts.device
+    if n > 0 and F == 0:
+        raise ValueError("sample_surface: a mesh without faces has no surface to sample")
+    points = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    face = torch.empty((n,), dtype=torch.int32, device=dev)
+    if n == 0:
+        return points, face
+    nb = int(lib().tir_distance_blocks(F))
+    cdf = torch.empty((F,), dtype=torch.int64, device=dev)
+    sums = torch.empty((max(nb, 1),), dtype=torch.int64, device=dev)
+    status = torch.zeros((4,), dtype=torch.int64, device=dev)
+    _call("tir_mesh_sample_cdf", _ptr(verts if V else None), V, _ptr(faces), F, _ptr(cdf), _ptr(sums), _ptr(status), _stream())
+    total, err, _, _ = [int(x) for x in status.cpu()]
+    if err:
+        raise _lib.TensoirHipError("sample_surface: " + _DISTANCE_FACE_INDEX)
+    if total <= 0:
+        raise _lib.TensoirHipError("sample_surface: every face is degenerate (no area to sample)")
+    _call("tir_mesh_sample", _ptr(verts), V, _ptr(faces), F, _ptr(cdf), n, seed, _ptr(points), _ptr(face), _stream())
+    return points, face
+
+
+def _grid_triplet(x, name, kind):
+    vals = [kind(x)] * 3 if isinstance(x, (int, float)) else [kind(v) for v in x]
+    if len(vals) != 3:
+        raise ValueError(f"{name} takes one or three values")
+    return vals
+
+
+def _face_grid_count(verts, faces, cell, origin, dims):
+    V, F = verts.shape[0], faces.shape[0]
+    c_cell, c_org = (C.c_float * 3)(*cell), (C.c_float * 3)(*origin)
+    c_dims = (C.c_int32 * 3)(*[max(min(d, 2 ** 31 - 1), -1) for d in dims])
+    status = torch.zeros((4,), dtype=torch.int64, device=verts.device)      # (F = 0 returns before any device work)
+    # (the library words the refusal of cell <= 0 and of dims beyond the limit: it validates them on the host first)
+    _call("tir_face_grid_count", _ptr(verts if V else None), V, _ptr(faces if F else None), F, c_cell, c_org, c_dims, _ptr(status),
+          _stream())
+    pairs, err, degenerate, listed = [int(x) for x in status.cpu()]
+    if err:
+        raise _lib.TensoirHipError("face_grid: " + _DISTANCE_FACE_INDEX)
+    return pairs, degenerate, listed, (c_cell, c_org, c_dims)
+
+
+def face_grid(verts, faces, cell=None, max_pairs=None, *, dims=None, origin=None):
+    """A uniform grid over a mesh's faces for point_mesh_distance (tir_face_grid_count + tir_face_grid_fill; the definition:
+    include/tensoir_hip.h).  verts [V, 3] f32, faces [F, 3] i32 on the GPU.  Every non-degenerate face is listed in every cell
+    its bounding box overlaps; a face without area (|cross|^2 == 0 in fp64) or with a non-finite corner is listed nowhere and
+    counted in "degenerate".  origin (default): the smallest finite vertex coordinates; dims (default): floor(extent / cell) + 1.
+    cell (one value or three): the cell edge.  cell=None chooses it: DISTANCE_CELL_FACTOR x the mean edge of the faces' finite
+    bounding boxes (all three axes together), raised per axis to extent / DISTANCE_MAX_DIM so that dims stay <= 256, and then
+    doubled (all axes) until the pairs fit max_pairs; with dims given and no cell, cell = extent / dims per axis.
+    max_pairs: the most (face, cell) pairs the grid may hold, default max(16 F, 2^20) (at most 2^31 - 1).  A total above it
+    with an explicit cell is REFUSED, TensoirHipError ("pairs", with the true total) -- never truncated.  A grid of 1 x 1 x 1
+    lists every face in its one cell: the brute-force path.
+    -> {"cell", "origin", "dims": host lists, "cursor" [cells] i32 (the end of every cell's list), "pairs" [P] i32 (face
+    indices; the order inside a cell may differ between runs, no result of point_mesh_distance depends on it), "n_pairs",
+    "degenerate", "listed", "n_faces", "n_verts"}.  One small read-back for the bounding box (and the mean edge), then one
+    32-byte read-back (pair total, error word, statistics) per cell edge tried; a face index outside [0, V) raises
+    TensoirHipError ("face index")."""
+    verts, faces = _mesh_args(verts, faces)
+    V, F = verts.shape[0], faces.shape[0]
+    dev = verts.device
+    limit = 2 ** 31 - 1
+    max_pairs = min(max(16 * F, 2 ** 20), limit) if max_pairs is None else int(max_pairs)
+    if not 0 <= max_pairs <= limit:
+        raise ValueError(f"face_grid: max_pairs in 0 .. {limit}")
+    lo = hi = None
+    if V:
+        fin = torch.isfinite(verts)
+        big = torch.finfo(torch.float32).max
+        lo_t = torch.where(fin, verts, torch.full_like(verts, big)).amin(0)
+        hi_t = torch.where(fin, verts, torch.full_like(verts, -big)).amax(0)
+        mean_edge = None
+        if cell is None and dims is None and F:
+            idx = faces.long().clamp(0, V - 1)
+            tri = verts[idx]                                          # [F, 3, 3]
+            ext = tri.amax(1) - tri.amin(1)
+            ok = torch.isfinite(ext)
+            mean_edge = torch.where(ok, ext, torch.zeros_like(ext)).double().sum() / ok.sum().clamp(min=1)
+        host = torch.cat([lo_t.double(), hi_t.double(), torch.zeros(1, dtype=torch.float64, device=dev) if mean_edge is None
+                          else mean_edge.reshape(1)]).cpu().tolist()
+        lo, hi, mean_edge = host[:3], host[3:6], host[6]
+        if any(l > h for l, h in zip(lo, hi)):
+            lo = hi = None
+    if lo is None:
+        lo, hi, mean_edge = [0.0] * 3, [0.0] * 3, 0.0
+    org = lo if origin is None else _grid_triplet(origin, "origin", float)
+    extent = [max(h - o, 0.0) for h, o in zip(hi, org)]
+    auto = cell is None and dims is None
+    if cell is not None:
+        cl = _grid_triplet(cell, "cell", float)
+    elif dims is not None:
+        dm = _grid_triplet(dims, "dims", int)
+        cl = [e / max(d, 1) * (1.0 + 1e-6) if e > 0 else 1.0 for e, d in zip(extent, dm)]
+    else:
+        base = DISTANCE_CELL_FACTOR * mean_edge if mean_edge > 0 else max(max(extent), 1.0)
+        cl = [max(base, e / DISTANCE_MAX_DIM * (1.0 + 1e-6)) for e in extent]
+    while True:
+        if dims is not None:
+            dm = _grid_triplet(dims, "dims", int)
+        elif auto:
+            dm = [min(int(e / c) + 1, DISTANCE_MAX_DIM) for e, c in zip(extent, cl)]
+        else:
+            dm = [int(min(e / c, 2.0 ** 31 - 2)) + 1 if c > 0 else 1 for e, c in zip(extent, cl)]
+        pairs, degenerate, listed, cargs = _face_grid_count(verts, faces, cl, org, dm)
+        if pairs <= max_pairs:
+            break
+        if not auto or max(dm) == 1:
+            raise _lib.TensoirHipError(f"face_grid: the grid needs {pairs} (face, cell) pairs, max_pairs allows {max_pairs}; "
+                                       "nothing is truncated -- take a larger cell or raise max_pairs")
+        cl = [2.0 * c for c in cl]
+    n_cells = dm[0] * dm[1] * dm[2]
+    nbc = int(lib().tir_distance_blocks(n_cells))
+    cursor = torch.empty((n_cells,), dtype=torch.int32, device=dev) if pairs else torch.zeros((n_cells,), dtype=torch.int32, device=dev)
+    counts = torch.empty((max(nbc, 1),), dtype=torch.int32, device=dev)
+    offsets = torch.empty((nbc + 1,), dtype=torch.int32, device=dev)
+    plist = torch.empty((pairs,), dtype=torch.int32, device=dev)
+    _call("tir_face_grid_fill", _ptr(verts if V else None), V, _ptr(faces if F else None), F, *cargs, pairs, _ptr(cursor), _ptr(counts),
+          _ptr(offsets), _ptr(plist if pairs else None), _stream())
+    return {"cell": [float(c) for c in cargs[0]], "origin": [float(o) for o in cargs[1]], "dims": dm, "cursor": cursor, "pairs": plist,
+            "n_pairs": pairs, "degenerate": degenerate, "listed": listed, "n_faces": F, "n_verts": V}
+
+
+def point_mesh_distance(points, verts, faces, grid=None, closest=False, tested=False):
+    """The exact unsigned distance of points to a mesh (tir_point_mesh_distance; the definition: include/tensoir_hip.h).
+    points [n, 3] f32, verts [V, 3] f32, faces [F, 3] i32 on one GPU; grid: face_grid(verts, faces) of THIS mesh (None builds
+    the default one).  -> (dist [n] f32, face [n] i32), plus closest [n, 3] f32 with closest=True and the number of
+    point-triangle tests [n] i32 with tested=True.  The closest point per triangle is found in fp64 (seven regions), the search
+    walks shells of grid cells and stops only when no unvisited cell can hold a face as near; ties go to the smaller face index:
+    the outputs are bit-identical for every grid over the same faces and on every run.  A mesh without a listed face gives
+    dist = +inf and face = -1, a non-finite point dist = NaN and face = -1.  No read-back when a grid is handed in."""
+    verts, faces = _mesh_args(verts, faces)
+    points = f32(points, "points", 3).view(-1, 3)
+    dev = verts.device
+    if points.device != dev:
+        raise ValueError("points: expected the device of verts")
+    if grid is None:
+        grid = face_grid(verts, faces)
+    V, F, n = verts.shape[0], faces.shape[0], points.shape[0]
+    if grid["n_faces"] != F or grid["n_verts"] != V or grid["cursor"].device != dev:
+        raise ValueError("grid: not a face_grid of this mesh")
+    dist = torch.empty((n,), dtype=torch.float32, device=dev)
+    face = torch.empty((n,), dtype=torch.int32, device=dev)
+    cl = torch.empty((n, 3), dtype=torch.float32, device=dev) if closest else None
+    nt = torch.empty((n,), dtype=torch.int32, device=dev) if tested else None
+    P = grid["n_pairs"]
+    _call("tir_point_mesh_distance", _ptr(points if n else None), n, _ptr(verts if V else None), V, _ptr(faces if F else None), F,
+          (C.c_float * 3)(*grid["cell"]), (C.c_float * 3)(*grid["origin"]), (C.c_int32 * 3)(*grid["dims"]), _ptr(grid["cursor"]),
+          _ptr(grid["pairs"] if P else None), P, _ptr(dist if n else None), _ptr(face if n else None),
+          _ptr(cl if closest and n else None), _ptr(nt if tested and n else None), _stream())
+    return (dist, face) + ((cl,) if closest else ()) + ((nt,) if tested else ())
+
+
 # ---- per-point bake (tensoir_amd/bake.py) ---------------------------------------------------------
 BAKE_ROW = 16
 
