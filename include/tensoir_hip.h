@@ -80,6 +80,14 @@ typedef struct TirField {
      * NULL / 0 (a zeroed descriptor) = no volume, the VM kernels run.  The caller rebuilds V when the field changes. */
     const float* dense_sigma;
     int32_t dense_pitch;
+    /* Optional dense appearance-feature volume of a field with ONE light (tir_dense_app_build): for grid corner (x, y, z) the
+     * 27 radiance features basis_mat . (plane x line x light row 0) as fp16, [z][y][x of dense_app_pitch >= grid[0] + 1]
+     * [half 2][16]: half 0 = features 0..13, half 1 = features 14..26, unused slots 0, 64 bytes per corner, 16-byte aligned,
+     * below 4 GiB.  Inside a grid cell the features are multilinear, so the trilinear lookup equals them in real arithmetic.
+     * The fp16 indirect-light entries (tir_vm_app_fwd_h16, tir_indirect_fused_fwd) read it instead of the fp16 shadow taps when
+     * it is given and n_lights == 1; NULL / 0 = no volume.  The caller rebuilds it when the field changes. */
+    int32_t dense_app_pitch;
+    const void* dense_app;
 } TirField;
 
 /* fp16 shadow of the appearance planes / lines (same channel-last element order as TirField::aplane / aline; 16-byte aligned),
@@ -171,6 +179,14 @@ int tir_filter_rays(const TirField* f, const float* rays, int64_t n, int32_t n_s
  *      arithmetic; UNSUPPORTED without a volume).  Out-of-range corners carry weight 0 as in the VM gather. */
 int tir_dense_sigma_build(const TirField* f, float* vol, int32_t pitch, void* stream);
 int tir_dense_sigma_fwd(const TirField* f, const float* xyz, float* feat, float* sigma, int64_t n, void* stream);
+
+/* ---- dense appearance-feature volume (TirField::dense_app; 48 components per plane, app_dim 27, ONE light).
+ *      tir_dense_app_build: vol [grid z][grid y][pitch][2][16] fp16 (pitch >= grid x + 1 corners, 16-byte aligned, below
+ *      4 GiB) receives the radiance features of light row 0 at every grid corner: the 144 plane x line x light products and
+ *      their basis_mat sums in fp32, rounded to fp16 once (saturating); corners [grid x, pitch) of every row and the unused
+ *      slots are 0.  f->dense_app is not read.  TIR_ERR_ARG: null / misaligned volume, pitch without the spare corner;
+ *      TIR_ERR_UNSUPPORTED: n_lights != 1, another width, a volume beyond 32-bit byte offsets. */
+int tir_dense_app_build(const TirField* f, void* vol, int32_t pitch, void* stream);
 
 /* ---- K6: analytic d sigma/d xyz and derived normal -normalize(grad, eps=1e-6)
  *      (compute_derived_normals models/tensorBase_rotated_lights.py:839-856 ->

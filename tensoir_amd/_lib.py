@@ -31,6 +31,7 @@ class TirField(C.Structure):
         ("occ_lo", C.c_float * 3), ("occ_hi", C.c_float * 3),
         ("tune_lds_lines", C.c_int32), ("tune_xcd_order", C.c_int32),
         ("dense_sigma", C.c_void_p), ("dense_pitch", C.c_int32),
+        ("dense_app_pitch", C.c_int32), ("dense_app", C.c_void_p),
     ]
 
 
@@ -75,6 +76,7 @@ SIGNATURES = {
     "tir_filter_rays": (C.c_int, [C.POINTER(TirField), P, I64, I32, I32, P, P]),
     "tir_dense_sigma_build": (C.c_int, [C.POINTER(TirField), P, I32, P]),
     "tir_dense_sigma_fwd": (C.c_int, [C.POINTER(TirField), P, P, P, I64, P]),
+    "tir_dense_app_build": (C.c_int, [C.POINTER(TirField), P, I32, P]),
     "tir_density_grad_fwd": (C.c_int, [C.POINTER(TirField), P, P, P, P, I64, P, P]),
     "tir_density_feat_grad_fwd": (C.c_int, [C.POINTER(TirField), P, P, P, I64, P]),
     "tir_vm_app_fwd": (C.c_int, [C.POINTER(TirField), P, P, P, P, P, I32, I32, I64, P, P]),

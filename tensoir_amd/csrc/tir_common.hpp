@@ -74,6 +74,23 @@ static inline bool tir_dense_sigma_ok(const TirField* f) {
     return f->grid[0] >= 2 && Y >= 1 && Z >= 1 && Y * Z < (1 << 24) && pb < (1 << 24) && Y * Z * pb < ((int64_t)1 << 32);
 }
 
+// the dense appearance-feature volume (64 B per corner) is addressed with 32-bit BYTE offsets formed by 24-bit multiplies
+// (tir::dense_app_lookup): grid y * grid z and the row bytes below 2^24, the volume below 4 GiB
+static inline bool tir_dense_app_index_ok(const int32_t (&grid)[3], int64_t pitch) {
+    const int64_t Y = grid[1], Z = grid[2], pb = pitch * 64;
+    return grid[0] >= 2 && Y >= 1 && Z >= 1 && Y * Z < (1 << 24) && pb < (1 << 24) && Y * Z * pb < ((int64_t)1 << 32);
+}
+
+// What the fp16 indirect-light entries make of TirField::dense_app: 0 = no volume (or a field of several lights, whose features
+// one volume cannot hold): the shadow-tap kernels run; 1 = the lookup kernels run; TIR_ERR_ARG for a pitch without a volume,
+// a volume without the spare corner per row or a misaligned one; TIR_ERR_UNSUPPORTED beyond the 32-bit offsets.
+static inline int tir_dense_app_route(const TirField* f) {
+    if (!f->dense_app) return f->dense_app_pitch ? TIR_ERR_ARG : 0;
+    if (f->dense_app_pitch <= f->grid[0] || reinterpret_cast<uintptr_t>(f->dense_app) % 16 != 0) return TIR_ERR_ARG;
+    if (!tir_dense_app_index_ok(f->grid, f->dense_app_pitch)) return TIR_ERR_UNSUPPORTED;
+    return f->n_lights == 1 && f->n_acomp == 48 && f->app_dim == 27 ? 1 : 0;
+}
+
 // ---- host side of the gather and decoder entry points (tir_field.hip, tir_mlp.hip, tir_vm_app_bwd): every precondition and
 // every launch formula is stated once here; where the entries differ, the difference is an argument with its reason.
 static inline bool tir_any_null(std::initializer_list<const void*> ptrs) {
@@ -711,6 +728,99 @@ __device__ __forceinline__ float dense_feature(const TirField& f, float x, float
     const float e = fmaf(b, ty.w.y, a * ty.w.x), g = fmaf(d, ty.w.y, c * ty.w.x);
     return fmaf(g, tz.w.y, e * tz.w.x);
 }
+// ---- radiance features from the dense appearance volume (TirField::dense_app, built by tir_dense_app_build; ONE light).
+// With one tap pair per axis for planes and line alike, plane x line x light row is multilinear inside a cell and the linear
+// basis_mat contraction keeps it so: the 27 features at a point are the trilinear interpolation of the corner features, with
+// make_tap_q's fractions and its zero weights for out-of-range corners.  The caller is lane (record, half h) of the fused
+// decoder layout: it loads its own 2 x 16 B of each of the 8 corners (all 16 loads issued before the first use) and gets slot
+// r = feature 14 h + r of the record, unclamped.
+// The masked weights of an out-of-range pair do not sum to 1, so a level is a weighted sum a w0 + b w1 (two instructions), not
+// a one-instruction lerp; the form here is the sum over the 8 corners with the products wx wy wz formed once per record in
+// fp32: per fp16 pair two chains of 1 multiply + 3 FMA (the z0 and the z1 face) and one add -- 9 packed instructions instead
+// of 14, five fp16 roundings on a path instead of six.
+// F32 = false: the sums on the packed fp16 pipe (v_pk_mul_f16 / v_pk_fma_f16, fp16 weights).  F32 = true: fp32 weights and
+// fp32 accumulation of the fp16 corners (v_fma_mix_f32), 128 fp32-class instructions instead of 72 packed ones.
+// 32-bit byte offsets on the 24-bit multiplier: grid y * grid z and the row bytes below 2^24, the volume below 4 GiB
+// (tir_dense_app_index_ok); every index is clamped to the grid (make_tap_q), so every load lies inside the volume.
+
+__device__ __forceinline__ uint4 ld16b(const void* base, unsigned byte_off) {
+    return *reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(base) + byte_off);
+}
+
+template <bool F32>
+__device__ __forceinline__ void dense_app_lookup(const TirField& f, float x, float y, float z, int h, float (&fo)[16]) {
+    const TapQ tx = make_tap_q(x, f.grid[0]), ty = make_tap_q(y, f.grid[1]), tz = make_tap_q(z, f.grid[2]);
+    const unsigned pb = (unsigned)f.dense_app_pitch * 64u, hb = 32u * (unsigned)h;
+    const unsigned xo[2] = {mad_u24(tx.i0, 64u, hb), mad_u24(tx.i1, 64u, hb)};
+    const unsigned z0 = mul_u24(tz.i0, (unsigned)f.grid[1]), z1 = mul_u24(tz.i1, (unsigned)f.grid[1]);
+    const unsigned row[4] = {z0 + ty.i0, z0 + ty.i1, z1 + ty.i0, z1 + ty.i1};       // corner c = 4 dz + 2 dy + dx
+    uint4 v[8][2];
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+        const unsigned o = mad_u24(row[c >> 1], pb, xo[c & 1]);
+        v[c][0] = ld16b(f.dense_app, o);
+        v[c][1] = ld16b(f.dense_app, o + 16u);
+    }
+    const float wyz[4] = {tz.w.x * ty.w.x, tz.w.x * ty.w.y, tz.w.y * ty.w.x, tz.w.y * ty.w.y};
+    float w[8];
+#pragma unroll
+    for (int c = 0; c < 8; ++c) w[c] = wyz[c >> 1] * ((c & 1) ? tx.w.y : tx.w.x);
+    auto H = [](unsigned u) { return __builtin_bit_cast(tir_h2, u); };
+    if constexpr (F32) {
+#pragma unroll
+        for (int q = 0; q < 2; ++q)
+#pragma unroll
+            for (int p = 0; p < 4; ++p) {
+                float lo[2], hi[2];
+#pragma unroll
+                for (int g = 0; g < 2; ++g) {                       // the z0 face, the z1 face
+                    const unsigned u0[4] = {v[4 * g][q].x, v[4 * g][q].y, v[4 * g][q].z, v[4 * g][q].w};
+                    tir_h2 e = H(u0[p]);
+                    lo[g] = (float)e.x * w[4 * g]; hi[g] = (float)e.y * w[4 * g];
+#pragma unroll
+                    for (int c = 1; c < 4; ++c) {
+                        const unsigned uc[4] = {v[4 * g + c][q].x, v[4 * g + c][q].y, v[4 * g + c][q].z, v[4 * g + c][q].w};
+                        e = H(uc[p]);
+                        lo[g] = fmaf((float)e.x, w[4 * g + c], lo[g]); hi[g] = fmaf((float)e.y, w[4 * g + c], hi[g]);
+                    }
+                }
+                fo[8 * q + 2 * p] = lo[0] + lo[1];
+                fo[8 * q + 2 * p + 1] = hi[0] + hi[1];
+            }
+    } else {
+        tir_h2 hw[8];
+#pragma unroll
+        for (int c = 0; c < 8; ++c) hw[c] = tir_h2{(_Float16)w[c], (_Float16)w[c]};
+#pragma unroll
+        for (int q = 0; q < 2; ++q)
+#pragma unroll
+            for (int p = 0; p < 4; ++p) {
+                tir_h2 s[2];
+#pragma unroll
+                for (int g = 0; g < 2; ++g) {
+                    const unsigned u0[4] = {v[4 * g][q].x, v[4 * g][q].y, v[4 * g][q].z, v[4 * g][q].w};
+                    s[g] = H(u0[p]) * hw[4 * g];
+#pragma unroll
+                    for (int c = 1; c < 4; ++c) {
+                        const unsigned uc[4] = {v[4 * g + c][q].x, v[4 * g + c][q].y, v[4 * g + c][q].z, v[4 * g + c][q].w};
+                        s[g] = __builtin_elementwise_fma(H(uc[p]), hw[4 * g + c], s[g]);
+                    }
+                }
+                const tir_h2 r = s[0] + s[1];
+                fo[8 * q + 2 * p] = (float)r.x;
+                fo[8 * q + 2 * p + 1] = (float)r.y;
+            }
+    }
+}
+
+// which arithmetic the dense appearance lookup ships with (the decision rule and what each form measured)
+#ifndef TIR_DENSE_APP_F32
+#define TIR_DENSE_APP_F32 0
+#endif
+constexpr bool kDenseAppF32 = TIR_DENSE_APP_F32 != 0;
+// the volume's shape: 48 components per plane, 27 features, of which lane half 0 owns the first 14 (FUS_NF0 of tir_mlp.hip)
+constexpr int DA_CA = 48, DA_F = 27, DA_NF0 = 14;
+
 // 32-bit LDS addresses (device code only: the host pass of hipcc parses these bodies too and has no address space 3)
 __device__ __forceinline__ unsigned lds_addr(const float* p) {
 #if defined(__HIP_DEVICE_COMPILE__)

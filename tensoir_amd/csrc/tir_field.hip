@@ -1371,11 +1371,40 @@ extern "C" int tir_pack_half_checked(const float* const* srcs, void* const* dsts
     return pack_half_launch(srcs, dsts, counts, n_tables, absmax, stream);
 }
 
+// tir_vm_app_fwd_h16 through the dense appearance volume: the fused dense kernel's lookup (tir::dense_app_lookup, the same
+// lane roles: record = lane & 31, half = lane >> 5), the clamped features written as fp32 rows; columns >= 27 are 0.
+__global__ void __launch_bounds__(256)
+k_vm_app_dense(TirField f, const float* __restrict__ xyz, float* __restrict__ rad_feat, int out_stride, int64_t n,
+               const int32_t* __restrict__ n_dev) {
+    if (n_dev) n = min(n, (int64_t)max(*n_dev, 0));
+    const int lane = threadIdx.x & 63, sl = lane & 31, h = lane >> 5;
+    const int64_t n_pass = (n + 31) / 32;
+    for (int64_t pass = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); pass < n_pass; pass += (int64_t)gridDim.x * 4) {
+        const int64_t s = pass * 32 + sl, sc = s < n ? s : n - 1;
+        float fo[16];
+        dense_app_lookup<kDenseAppF32>(f, xyz[3 * sc], xyz[3 * sc + 1], xyz[3 * sc + 2], h, fo);
+        if (s >= n) continue;
+        float* o = rad_feat + s * out_stride + (h ? DA_NF0 : 0);
+        const int cols = h ? out_stride - DA_NF0 : DA_NF0;                  // half 1 also writes the zero columns up to the stride
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+            if (r < cols) o[r] = (h && r >= DA_F - DA_NF0) ? 0.0f : __builtin_amdgcn_fmed3f(fo[r], -65504.0f, 65504.0f);
+        for (int r = 16; r < cols; ++r) o[r] = 0.0f;
+    }
+}
+
 extern "C" int tir_vm_app_fwd_h16(const TirField* f, const TirFieldHalf* fh, const float* xyz, const int32_t* light_idx,
                                   const int32_t* idx_map, float* rad_feat, int32_t out_stride, int32_t idx_div, int64_t n,
                                   const int32_t* n_dev, void* stream) {
     if (!f || !fh) return TIR_ERR_ARG;
     if (int rc = tir_check_app_field(f, TirAppNeeds().fp16_tables(fh).aligned().element_index32().width(48), out_stride)) return rc;
+    const int dense = tir_dense_app_route(f);
+    if (dense < 0) return dense;
+    if (dense)        // one light: no light index is looked up; the volume's slots behind feature 26 are 0
+        return tir_with_rows(n, {xyz, rad_feat, light_idx}, {}, [&] {
+            return tir_launch(k_vm_app_dense, 0, dim3(tir_gather_blocks(n, 128, 2048, 0)), dim3(256), 0, tir_stream(stream), *f, xyz,
+                              rad_feat, (int)out_stride, n, n_dev);
+        });
     return tir_with_rows(n, {xyz, rad_feat, light_idx}, {}, [&] {
         const int lt_rows = f->n_lights <= 16 ? f->n_lights : 0;
         const size_t lds = (size_t)(3 * 3 * 2 * 32) * 16 + (size_t)(lt_rows + 1) * 144 * sizeof(float) + (size_t)4 * 32 * TIR_XH * 2;

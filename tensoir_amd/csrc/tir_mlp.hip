@@ -909,6 +909,102 @@ __device__ __forceinline__ void fus_issue(FusChunk& c, const void* __restrict__ 
     c.e = ld_u4b(ln, g.l0 + o);  c.g = ld_u4b(ln, g.l1 + o);
 }
 
+// The decoder phase of the fused kernels for lane (record sl = lane & 31, half h = lane >> 5) -- shared by k_indirect_fused (features
+// from the fp16 shadow taps) and k_indirect_fused_dense (features from the dense volume): facc = this half's 16 feature slots,
+// unclamped; ai = the record's aux-table row; sd = the record (nothing is stored for sd >= n: the clamped lanes of the last tile).
+// `lds` = the kernel's LDS with the fp16 decoder image at its start, w0hi / w1hi = this lane's tile addresses in it.
+template <bool PACK>
+__device__ __forceinline__ void fus_decode(const float* lds, unsigned w0hi, unsigned w1hi, const f32x16& facc, const float* __restrict__ table,
+                                           unsigned ai, int lane, int h, int64_t sd, int64_t n, float* __restrict__ out, int out_dim, int act) {
+    // The decoder phase runs at a raised wave priority: the waves of a SIMD tend to run the same phase at the same time, and with
+    // equal priorities the arbiter lets the gather-phase VALU work of one wave delay the matrix instructions of another whose
+    // accumulators everything downstream waits for.  Measured: alone on the stream 0.377-0.384 -> 0.370-0.371 ms (priority 3;
+    // 1: nothing), in the bench step 0.941 -> 0.936 ms (three alternating runs each).  The hp kernel gains 3 % alone on the stream
+    // with priority 1 and nothing in the step (two batches in flight): left without.
+    __builtin_amdgcn_s_setprio(FUS_DECODER_PRIO);
+    // ---------------- decoder phase: facc[4 i + r] = this half's feature slot 4 i + r  (half 0: features 0..13, half 1: 14..26)
+    float fo[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) fo[r] = __builtin_amdgcn_fmed3f(facc[r], -65504.0f, 65504.0f);
+    f32x16 acc[4];
+    if (PACK) {                          // the layer-1 accumulators' start values: aux-table row of the record's direction
+        const float* tp = table + (size_t)ai * HID + 4 * h;
+#pragma unroll
+        for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const float4 t4 = *reinterpret_cast<const float4*>(tp + mt * 32 + 8 * i);
+                acc[mt][4 * i] = t4.x; acc[mt][4 * i + 1] = t4.y; acc[mt][4 * i + 2] = t4.z; acc[mt][4 * i + 3] = t4.w;
+            }
+    }
+    fus_layer1<0>(w0hi, fo, acc);
+    f32x16 acc2[4];
+    if constexpr (PACK) {
+        unsigned hp[32];
+#pragma unroll
+        for (int q = 0; q < 64; q += 2) {
+            // (the builtin, not the inline-asm relu_sat16: these reads come straight behind layer 1's last MFMAs, and the hazard
+            //  recogniser does not insert the MFMA -> VALU wait states for inline asm -- that read stale accumulators: 1e-3 errors)
+            // Convert first, then ReLU and saturation on the PACKED fp16 pipe (v_pk_max_f16 / v_pk_min_f16): the same values for every
+            // finite input (rounding is monotonic, rnd(0) = 0, an overflow becomes inf and is cut to 65504), 32 fp32-class
+            // instructions instead of 96 -- and packed fp16 instructions run under other waves' matrix instructions, fp32 ones
+            // do not (profiles/r06_mfma_valu_overlap.txt).
+            const f32x2_t v2 = {acc[q >> 4][q & 15], acc[(q + 1) >> 4][(q + 1) & 15]};
+            fus_f16x2 hv = __builtin_convertvector(v2, fus_f16x2);
+            hv = __builtin_elementwise_min(__builtin_elementwise_max(hv, fus_f16x2{(_Float16)0.0f, (_Float16)0.0f}),
+                                           fus_f16x2{(_Float16)65504.0f, (_Float16)65504.0f});
+            hp[q >> 1] = __builtin_bit_cast(unsigned, hv);
+        }
+#pragma unroll
+        for (int mt = 0; mt < 4; ++mt) {
+            const float* bp = lds + BH_B1 + (h * 4 + mt) * 16;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc2[mt][r] = bp[r];
+        }
+        fus_layer2p<0>(w1hi, hp, acc2);
+    } else {
+#pragma unroll
+        for (int mt = 0; mt < 4; ++mt) {
+            const float* bp = lds + BH_B1 + (h * 4 + mt) * 16;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc2[mt][r] = bp[r];
+        }
+        layer2_interleaved<1, 0, true>(w1hi, w1hi, acc, acc2);
+    }
+    f32x4 o4[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) o4[c] = f32x4{0.f, 0.f, 0.f, 0.f};
+    {
+        const float* wp = lds + BH_W2 + (h * 4 + (lane & 3)) * W2A_STRIDE;
+#pragma unroll
+        for (int g = 0; g < 16; ++g) {
+            const float4 w = *reinterpret_cast<const float4*>(wp + 4 * g);
+            const float wv[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int q = 4 * g + e;
+                const float x = acc2[q >> 4][q & 15];
+                o4[e] = __builtin_amdgcn_mfma_f32_4x4x1f32(wv[e], x + __builtin_fabsf(x), o4[e], 0, 0, 0);
+            }
+        }
+    }
+    float o0 = (o4[0][0] + o4[1][0]) + (o4[2][0] + o4[3][0]);
+    float o1 = (o4[0][1] + o4[1][1]) + (o4[2][1] + o4[3][1]);
+    float o2 = (o4[0][2] + o4[1][2]) + (o4[2][2] + o4[3][2]);
+    float o3 = (o4[0][3] + o4[1][3]) + (o4[2][3] + o4[3][3]);
+    o0 += __shfl_xor(o0, 32, 64); o1 += __shfl_xor(o1, 32, 64);
+    o2 += __shfl_xor(o2, 32, 64); o3 += __shfl_xor(o3, 32, 64);
+    __builtin_amdgcn_s_setprio(0);
+    if (h == 0 && sd < n) {
+        const float* b2 = lds + BH_B2;
+        float* op = out + sd * out_dim;
+        op[0] = act_out(o0 + b2[0], act);
+        if (out_dim > 1) op[1] = act_out(o1 + b2[1], act);
+        if (out_dim > 2) op[2] = act_out(o2 + b2[2], act);
+        if (out_dim > 3) op[3] = act_out(o3 + b2[3], act);
+    }
+}
+
 // NW waves per workgroup (tile = 32 NW records).  PACK: the three-waves-per-SIMD form -- the aux-table row is loaded at the START of
 // the decoder phase (no prefetch registers during the gather; the other two waves of the SIMD cover the latency) and layer 2 runs on
 // packed activations (fus_layer2p).
@@ -976,17 +1072,6 @@ k_indirect_fused(TirField f, TirFieldHalf fh, const float* __restrict__ packed, 
         f32x16 facc;
 #pragma unroll
         for (int r = 0; r < 16; ++r) facc[r] = 0.0f;
-        f32x16 acc[4];
-        auto load_table = [&]() {       // the layer-1 accumulators' start values: aux-table row of the record's direction
-            const float* tp = table + (size_t)ai * HID + 4 * h;
-#pragma unroll
-            for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const float4 t4 = *reinterpret_cast<const float4*>(tp + mt * 32 + 8 * i);
-                    acc[mt][4 * i] = t4.x; acc[mt][4 * i + 1] = t4.y; acc[mt][4 * i + 2] = t4.z; acc[mt][4 * i + 3] = t4.w;
-                }
-        };
         {
             // Nine 16-channel chunks (3 VM groups x 3), software-pipelined THREE deep (round 6): the six 16-byte taps of chunks
             // i + 1 .. i + 3 are in flight while chunk i is interpolated on the packed fp16 pipe and contracted -- as many loads
@@ -1026,83 +1111,45 @@ k_indirect_fused(TirField f, TirFieldHalf fh, const float* __restrict__ packed, 
                 __builtin_amdgcn_wave_barrier();
             }
         }
-        // The decoder phase runs at a raised wave priority: the waves of a SIMD tend to run the same phase at the same time, and with
-        // equal priorities the arbiter lets the gather-phase VALU work of one wave delay the matrix instructions of another whose
-        // accumulators everything downstream waits for.  Measured: alone on the stream 0.377-0.384 -> 0.370-0.371 ms (priority 3;
-        // 1: nothing), in the bench step 0.941 -> 0.936 ms (three alternating runs each).  The hp kernel gains 3 % alone on the stream
-        // with priority 1 and nothing in the step (two batches in flight): left without.
-        __builtin_amdgcn_s_setprio(FUS_DECODER_PRIO);
-        // ---------------- decoder phase: facc[4 i + r] = this half's feature slot 4 i + r  (half 0: features 0..13, half 1: 14..26)
-        float fo[16];
+        fus_decode<PACK>(lds, w0hi, w1hi, facc, table, ai, lane, h, sd, n, out, out_dim, act);
+    }
+}
+
+// k_indirect_fused on a field with ONE light and a dense appearance-feature volume (TirField::dense_app): the feature phase is
+// the trilinear lookup of the volume (tir::dense_app_lookup) by the lane that feeds the slots into layer 1 -- record = lane & 31,
+// half = lane >> 5 -- so there are no shadow taps, no product tile, no wave barriers and no basis_mat contraction; the decoder
+// phase is fus_decode as above.  No light index is read (one light: every index clamps to row 0).  LDS: the fp16 decoder image.
+template <int NW>
+__global__ void __launch_bounds__(NW * 64)
+k_indirect_fused_dense(TirField f, const float* __restrict__ packed, const float* __restrict__ xyz, const int32_t* __restrict__ rec_map,
+                       int aux_mod, const float* __restrict__ table, float* __restrict__ out, int64_t n,
+                       const int32_t* __restrict__ n_dev, int out_dim, int act) {
+    using namespace tir;
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    for (int i = threadIdx.x * 4; i < FH_FLOATS; i += NW * 64 * 4)
+        *reinterpret_cast<float4*>(lds + i) = *reinterpret_cast<const float4*>(packed + OFF_FF + i);
+    __syncthreads();
+    if (n_dev) n = min(n, (int64_t)max(*n_dev, 0));
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int sl = lane & 31, h = lane >> 5;
+    const unsigned lds0 = (unsigned)(size_t)lds;
+    const unsigned lane_off = lds0 + BH_FLOATS * 4 + (unsigned)(h * 128 + sl) * 16;
+    const unsigned w0hi = opaque(lane_off);
+    const unsigned w1hi = opaque(lane_off + BW0A_ELEMS * 2);
+    constexpr int TILE = NW * 32;
+    const int64_t n_tiles = (n + TILE - 1) / TILE;
+    const UDiv by_mod = make_udiv(aux_mod);
+    for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        // this lane's record (the last partial tile is clamped to record n - 1) and its aux-table row
+        const int64_t sd = tile * TILE + wave * 32 + sl, sdc = sd < n ? sd : n - 1;
+        unsigned ai = rec_map ? (unsigned)rec_map[sdc] : (unsigned)sdc;
+        if (aux_mod > 0) udiv(ai, by_mod, ai);
+        float fr[16];
+        dense_app_lookup<kDenseAppF32>(f, xyz[3 * sdc], xyz[3 * sdc + 1], xyz[3 * sdc + 2], h, fr);
+        f32x16 facc;
 #pragma unroll
-        for (int r = 0; r < 16; ++r) fo[r] = __builtin_amdgcn_fmed3f(facc[r], -65504.0f, 65504.0f);
-        if (PACK) load_table();
-        fus_layer1<0>(w0hi, fo, acc);
-        f32x16 acc2[4];
-        if constexpr (PACK) {
-            unsigned hp[32];
-#pragma unroll
-            for (int q = 0; q < 64; q += 2) {
-                // (the builtin, not the inline-asm relu_sat16: these reads come straight behind layer 1's last MFMAs, and the hazard
-                //  recogniser does not insert the MFMA -> VALU wait states for inline asm -- that read stale accumulators: 1e-3 errors)
-                // Convert first, then ReLU and saturation on the PACKED fp16 pipe (v_pk_max_f16 / v_pk_min_f16): the same values for every
-                // finite input (rounding is monotonic, rnd(0) = 0, an overflow becomes inf and is cut to 65504), 32 fp32-class
-                // instructions instead of 96 -- and packed fp16 instructions run under other waves' matrix instructions, fp32 ones
-                // do not (profiles/r06_mfma_valu_overlap.txt).
-                const f32x2_t v2 = {acc[q >> 4][q & 15], acc[(q + 1) >> 4][(q + 1) & 15]};
-                fus_f16x2 hv = __builtin_convertvector(v2, fus_f16x2);
-                hv = __builtin_elementwise_min(__builtin_elementwise_max(hv, fus_f16x2{(_Float16)0.0f, (_Float16)0.0f}),
-                                               fus_f16x2{(_Float16)65504.0f, (_Float16)65504.0f});
-                hp[q >> 1] = __builtin_bit_cast(unsigned, hv);
-            }
-#pragma unroll
-            for (int mt = 0; mt < 4; ++mt) {
-                const float* bp = lds + BH_B1 + (h * 4 + mt) * 16;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc2[mt][r] = bp[r];
-            }
-            fus_layer2p<0>(w1hi, hp, acc2);
-        } else {
-#pragma unroll
-            for (int mt = 0; mt < 4; ++mt) {
-                const float* bp = lds + BH_B1 + (h * 4 + mt) * 16;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc2[mt][r] = bp[r];
-            }
-            layer2_interleaved<1, 0, true>(w1hi, w1hi, acc, acc2);
-        }
-        f32x4 o4[4];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) o4[c] = f32x4{0.f, 0.f, 0.f, 0.f};
-        {
-            const float* wp = lds + BH_W2 + (h * 4 + (lane & 3)) * W2A_STRIDE;
-#pragma unroll
-            for (int g = 0; g < 16; ++g) {
-                const float4 w = *reinterpret_cast<const float4*>(wp + 4 * g);
-                const float wv[4] = {w.x, w.y, w.z, w.w};
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const int q = 4 * g + e;
-                    const float x = acc2[q >> 4][q & 15];
-                    o4[e] = __builtin_amdgcn_mfma_f32_4x4x1f32(wv[e], x + __builtin_fabsf(x), o4[e], 0, 0, 0);
-                }
-            }
-        }
-        float o0 = (o4[0][0] + o4[1][0]) + (o4[2][0] + o4[3][0]);
-        float o1 = (o4[0][1] + o4[1][1]) + (o4[2][1] + o4[3][1]);
-        float o2 = (o4[0][2] + o4[1][2]) + (o4[2][2] + o4[3][2]);
-        float o3 = (o4[0][3] + o4[1][3]) + (o4[2][3] + o4[3][3]);
-        o0 += __shfl_xor(o0, 32, 64); o1 += __shfl_xor(o1, 32, 64);
-        o2 += __shfl_xor(o2, 32, 64); o3 += __shfl_xor(o3, 32, 64);
-        __builtin_amdgcn_s_setprio(0);
-        if (h == 0 && sd < n) {
-            const float* b2 = lds + BH_B2;
-            float* op = out + sd * out_dim;
-            op[0] = act_out(o0 + b2[0], act);
-            if (out_dim > 1) op[1] = act_out(o1 + b2[1], act);
-            if (out_dim > 2) op[2] = act_out(o2 + b2[2], act);
-            if (out_dim > 3) op[3] = act_out(o3 + b2[3], act);
-        }
+        for (int r = 0; r < 16; ++r) facc[r] = fr[r];
+        fus_decode<true>(lds, w0hi, w1hi, facc, table, ai, lane, h, sd, n, out, out_dim, act);
     }
 }
 
@@ -2659,10 +2706,15 @@ extern "C" int tir_indirect_fused_fwd(const TirField* f, const TirFieldHalf* fh,
     if (!f || !fh) return TIR_ERR_ARG;
     if (int rc = check_mlp(m)) return rc;
     if (int rc = tir_check_app_field(f, TirAppNeeds().fp16_tables(fh).aligned().element_index32().width(48).app_dim_is(F).no_feature_rows(), 0)) return rc;
+    const int dense = tir_dense_app_route(f);      // a dense appearance volume on a one-light field: the lookup kernel
+    if (dense < 0) return dense;
     return tir_with_rows(n, {xyz, light_idx, table, out}, {table}, [&] {
         if (!fused_index_ok(n, idx_div, aux_mod)) return (int)TIR_ERR_UNSUPPORTED;
         const int lt_rows = f->n_lights <= 16 ? f->n_lights : 0;
         constexpr int NW = 12; constexpr bool PACK = true;
+        if (dense)
+            return tir_launch(k_indirect_fused_dense<NW>, FH_BYTES, dim3(decoder_grid(n, NW * 32, m->tune_grid)), dim3(NW * 64), FH_BYTES,
+                              tir_stream(stream), *f, m->packed, xyz, rec_map, aux_mod, table, out, n, n_dev, m->out_dim, m->act);
         const size_t lds = (size_t)FH_BYTES + FUS_WH_BYTES + (size_t)(lt_rows + 1) * 144 * sizeof(float) + (size_t)NW * 32 * FUS_XH * 2;
         return tir_launch(k_indirect_fused<NW, PACK>, (int)lds, dim3(decoder_grid(n, NW * 32, m->tune_grid)), dim3(NW * 64), lds,
                           tir_stream(stream), *f, *fh, m->packed, xyz, light_idx, rec_map, idx_div, aux_mod, table, out, n, n_dev,

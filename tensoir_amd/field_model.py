@@ -673,7 +673,7 @@ class TensorVMSplit(nn.Module):
         key walk over the parameters is not repeated)."""
         return self._field_cache.get("half_range") if self.packed_field_half(_fresh) is not None else None
 
-    def packed_field_dense(self, _fresh=False):
+    def packed_field_dense(self, _fresh=False, app=False):
         """packed_field() with the dense density-feature volume attached (TirField.dense_sigma) -- the descriptor of the
         INFERENCE secondary marches (relight._secondary outside a training pass, the relighting visibility marches, the bake);
         training passes keep packed_field(): the field changes every step there and a rebuild costs about what it saves.
@@ -681,7 +681,10 @@ class TensorVMSplit(nn.Module):
         optimizer step, upsample, shrink or load drops it.  Switched off (TENSOIR_DENSE_SIGMA=0), above the size cap
         (TENSOIR_DENSE_SIGMA_MAX_MB), beyond the kernel's 32-bit addressing or when the allocation fails there is no volume
         and this IS packed_field(): the choice depends on the model and the switches only, never on the call history
-        (dense_sigma_state() reports it).  _fresh: the caller has just called packed_field()."""
+        (dense_sigma_state() reports it).  _fresh: the caller has just called packed_field().
+        app=True: the descriptor of a pass that decodes indirect-light records -- the same one with the dense appearance-feature
+        volume attached as well (TirField.dense_app: 64 (X+1) Y Z bytes, one-light fields of 48 components; TENSOIR_DENSE_APP,
+        TENSOIR_DENSE_APP_MAX_MB; dense_app_state() reports it).  Marches read neither more nor less through it."""
         if not _fresh:
             self.packed_field()
         keep = self._field_cache
@@ -693,7 +696,61 @@ class TensorVMSplit(nn.Module):
             ent = keep["dense"] = self._build_dense(keep, sel)
         if ops.CAPTURE_KEEPALIVE is not None and ent["vol"] is not None:
             ops.CAPTURE_KEEPALIVE.append(ent["vol"])        # a captured march bakes the volume's address
-        return ent["desc"]
+        if not app:
+            return ent["desc"]
+        # ... and the dense appearance-feature volume (TirField.dense_app) for the passes that decode indirect-light records:
+        # the f16 tier's gather reads it instead of the fp16 shadow taps.  Same rules -- one launch on first use, cached under
+        # the packed field's key (and the switches), refused inside a capture, kept alive for a captured launch -- and it
+        # rides on the descriptor of the density volume: without that one (switched off, above ITS cap) there is none either,
+        # and packed_field_dense() stays packed_field().
+        asel = (ops.TUNE["dense_app"], ops.TUNE["dense_app_max_mb"])
+        aent = ent.get("app")
+        if aent is None or aent["sel"] != asel:
+            if torch.cuda.is_current_stream_capturing():
+                raise TensoirHipError("graph capture needs the dense appearance volume of the current field (run the pass eagerly first)")
+            aent = ent["app"] = self._build_dense_app(keep, ent, asel)
+        if ops.CAPTURE_KEEPALIVE is not None and aent["vol"] is not None:
+            ops.CAPTURE_KEEPALIVE.append(aent["vol"])
+        return aent["desc"]
+
+    @staticmethod
+    def _build_dense_app(keep, ent, sel):
+        f = ent["desc"]
+        nbytes = ops.dense_app_bytes(f)
+        X, Y, Z = [int(g) for g in f.grid]
+        aent = {"sel": sel, "desc": f, "vol": None, "mb": nbytes / 2 ** 20, "why": None}
+        if not sel[0]:
+            aent["why"] = "switched off"
+        elif ent["vol"] is None:
+            aent["why"] = "no dense density volume"
+        elif int(f.n_lights) != 1:
+            aent["why"] = "several lights"
+        elif int(f.n_acomp) != 48 or int(f.app_dim) != 27:
+            aent["why"] = "not a 48-component, 27-feature field"
+        elif nbytes > sel[1] * 2 ** 20:
+            aent["why"] = "above the size cap"
+        elif Y * Z >= 1 << 24 or 64 * (X + 1) >= 1 << 24 or nbytes >= 1 << 32:
+            aent["why"] = "beyond 32-bit addressing"
+        else:
+            try:
+                vol, pitch = ops.dense_app_build(f, keep["ap0"].device)
+            except torch.cuda.OutOfMemoryError:
+                aent["why"] = "allocation failed"
+                return aent
+            g = TirField.from_buffer_copy(f)
+            g.dense_app, g.dense_app_pitch = vol.data_ptr(), pitch
+            aent["desc"], aent["vol"] = g, vol
+        return aent
+
+    def dense_app_state(self, training=False):
+        """Whether the indirect-light records of this model's inference passes (f16 tier) read the dense appearance volume:
+        {"on": bool, "why": reason when off, "mb": its size} (builds the volume if the current field has none yet).  A training
+        pass never does: it keeps packed_field()."""
+        if training:
+            return {"on": False, "why": "training pass", "mb": ops.dense_app_bytes(self.packed_field()) / 2 ** 20}
+        self.packed_field_dense(app=True)
+        aent = self._field_cache["dense"]["app"]
+        return {"on": aent["vol"] is not None, "why": aent["why"], "mb": aent["mb"]}
 
     @staticmethod
     def _build_dense(keep, sel):

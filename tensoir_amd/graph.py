@@ -106,7 +106,9 @@ class GraphedRenderer:
         lights = m.light_parameters()
         return (m._field_key, tuple((t.data_ptr(), t._version) for t in lights), tuple(d._key for d in decs),
                 float(m.march_t_stop), ops.MLP_IMPL, ops.app_contraction(), ops.secondary_mlp_impl(), ops.secondary_app_impl(), ops.fused_indirect(),
-                ops.INDIRECT_GUARD and indirect.verdict(m))
+                ops.INDIRECT_GUARD and indirect.verdict(m),
+                # the dense volumes a captured launch reads (their switches decide which kernels the graph holds)
+                ops.TUNE["dense_sigma"], ops.TUNE["dense_sigma_max_mb"], ops.TUNE["dense_app"], ops.TUNE["dense_app_max_mb"])
 
     def _stale(self):
         return self.graph is not None and self._key() != self._model_key

@@ -32,8 +32,14 @@ TIMING = None
 #   TIR_PAIR_ORDER=m      point-major secondary pair list (default direction-major)   -> tir_shade_setup_compact(pair_order = 2)
 #   TENSOIR_DENSE_SIGMA=0 inference secondary marches without the dense density volume -> TirField.dense_sigma = NULL
 #   TENSOIR_DENSE_SIGMA_MAX_MB=n   largest dense density volume that is built (default 1024; 300^3 needs 108 MB, 400^3 257 MB)
-# (the dense volume is the one option that is not bit-neutral: the march's density feature differs in its last fp32 bits)
+#   TENSOIR_DENSE_APP=0   inference indirect-light records without the dense appearance volume -> TirField.dense_app = NULL
+#   TENSOIR_DENSE_APP_MAX_MB=n     largest dense appearance volume that is built (default 4096; 300^3 needs 1.73 GB; 4 GiB is
+#                                  the kernels' limit)
+# (the dense volumes are the options that are not bit-neutral: the march's density feature differs in its last fp32 bits, the
+#  f16 tier's appearance features by fp16 roundings -- rgb_with_brdf_map within the precision policy's own limit)
 TUNE = {
+    "dense_app": 0 if os.environ.get("TENSOIR_DENSE_APP", "1") == "0" else 1,
+    "dense_app_max_mb": max(0, int(os.environ.get("TENSOIR_DENSE_APP_MAX_MB", "4096") or 0)),
     "lds_lines": 2 if os.environ.get("TENSOIR_LDS_LINES", "1") == "0" else 0,
     "xcd_order": 1 if os.environ.get("TIR_XCD", "0") == "1" else 0,
     "dense_sigma": 0 if os.environ.get("TENSOIR_DENSE_SIGMA", "1") == "0" else 1,
@@ -375,6 +381,22 @@ def dense_sigma_build(field: TirField, device):
     pitch = X + 1
     vol = torch.empty((Z, Y, pitch), dtype=torch.float32, device=device)
     _call("tir_dense_sigma_build", C.byref(field), _ptr(vol), pitch, _stream())
+    return vol, pitch
+
+
+def dense_app_bytes(field: TirField):
+    """Size of the dense appearance-feature volume of `field`: 64 bytes per corner, rows of grid x + 1 corners."""
+    X, Y, Z = [int(g) for g in field.grid]
+    return 64 * (X + 1) * Y * Z
+
+
+def dense_app_build(field: TirField, device):
+    """The dense appearance-feature volume of a one-light `field` (tir_dense_app_build): fp16 [grid z][grid y][grid x + 1][2][16]
+    and its row pitch in corners."""
+    X, Y, Z = [int(g) for g in field.grid]
+    pitch = X + 1
+    vol = torch.empty((Z, Y, pitch, 2, 16), dtype=torch.float16, device=device)
+    _call("tir_dense_app_build", C.byref(field), _ptr(vol), pitch, _stream())
     return vol, pitch
 
 

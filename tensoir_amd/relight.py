@@ -148,8 +148,9 @@ def _secondary(tensoIR, origins, dirs, n_rays, z, org_map, dir_map, active, ligh
                probe_map=None):
     """Shared driver of compute_transmittance / compute_radiance / render_with_BRDF: march (+ record the w > thres samples) ->
     _decode_pass, repeated until the records fit and the range guard holds, under the record-capacity protocol of capacity.py.
-    An inference pass marches through the dense density volume (packed_field_dense); a training pass keeps the VM kernels."""
-    f = tensoIR.packed_field() if training else tensoIR.packed_field_dense()
+    An inference pass marches through the dense density volume (packed_field_dense) and, where it decodes records, reads their
+    f16-tier appearance features from the dense appearance volume; a training pass keeps the VM kernels."""
+    f = tensoIR.packed_field() if training else tensoIR.packed_field_dense(app=bool(want_indirect))
     if not want_indirect:
         vis, oma, _ = ops.march_secondary(f, origins, dirs, z, n_rays, org_map, dir_map, active,
                                           tensoIR.march_t_stop, False, 0, want_nerfactor, n_dirs)
