@@ -273,8 +273,9 @@ int tir_mlp_fwd_bf16x3(const TirMlp* m, const float* feat, int32_t feat_stride, 
  *      tir_pack_half: fp32 -> fp16 copies (round to nearest even, SATURATING: |x| > 65504 -> +-65504, never inf) of up to
  *      TIR_HALF_MAX_JOBS tables in one launch; srcs / dsts / counts are HOST arrays, tables 16-byte aligned.
  *      tir_pack_half_checked: the same, and absmax[i] (DEVICE floats, zeroed by the caller before the call) receives max |x| of
- *      table i (a NaN anywhere in the table is reported as NaN); dsts[i] == NULL scans table i without writing a copy (light
- *      rows, basis_mat).  RANGE CONTRACT of the fp16 gather below: interpolation and the products (plane * line) * light-row run
+ *      table i (a NaN anywhere in the table is reported as NaN; its fp16 copy is -65504, the saturating clamp orders a NaN below
+ *      every number); dsts[i] == NULL scans table i without writing a copy (light rows, basis_mat).
+ *      RANGE CONTRACT of the fp16 gather below: interpolation and the products (plane * line) * light-row run
  *      on the packed fp16 pipe WITHOUT a saturation test in the hot loop, so the caller must establish
  *      max|plane_i| * max|line_i| * max(1, max|light row|) < 65504 for i = 0..2 and max|basis_mat| < 65504 from these maxima
  *      (bilinear taps are convex combinations, so the bound is rigorous) and use the fp32 gather (tir_vm_app_fwd) otherwise --
@@ -282,7 +283,13 @@ int tir_mlp_fwd_bf16x3(const TirMlp* m, const float* feat, int32_t feat_stride, 
  *      tir_vm_app_fwd_h16 = tir_vm_app_fwd(rad_feat only) for n_acomp == 48 on the fp16 shadow `fh` of f->aplane / f->aline:
  *      half the bytes through the vector L1 (the bound of the fp32 gather), interpolation and light-row product on the packed
  *      fp16 pipe (v_pk_fma_f16: two channels per instruction, rounded after every step), the basis_mat contraction on
- *      v_mfma_f32_32x32x16_f16 (fp32 accumulate).  ~5e-4 relative on a
+ *      v_mfma_f32_32x32x16_f16 (fp32 accumulate).  In full: the light rows and basis_mat are rounded to fp16 in the kernel
+ *      (saturating, like the shadow), the bilinear weights wx * wy (formed in fp32) and the line weights are rounded to fp16, and
+ *      every step of pl = a w00 + b w01 + c w10 + d w11, ln = e l0 + g l1 and (pl * ln) * light rounds to fp16.  The light row
+ *      is light_idx[(idx_map ? idx_map[s] : s) / idx_div] clamped to [0, n_lights - 1].  On a descriptor that carries
+ *      dense_app (one light; no index is read) the features are instead the sum over the 8 cell corners of the volume's fp16
+ *      corner features (accumulated in fp32 from the fp32 parameters, rounded once) times wx wy wz (formed in fp32, rounded to
+ *      fp16), on the packed fp16 pipe: one fp16 rounding per step, clamped to +-65504; columns >= 27 are 0.  ~5e-4 relative on a
  *      feature: NOT parity grade on its own -- the product path uses it only for the secondary-ray records, whose radiance is
  *      averaged over a ray's records and the light directions before it reaches rgb_with_brdf_map.  Other arguments as
  *      tir_vm_app_fwd. */
@@ -296,7 +303,9 @@ int tir_vm_app_fwd_h16(const TirField* f, const TirFieldHalf* fh, const float* x
 /* The two launches above fused (north_star: gathers and decoder "in one pass"): for every record s < min(n, *n_dev) the radiance
  * features of xyz[s] (light row light_idx[rec_map[s] / idx_div]) are gathered from the fp16 shadow, contracted with basis_mat and
  * decoded by `m` (the radiance decoder; view-direction columns from `table` row rec_map[s] % aux_mod, tir_mlp_aux_table) without
- * the feature rows ever reaching HBM.  out [n][m->out_dim].  n_acomp == 48, app_dim == 27.  Same precision class as the pair
+ * the feature rows ever reaching HBM.  The light index is clamped to [0, n_lights - 1] (a field with one light reads none: row 0);
+ * the features are clamped to +-65504 before they enter the decoder; a descriptor with dense_app takes the volume lookup of
+ * tir_vm_app_fwd_h16.  out [n][m->out_dim].  n_acomp == 48, app_dim == 27.  Same precision class as the pair
  * tir_vm_app_fwd_h16 + tir_mlp_fwd_auxtab_f16 (results agree to fp32 summation order). */
 int tir_indirect_fused_fwd(const TirField* f, const TirFieldHalf* fh, const TirMlp* m, const float* xyz,
                            const int32_t* light_idx, const int32_t* rec_map, int32_t idx_div, int32_t aux_mod,
@@ -307,8 +316,17 @@ int tir_indirect_fused_fwd(const TirField* f, const TirFieldHalf* fh, const TirM
  * before round 6 that fallback was tir_vm_app_fwd + tir_mlp_fwd_auxtab_bf16x3 with the feature rows through HBM): fp32 taps from
  * the parameters themselves (no shadow), fp32 interpolation, basis_mat contraction on fp16 hi + lo operands (three products),
  * decoder with fp16 activations and weights as fp16 + fp8 residue (tir_pack_mlp's OFF_F8 image, multiplied on the block-scaled
- * fp8 matrix instruction with the scale 2^-17 into the same fp32 accumulators; layer 3 exact).  n_lights <= 8.  Arguments as tir_indirect_fused_fwd without the shadow.  Deviation from the exact decoder on rgb_with_brdf_map:
- * measured per checkpoint by the policy's self-check (profiles/r06_*). */
+ * fp8 matrix instruction with the scale 2^-17 into the same fp32 accumulators; layer 3 exact).  n_lights <= 8 (more:
+ * TIR_ERR_UNSUPPORTED, nothing is written).  Arguments as tir_indirect_fused_fwd without the shadow.  In full: each product
+ * (plane * line) * light is clamped to +-65504 and split hi = fp16(x), lo = fp16(x - hi), basis_mat the same way, and hi hi + hi lo
+ * + lo hi are summed in fp32; the features are clamped to +-65504.  The residue is e4m3((W - fp16(W)) 2^17) clamped to +-448 (it
+ * saturates from |W| >= 7); the activations it multiplies are e4m3 as well -- the positional-encoding values as they are, the raw
+ * feature clamped to +-448 first, the hidden activations cut at 448 -- so the residue corrects the weights, not the fp16 rounding
+ * of the activations (~5e-4 of a record's output; it averages out, the weight rounding does not).  Range: a lo part below 2^-14 is
+ * an fp16 subnormal and one below 2^-25 is nothing, so with products or basis_mat entries below ~2^-3 the contraction loses bits
+ * step by step, and with products below 2^-14 (or basis_mat entries below ~1e-4) it is that of single fp16 operands: no better
+ * than tir_indirect_fused_fwd there (tests/test_indirect_cpu.py prints the figures).  Deviation from the exact decoder on
+ * rgb_with_brdf_map: measured per checkpoint by the policy's self-check (profiles/r06_*). */
 int tir_indirect_fused_hp_fwd(const TirField* f, const TirMlp* m, const float* xyz, const int32_t* light_idx,
                               const int32_t* rec_map, int32_t idx_div, int32_t aux_mod, const float* table, float* out,
                               int64_t n, const int32_t* n_dev, void* stream);

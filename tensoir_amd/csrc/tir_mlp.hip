@@ -1396,7 +1396,7 @@ k_indirect_fused_hp(TirField f, const float* __restrict__ packed, const float* _
                 lia = light_idx[la]; lib = light_idx[lb];
                 lia = min(max(lia, 0), f.n_lights - 1); lib = min(max(lib, 0), f.n_lights - 1);
             }
-            lrA = LT + lia * (3 * CA);         // (the launcher stages every light row in LDS: n_lights <= 16)
+            lrA = LT + lia * (3 * CA);         // (the launcher stages every light row in LDS: n_lights <= 8)
             lrB = LT + lib * (3 * CA);
         }
         // decoder role: this lane's record and its aux-table row
