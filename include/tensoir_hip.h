@@ -134,8 +134,10 @@ int  tir_device_check(void);
 /* [C,H,W] -> [H,W,C]   (also lines with W=1) */
 int tir_pack_plane(const float* src, float* dst, int32_t C, int32_t H, int32_t W, void* stream);
 /* float volume [D][H][W] -> (D+1)*(H+1)*(W+1) neighbourhood bytes: byte (z0+1,y0+1,x0+1), bit dx+2dy+4dz =
- * voxel (x0+dx,y0+dy,z0+dz) inside the grid and > 0.5.  The trilinear "sample_alpha(...) > 0" test of a
- * point then needs one byte. */
+ * voxel (x0+dx,y0+dy,z0+dz) inside the grid and > 0.5 (0.5 itself is not occupied).  The trilinear
+ * "sample_alpha(...) > 0" test of a point then needs one byte.  Base voxels run from -1 to dim-1 per axis: the
+ * volume is zero outside its grid (grid_sample's zero padding), so the bytes of base -1 and of base dim-1 hold
+ * the one-cell skirt round the mask's box in which a point can still be a hit. */
 int tir_pack_occupancy(const float* vol, uint8_t* nbr, int32_t W, int32_t H, int32_t D, void* stream);
 /* basis_mat.weight [app_dim][n_in] -> [n_in][32] */
 int tir_pack_basis(const float* w, float* dst, int32_t app_dim, int32_t n_in, void* stream);
@@ -154,16 +156,32 @@ int tir_vm_density_fwd(const TirField* f, const float* xyz, float* feat, float* 
                        int64_t n, void* stream);
 
 /* ---- a2: AlphaGridMask.sample_alpha(xyz) > 0 (models/tensorBase_rotated_lights.py:112-119) at
- *      world-space points; hit[n] = 1/0.  Needs f->occ_nbr. */
+ *      world-space points; hit[n] = 1/0.  Needs f->occ_nbr.  The lookup, shared by every kernel that culls by the
+ *      mask: index coordinates i = ((q + 1) / 2) * (dim - 1), q = (p - occ_aabb_min) * occ_inv - 1, each step
+ *      rounded to float32 (the reference's own steps) -- in the MASK's box, which need not be the field's (after
+ *      shrink it is larger).  The point is a hit when one of the 8 voxels round it (base floor(i), zero outside the
+ *      grid) is occupied AND has a non-zero trilinear weight: a coordinate with fraction exactly 0 sees only its
+ *      base voxel on that axis.  Points up to one cell outside the mask's box can therefore be hits (the skirt),
+ *      points further out never are.  A coordinate that is NaN, +-inf or far beyond the box (+-1e30: floor(i) is
+ *      clamped to [-2, dim] before the integer conversion) makes the point a miss. */
 int tir_occupancy_query(const TirField* f, const float* xyz, uint8_t* hit, int64_t n, void* stream);
 
 /* ---- occupancy-grid maintenance (models/tensorBase_rotated_lights.py:737-811, :819-837).
  *      tir_dense_alpha: getDenseAlpha + compute_alpha on a gx*gy*gz lattice spanning the aabb; lin_* are the
  *      caller's linspace(0,1,g) tables (device), alpha [gx][gy][gz] = 1 - exp(-sigma * length), sigma = 0 where the
  *      current mask (f->occ_nbr, may be NULL) culls the point.
- *      tir_alpha_pool: updateAlphaMask's clamp -> transpose -> 3x3x3 max-pool -> threshold; vol [gz][gy][gx] float 0/1,
- *      bbox (optional, 6 ints pre-set to {INT_MAX x3, -1 x3}) receives the index bounding box of the occupied voxels.
- *      tir_filter_rays: filtering_rays; mask[i] = ray i may hit something (bbox_only: slab test only). */
+ *      tir_alpha_pool: updateAlphaMask's clamp -> transpose -> 3x3x3 max-pool -> threshold; vol [gz][gy][gx] float 0/1:
+ *      vol[z][y][x] = 1 when the maximum of min(max(alpha[x'][y'][z'], 0), 1) over the neighbours inside the lattice
+ *      (the window is cut at the borders, nothing wraps) is >= thres, compared in float32.  A NaN alpha counts as 0
+ *      (fmaxf drops it, where max_pool3d would spread it): it passes thres <= 0 only.  bbox (optional, 6 ints pre-set
+ *      by the caller to the sentinels {INT_MAX x3, -1 x3}) receives min x, y, z and max x, y, z of the occupied
+ *      voxels through atomic min / max; when no voxel passes the words keep the sentinels (bbox[3] < 0: empty scene).
+ *      tir_filter_rays: filtering_rays; mask[i] = ray i may hit something.  Slab test of the FIELD's box: a zero
+ *      direction component (+0 or -0) is replaced by +1e-6f, rates (aabb - o) / d by IEEE division, tmin the largest
+ *      of the three smaller rates, tmax the smallest of the larger.  bbox_only: mask = tmax > tmin, strictly (a ray
+ *      through an edge or a corner, tmax == tmin, gives 0, as the reference does).  Otherwise t0 = min(max(tmin,
+ *      near_), far_) and mask = some sample k in [0, n_samples) at o + d * (t0 + step_size * k) is a hit of the
+ *      lookup above (samples are not tested against the box; one wave per ray, 64 samples per pass). */
 int tir_dense_alpha(const TirField* f, const float* lin_x, const float* lin_y, const float* lin_z,
                     int32_t gx, int32_t gy, int32_t gz, float length, float* alpha, void* stream);
 int tir_alpha_pool(const float* alpha, int32_t gx, int32_t gy, int32_t gz, float thres, float* vol,

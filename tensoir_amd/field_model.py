@@ -876,11 +876,11 @@ class TensorVMSplit(nn.Module):
         alpha, lins = ops.dense_alpha(self.packed_field(), gridSize, float(self.stepSize))
         vol, bbox = ops.alpha_pool(alpha, self.alphaMask_thres)
         total_voxels = gridSize[0] * gridSize[1] * gridSize[2]
+        b = bbox.tolist()
+        if b[3] < 0:                                # raised before anything is assigned: the model keeps the mask it had
+            raise TensoirHipError("updateAlphaMask: no voxel passes alphaMask_thres (empty scene)")
         self.alphaMask = AlphaGridMask(self.device, self.aabb, vol)
         self._field_key = None
-        b = bbox.tolist()
-        if b[3] < 0:
-            raise TensoirHipError("updateAlphaMask: no voxel passes alphaMask_thres (empty scene)")
         lo = torch.stack([lins[a][b[a]] for a in range(3)])
         hi = torch.stack([lins[a][b[3 + a]] for a in range(3)])
         xyz_min = self.aabb[0] * (1 - lo) + self.aabb[1] * lo

@@ -24,7 +24,7 @@ COMPOSITE_MARGIN = 1e-5 on the max(a, a_jit, 1e-6) ties, on view . normal, on th
 normal-length clamp; their designed rays sit on thresholds with exact values.
 
 The occupancy mask of the masked scene is built by the oracle (O.update_alpha_mask) on the CPU and travels in the checkpoint, so
-that the CPU file sees the very fixtures the GPU file runs; building a mask on the device is tested elsewhere."""
+that the CPU file sees the very fixtures the GPU file runs; building a mask on the device is tested in tests/test_gpu_occupancy_kernels.py."""
 from types import SimpleNamespace
 
 import numpy as np
