@@ -765,10 +765,15 @@ int tir_density_feat_bwd(const TirField* f, const TirFieldGrad* g, const float* 
 int tir_density_feat_grad_bwd(const TirField* f, const TirFieldGrad* g, const float* xyz, const float* v,
                               float* g_xyz_out, int64_t n, void* stream);
 
-/* Backward of tir_vm_app_fwd.  g_rad / g_int [n][stride] (either may be NULL).  Accumulates into g->aplane,
- * g->aline, g->light_line, g->light_mean; writes y_rad / y_int [n][3*n_acomp] = (plane*line) (.) light row,
+/* Backward of tir_vm_app_fwd.  g_rad / g_int [n][stride] (either may be NULL; the first app_dim columns of a row are read,
+ * the padding never).  The gradient buffers are ADDED to (float atomics: zero them first; a second call doubles them):
+ * g->aplane, g->aline, g->light_line (the rows the samples used) and g->light_mean (the row the intrinsic feature used:
+ * kept apart, the caller composes d light_line = light_line + light_mean / n_lights).  The y buffers are OVERWRITTEN:
+ * y_rad / y_int [n][3*n_acomp] = (plane*line) (.) light row / light_mean,
  * the left operand of d basis_mat = g_feat^T y (tir_gemm_tn).  y_rad (y_int) is REQUIRED whenever g_rad (g_int) is
  * given: the buffer first holds dY = g_feat . basis_mat (an MFMA GEMM) and is then overwritten in place with y.
+ * Sample i uses light row light_idx[idx_map ? idx_map[i] : i], CLAMPED to [0, n_lights - 1] (as tir_vm_app_fwd and
+ * tir_shade_integrate do); idx_map (may be NULL) is read only when g_rad is given.
  * Samples should arrive in (ray, sample-along-ray) order -- tir_compact_primary's order: consecutive samples that
  * share a plane cell are summed in registers before they are scattered. */
 int tir_vm_app_bwd(const TirField* f, const TirFieldGrad* g, const float* xyz,
@@ -1093,7 +1098,8 @@ int tir_irradiance_integrate(const float* rows, const float* dirs, const float* 
  *      upper face (the world direction of +u); when that vector is shorter than 1e-20, the same expression with the coordinate
  *      axis of n's smallest |component| (the first of equals) in place of e_u.  b = cross(n, t); w = +1 always.
  * tir_atlas_corners: the unwelded mesh.  Corner q = 3 f + k: pos / nrm [3F][3] = bit copies of verts / normals [faces[f][k]],
- *   uv [3F][2] (step 2), tan [3F][4] = (t, 1) of step 5 with n = the corner's normal normalised as in step 4 (b = unit vector k).
+ *   uv [3F][2] (step 2), tan [3F][4] = (t, 1) of step 5 with n = the corner's normal normalised as in step 4 (b = unit vector k),
+ *   both steps evaluated in double and rounded once (a vertex normal nearly along the edge makes step 5 cancel).
  * tir_atlas_texels: for the n_cells T T texels in cell-major order (c T T + j T + i): point [N][3], outward [N][3] (step 4),
  *   face [N] = the owner.  One thread per texel; 16-byte stores when point and outward are 16-byte aligned.
  * tir_atlas_pack: the three size x size RGBA8 images, in image order (row-major from the top), from the per-texel results of

@@ -1152,6 +1152,47 @@ __device__ __forceinline__ void atlas_tangent(const AtlasFace& F, bool upper, co
     for (int a = 0; a < 3; ++a) t[a] = t[a] / l;
 }
 
+// The corner's tangent (steps 4 and 5 at the corner, where sum b_k n_k is the vertex normal) in double, rounded once.  On the thin
+// triangles of a simplified mesh the vertex normal can lie almost along the edge: e - n (n . e) then cancels to a small part of
+// |e|, and float32 arithmetic -- the restatement's as well as the kernel's -- is several 1e-6 from the exact unit vector (2e-6 to
+// 4e-6 on simplified trained fields).  The tangent goes into the asset, 3 F values per export: the double form costs nothing.
+__device__ __forceinline__ double atlas_len_d(const double x[3]) { return sqrt(x[0] * x[0] + x[1] * x[1] + x[2] * x[2]); }
+
+__device__ __forceinline__ void atlas_corner_tangent(const AtlasFace& F, int k, bool upper, float t_out[3]) {
+    double s[3], e[3], t[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a)          // sum b_k n_k with b the corner's unit vector (a NaN in another vertex normal still counts)
+        s[a] = (k == 0 ? 1.0 : 0.0) * (double)F.n[0][a] + (k == 1 ? 1.0 : 0.0) * (double)F.n[1][a] + (k == 2 ? 1.0 : 0.0) * (double)F.n[2][a];
+    double l = atlas_len_d(s);
+    if (!(l >= 1e-20)) {
+        double e1[3], e2[3];
+#pragma unroll
+        for (int a = 0; a < 3; ++a) { e1[a] = (double)F.v[1][a] - (double)F.v[0][a]; e2[a] = (double)F.v[2][a] - (double)F.v[0][a]; }
+        s[0] = e1[1] * e2[2] - e1[2] * e2[1];
+        s[1] = e1[2] * e2[0] - e1[0] * e2[2];
+        s[2] = e1[0] * e2[1] - e1[1] * e2[0];
+        l = atlas_len_d(s);
+        if (!(l >= 1e-20)) { s[0] = 0.0; s[1] = 0.0; s[2] = 1.0; l = 1.0; }
+    }
+    const double n[3] = {s[0] / l, s[1] / l, s[2] / l};
+#pragma unroll
+    for (int a = 0; a < 3; ++a) e[a] = upper ? (double)F.v[0][a] - (double)F.v[1][a] : (double)F.v[1][a] - (double)F.v[0][a];
+    double d = n[0] * e[0] + n[1] * e[1] + n[2] * e[2];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) t[a] = e[a] - n[a] * d;
+    l = atlas_len_d(t);
+    if (!(l >= 1e-20)) {
+        const double a0 = fabs(n[0]), a1 = fabs(n[1]), a2 = fabs(n[2]);
+        const int ax = (a0 <= a1 && a0 <= a2) ? 0 : (a1 <= a2 ? 1 : 2);
+        d = ax == 0 ? n[0] : (ax == 1 ? n[1] : n[2]);
+#pragma unroll
+        for (int a = 0; a < 3; ++a) t[a] = (a == ax ? 1.0 : 0.0) - n[a] * d;
+        l = atlas_len_d(t);
+    }
+#pragma unroll
+    for (int a = 0; a < 3; ++a) t_out[a] = (float)(t[a] / l);
+}
+
 __global__ void __launch_bounds__(ATLAS_THREADS)
 k_atlas_corners(const float* __restrict__ verts, const float* __restrict__ normals, const int32_t* __restrict__ faces,
                 AtlasLayout A, float* __restrict__ pos, float* __restrict__ nrm, float* __restrict__ tan, float* __restrict__ uv,
@@ -1169,10 +1210,7 @@ k_atlas_corners(const float* __restrict__ verts, const float* __restrict__ norma
     AtlasFace F;
     float t[3] = {0.f, 0.f, 0.f}, p[3] = {0.f, 0.f, 0.f}, m[3] = {0.f, 0.f, 0.f};
     if (atlas_load_face(verts, normals, faces, f, A.n_verts, F)) {
-        const float b[3] = {k == 0 ? 1.f : 0.f, k == 1 ? 1.f : 0.f, k == 2 ? 1.f : 0.f};
-        float n[3];
-        atlas_normal(F, b, n);
-        atlas_tangent(F, upper, n, t);
+        atlas_corner_tangent(F, k, upper, t);
 #pragma unroll
         for (int a = 0; a < 3; ++a) {
             p[a] = k == 0 ? F.v[0][a] : (k == 1 ? F.v[1][a] : F.v[2][a]);

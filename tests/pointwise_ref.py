@@ -81,8 +81,9 @@ def _axis(x32, size):
 
 
 def _clamped_feature(sc, x32, x64):
-    """compute_densityfeature_with_xyz_grad with the reference's grid_sample: clamped tap indices, unclamped weights."""
-    out = torch.zeros(x64.shape[0], dtype=torch.float64)
+    """compute_densityfeature_with_xyz_grad with the reference's grid_sample: clamped tap indices, unclamped weights.  Evaluated
+    in the type of x64 (float64 for every caller but the float32 yardstick of tests/fieldgrad_reference.py)."""
+    out = torch.zeros(x64.shape[0], dtype=x64.dtype)
     for i in range(3):
         m0, m1 = O.MAT_MODE[i]
         vi = O.VEC_MODE[i]
@@ -95,7 +96,7 @@ def _clamped_feature(sc, x32, x64):
         ix = ((x64[:, m0] + 1) / 2) * (W - 1)
         iy = ((x64[:, m1] + 1) / 2) * (H - 1)
         il = ((x64[:, vi] + 1) / 2) * (R - 1)
-        tx, ty, tl = ix - x0.double(), iy - y0.double(), il - l0.double()
+        tx, ty, tl = ix - x0.to(x64.dtype), iy - y0.to(x64.dtype), il - l0.to(x64.dtype)
         flat = plane.reshape(C, H * W)
         tap = lambda xx, yy: flat[:, yy.clamp(0, H - 1) * W + xx.clamp(0, W - 1)]
         P = (tap(x0, y0) * ((1 - tx) * (1 - ty)) + tap(x0 + 1, y0) * (tx * (1 - ty)) + tap(x0, y0 + 1) * ((1 - tx) * ty)

@@ -218,6 +218,8 @@ def test_export_textured_on_trained_field(trained, tmp_path):
     # uv, tangents and the bilinear footprint against the restatement
     hv, hn, hf = verts.cpu().numpy(), normals.cpu().numpy(), faces.cpu().numpy()
     _, _, rtan, ruv = A.corners(hv, hn, hf, size, cols, T)
+    tan32 = np.abs(A.corners(hv, hn, hf, size, cols, T, np.float32)[2] - rtan).max()
+    print(f"[atlas export] tangent: device {np.abs(file['tan'] - rtan).max():.2e}, float32 restatement on this mesh {tan32:.2e}")
     assert np.array_equal(u32(file["uv"]), u32(ruv)) and np.abs(file["tan"] - rtan).max() <= TAN_TOL
     base = file["images"]["base"].astype(np.float64)
     lo, hi = A.corner_uv_local(T)
