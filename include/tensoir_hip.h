@@ -1049,6 +1049,75 @@ int tir_point_mesh_distance(const float* points, int64_t n, const float* verts, 
                             const int32_t* pairs, int64_t n_pairs, float* dist, int32_t* face, float* closest, int32_t* tested,
                             void* stream);
 
+/* ---- Ray cast against a mesh over the same grid (tensoir_amd/csrc/tir_distance.hip; ops.ray_mesh / mesh_inside, mesh.raycast,
+ *      mesh.distance(signed=True)).  The mesh and grid arguments are those of tir_point_mesh_distance.
+ *   origins [n][3], dirs [n][3] fp32 (a direction need not be unit: t is in units of |d|), trange [n][2] fp32 = {t0, t1} per ray
+ *   (NULL: [0, +inf]; negative values reach behind the origin), bounds [6] fp32 ON THE DEVICE = {low xyz, high xyz} of a box that
+ *   contains every listed face (ops.face_grid's "bounds": the box of the finite vertices, padded by 2^-16 max(max |coordinate|,
+ *   largest extent)).
+ *   t [n] fp32 = the parameter of the nearest accepted hit (+inf on a miss), face [n] int32 = its face (-1 on a miss),
+ *   bary [n][2] fp32 = the weights of corners b and c at that hit (NaN on a miss; NULL skips), count [n] int32 (NULL skips),
+ *   flags [n] int32 (NULL skips), tested [n] int32 = ray-triangle tests made (NULL skips; the one output that depends on the grid).
+ *
+ * Ray-triangle rule.  Everything in fp64 from the fp32 inputs, one rounding per operation, nothing contracted.  With A = a - o,
+ *   B = b - o, C = c - o and
+ *       e(P, Q) = (dx (Py Qz - Pz Qy) + dy (Pz Qx - Px Qz)) + dz (Px Qy - Py Qx),     u = e(B, C), v = e(C, A), w = e(A, B):
+ *   the LINE meets the face iff u, v, w are all >= 0 or all <= 0, and not all zero.  n = (b - a) x (c - a), den = (dx nx + dy ny)
+ *   + dz nz; den == 0 is a miss.  t = ((Ax nx + Ay ny) + Az nz) / den (IEEE division); the hit is ACCEPTED iff t0 <= t <= t1.
+ *   bary = (v, w) / ((u + v) + w).  Nearest: the smaller fp64 t, an equal t goes to the smaller face index.  e(Q, P) == -e(P, Q)
+ *   bit for bit, so the two faces of a shared edge see a ray on opposite sides of it: on a closed, consistently oriented mesh a
+ *   ray with no zero edge value crosses the surface watertight, and the parity of its hits tells inside from outside.
+ *   Only the faces a grid lists are met (4.15 b: a face without area or with a non-finite corner is listed nowhere).
+ *
+ * Modes and what they report.
+ *   TIR_RAY_CLOSEST  t, face, bary of the nearest hit; count = 1 on a hit, 0 on a miss; flag bit 0 = THAT hit has an edge value
+ *                    equal to zero.  The walk may stop early.
+ *   TIR_RAY_COUNT    t, face, bary as above; count = the exact number of accepted hits; flag bit 0 = SOME accepted hit has an edge
+ *                    value equal to zero (the ray passes exactly through an edge or a vertex, which count may then have counted
+ *                    twice, or not at all).  No early stop.
+ *   TIR_RAY_ANY      count = 0 or 1 only, flags reports bit 1 only; t, face and bary must be NULL (which face is met first depends
+ *                    on the grid).  Stops at the first accepted hit.
+ *   Flag bit 1, TIR_RAY_FLAG_INVALID: a non-finite origin or direction, d == 0, a NaN in trange or t0 > t1.  Then t = NaN,
+ *   face = -1, bary = NaN, count = 0, tested = 0.
+ *
+ * Traversal (conservative; every loop runs on an integer counter whose bound is known before it starts, so no NaN, infinity or
+ *   zero direction component keeps a lane running).  Per axis the slack is s = TIR_DISTANCE_SLACK * cell + TIR_RAY_COORD_SLACK *
+ *   max |bounds| of that axis: the first term covers the rounding of the cell function (4.15 c), the second the rounding of a
+ *   hit point to fp32 (2^-24 of a coordinate) sixteen times over.
+ *   1. [T0, T1] = [t0, t1] clipped to `bounds` (fp64 slab test; an axis with d == 0 and the origin outside its slab: a miss).
+ *      Clipping removes no hit, because no listed face leaves the box.
+ *   2. The major axis m is the one of the largest |d| (the lower axis wins a tie).  Its slabs of cells are walked in the travel
+ *      direction from cell(x_in -/+ s_m) to cell(x_out +/- s_m), x_in / x_out the major coordinates at T0 / T1.
+ *   3. Slab k covers the coordinates [origin + k cell - s_m, origin + (k + 1) cell + s_m], open-ended for the first and the last
+ *      cell of the axis; its t interval is that of those two planes, cut to [T0 - w, T1 + w], w = max_axis s / |d_m|.
+ *   4. The two other coordinates are evaluated at both ends of the interval; the rectangle of cells from cell(min - s) to
+ *      cell(max + s) per axis is visited, every face listed in a cell is tested (listed faces and their indices are checked again).
+ *      Slabs differ in their major index: no cell is visited twice.
+ *   5. TIR_RAY_CLOSEST stops before a slab only when the best t lies STRICTLY below that slab's widened entry.
+ *   Counting each hit once (TIR_RAY_COUNT): a face is listed in several cells; its hit counts only in the cell of the hit point,
+ *   cell(fp32(o + t d)) per axis (fp64 multiply and add, then rounded), clamped per axis into the cells the face is listed in.
+ *   The widening guarantees that this cell is visited, so t, face, bary, count and flags are bit-identical for every grid over the
+ *   same faces (1 x 1 x 1, the brute-force path, included), for every fill order and on every run -- for origins whose distance
+ *   from the mesh is within fp64's reach of the slack (2^30 extents, say) and hits that are not seen at a grazing angle below 2^-30.
+ *
+ * ops.mesh_inside casts TIR_RAY_COUNT rays along three fixed directions (fp32, below) over [0, +inf]; a vote is an odd count.
+ *
+ * Host validation before any device work: a null pointer with n > 0, a negative count, an unknown mode, t / face missing in
+ * TIR_RAY_CLOSEST / TIR_RAY_COUNT, count missing or t / face / bary given in TIR_RAY_ANY, the grid conditions above ->
+ * TIR_ERR_ARG; n or n_pairs > 2^31-1 -> TIR_ERR_UNSUPPORTED; n == 0 -> TIR_OK.  The entry takes a stream and allocates nothing. */
+#define TIR_RAY_CLOSEST 0
+#define TIR_RAY_COUNT 1
+#define TIR_RAY_ANY 2
+#define TIR_RAY_FLAG_GRAZED 1
+#define TIR_RAY_FLAG_INVALID 2
+#define TIR_RAY_COORD_SLACK (1.0 / 1048576.0)
+#define TIR_RAY_INSIDE_DIRECTIONS {{0.5345225f, 0.2672612f, 0.8017837f}, {-0.6882472f, 0.6246950f, -0.3692745f}, \
+                                   {0.1825742f, -0.9128709f, -0.3651484f}}
+int tir_ray_mesh(const float* origins, const float* dirs, const float* trange, int64_t n, const float* verts, int64_t n_verts,
+                 const int32_t* faces, int64_t n_faces, const float* cell, const float* origin, const int32_t* dims,
+                 const int32_t* cursor, const int32_t* pairs, int64_t n_pairs, const float* bounds, int mode, float* t,
+                 int32_t* face, float* bary, int32_t* count, int32_t* flags, int32_t* tested, void* stream);
+
 /* ---- per-point bake of materials and direct lighting (tensoir_amd/bake.py).  Point p is marched inward from
  * origins[p] along dirs[p] by tir_march_secondary_fwd with records; the caller decodes every record (BRDF decoder output
  * rec_brdf [A][4] = albedo rgb + raw roughness, shading normal rec_normal [A][3]).

@@ -180,6 +180,8 @@ SIGNATURES = {
     "tir_face_grid_fill": (C.c_int, [P, I64, P, I64, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(I32), I64, P, P, P, P, P]),
     "tir_point_mesh_distance": (C.c_int, [P, I64, P, I64, P, I64, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(I32), P, P,
                                           I64, P, P, P, P, P]),
+    "tir_ray_mesh": (C.c_int, [P, P, P, I64, P, I64, P, I64, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(I32), P, P, I64, P,
+                               C.c_int, P, P, P, P, P, P, P]),
     "tir_bake_composite": (C.c_int, [P, P, P, P, P, P, P, P, P, C.POINTER(C.c_float), I64, I64, P, P]),
     "tir_irradiance_integrate": (C.c_int, [P, P, P, P, P, P, I64, I32, I32, P, P]),
     "tir_atlas_corners": (C.c_int, [P, I64, P, P, I64, I32, I32, I32, P, P, P, P, P, P]),

@@ -187,6 +187,12 @@ def main(argv=None):
     ap.add_argument("--check-distance", type=int, nargs="?", const=262144, default=None, metavar="N", help="after writing OUT (.ply or "
                     ".glb), read it back and print its surface distance (mesh.distance, N samples per direction, default 262144) "
                     "to the full-resolution extraction as one JSON line")
+    ap.add_argument("--check-fscore", type=float, nargs="+", default=None, metavar="T", help="with --check-distance: add the F-score "
+                    "(precision of OUT, recall of the full-resolution extraction) at every distance threshold T")
+    ap.add_argument("--check-signed", action="store_true", help="with --check-distance: add the signed mean distance, the share of "
+                    "samples inside the other mesh and the undecided / grazed counts per direction (both meshes must be closed)")
+    ap.add_argument("--check-normals", action="store_true", help="with --check-distance: add normal_consistency and flipped_share per "
+                    "direction")
     ap.add_argument("--texture-size", type=int, default=None, metavar="N", help="write OUT as a binary glTF (.glb) with an N x N "
                     "texture atlas baked at every texel (base colour, occlusion / roughness / metallic, normal) instead of a PLY "
                     "with per-vertex attributes")
@@ -218,6 +224,10 @@ def main(argv=None):
         ap.error("--simplify K and --simplify-tolerance T are mutually exclusive")
     if a.check_distance is not None and a.check_distance < 0:
         ap.error("--check-distance N: N >= 0")
+    if a.check_distance is None and (a.check_fscore is not None or a.check_signed or a.check_normals):
+        ap.error("--check-fscore, --check-signed and --check-normals add to --check-distance")
+    if a.check_fscore is not None and any(not t >= 0.0 for t in a.check_fscore):
+        ap.error("--check-fscore T: T >= 0")
     simp = {"simplify": a.simplify, "simplify_tolerance": a.simplify_tolerance, "simplify_max": a.simplify_max}
     extra = {} if a.envmap is None else {"envmap_h": a.envmap[0], "envmap_w": a.envmap[1]}
     model = load_model(a.ckpt, "cuda", **extra)
@@ -252,7 +262,10 @@ def main(argv=None):
         if a.texture_size is not None:                     # the writer unwelds: three vertices per face, no index buffer
             full_v = full_v[full_f.reshape(-1).long()].contiguous()
             full_f = torch.arange(full_v.shape[0], dtype=torch.int32, device=full_v.device).view(-1, 3)
-        print(json.dumps({"check_distance": metrics.chamfer(a.out, (full_v, full_f), samples=a.check_distance)}))
+        more = {} if a.check_fscore is None else {"thresholds": tuple(a.check_fscore)}
+        more.update({"signed": True} if a.check_signed else {})
+        more.update({"normals": True} if a.check_normals else {})
+        print(json.dumps({"check_distance": metrics.chamfer(a.out, (full_v, full_f), samples=a.check_distance, **more)}))
     if a.check_views is not None:
         import json
         from . import raster

@@ -11,6 +11,7 @@
 //                                 of the block sums in between)
 //              k_fg_cells<true>   per face and overlapped cell: pairs[cursor[cell]++] = face; cursor[cell] ends as the cell's end
 //   query      k_point_mesh_distance  one lane per point: shells of cells of growing Chebyshev radius, fp64 closest point
+//              k_ray_mesh<mode>   one lane per ray: slabs of cells along the major axis, fp64 ray-triangle rule (tir_ray_mesh)
 // Every sum that crosses lanes is an integer sum, every minimum / maximum is order-independent: no output depends on the order
 // the device worked in, the order of the faces inside a cell included (ties go to the smaller face index).
 #include "tir_common.hpp"
@@ -498,6 +499,229 @@ k_point_mesh_distance(const float* __restrict__ points, int64_t n, const float* 
     if (tested) tested[i] = nt;
 }
 
+// ---- the ray query ---------------------------------------------------------------------------------------------------------------
+// e(P, Q) of the header: e(Q, P) == -e(P, Q) bit for bit (every difference of products is the exact negation of the other one)
+__device__ __forceinline__ double rm_edge(double dx, double dy, double dz, double px, double py, double pz, double qx, double qy,
+                                          double qz) {
+    const double x = d_mul(dx, d_sub(d_mul(py, qz), d_mul(pz, qy)));
+    const double y = d_mul(dy, d_sub(d_mul(pz, qx), d_mul(px, qz)));
+    const double z = d_mul(dz, d_sub(d_mul(px, qy), d_mul(py, qx)));
+    return d_add(d_add(x, y), z);
+}
+
+// the ray-triangle rule of the header: true when the LINE meets the face and den != 0; the range is the caller's
+__device__ __forceinline__ bool rm_test(const DsTri& T, double ox, double oy, double oz, double dx, double dy, double dz, double& t,
+                                        double& u, double& v, double& w) {
+    const double ax = d_sub(T.ax, ox), ay = d_sub(T.ay, oy), az = d_sub(T.az, oz);
+    const double bx = d_sub(T.bx, ox), by = d_sub(T.by, oy), bz = d_sub(T.bz, oz);
+    const double cx = d_sub(T.cx, ox), cy = d_sub(T.cy, oy), cz = d_sub(T.cz, oz);
+    u = rm_edge(dx, dy, dz, bx, by, bz, cx, cy, cz);
+    v = rm_edge(dx, dy, dz, cx, cy, cz, ax, ay, az);
+    w = rm_edge(dx, dy, dz, ax, ay, az, bx, by, bz);
+    const bool meets = ((u >= 0.0 && v >= 0.0 && w >= 0.0) || (u <= 0.0 && v <= 0.0 && w <= 0.0)) && !(u == 0.0 && v == 0.0 && w == 0.0);
+    const double px = d_sub(T.bx, T.ax), py = d_sub(T.by, T.ay), pz = d_sub(T.bz, T.az);
+    const double qx = d_sub(T.cx, T.ax), qy = d_sub(T.cy, T.ay), qz = d_sub(T.cz, T.az);
+    const double nx = d_sub(d_mul(py, qz), d_mul(pz, qy));
+    const double ny = d_sub(d_mul(pz, qx), d_mul(px, qz));
+    const double nz = d_sub(d_mul(px, qy), d_mul(py, qx));
+    const double den = d_add(d_add(d_mul(dx, nx), d_mul(dy, ny)), d_mul(dz, nz));
+    t = d_div(d_add(d_add(d_mul(ax, nx), d_mul(ay, ny)), d_mul(az, nz)), den);
+    return meets && den != 0.0;
+}
+
+// one of three values by a runtime axis, as conditional moves (an array indexed by it would become a scratch object)
+template <typename T>
+__device__ __forceinline__ T rm_sel(int axis, T a0, T a1, T a2) {
+    return axis == 0 ? a0 : (axis == 1 ? a1 : a2);
+}
+
+// the cell of an fp64 coordinate: rounded to fp32 first, as the cell function takes it (NaN -> cell 0, beyond fp32 -> an end cell)
+__device__ __forceinline__ int rm_cell(double x, float origin, float cell, int32_t dim) { return ds_cell((float)x, origin, cell, dim); }
+
+struct RmBest {
+    double t, u, v, w;
+    int32_t face, count, flags;
+};
+
+// every face listed in cell (x, y, z) against the ray; returns the number of faces tested.  MODE TIR_RAY_COUNT takes a hit only
+// in the cell of its own hit point (clamped into the cells the face is listed in), so that a face listed in several visited
+// cells is counted once; the other two modes keep the nearest / the first hit, which a second meeting does not change.
+template <int MODE>
+__device__ __forceinline__ int rm_visit(const float* __restrict__ verts, int64_t V, const int32_t* __restrict__ faces, int64_t F,
+                                        const DsGrid& G, const int32_t* __restrict__ cursor, const int32_t* __restrict__ pairs,
+                                        int64_t n_pairs, int x, int y, int z, double ox, double oy, double oz, double dx, double dy,
+                                        double dz, double t0, double t1, RmBest& B) {
+    const int32_t key = ds_cell_key(G, x, y, z);
+    int64_t k = key ? cursor[key - 1] : 0, end = cursor[key];
+    k = k < 0 ? 0 : k;
+    end = end < n_pairs ? end : n_pairs;
+    const int n_list = end > k ? (int)(end - k) : 0;       // an integer bound known before the loop
+    int tested = 0;
+    for (int j = 0; j < n_list; ++j) {
+        const int32_t f = pairs[k + j];
+        int32_t i0, i1, i2;
+        if (f < 0 || f >= F || !ds_face(faces, f, V, i0, i1, i2)) continue;
+        const DsTri T = ds_corners(verts, i0, i1, i2);
+        double t, u, v, w;
+        const bool meets = rm_test(T, ox, oy, oz, dx, dy, dz, t, u, v, w);
+        ++tested;
+        if (!(meets && t >= t0 && t <= t1)) continue;      // (false for a NaN)
+        const int grazed = (u == 0.0 || v == 0.0 || w == 0.0) ? TIR_RAY_FLAG_GRAZED : 0;
+        if constexpr (MODE == TIR_RAY_COUNT) {
+            const int hx = rm_cell(d_add(ox, d_mul(t, dx)), G.origin[0], G.cell[0], G.dims[0]);
+            const int hy = rm_cell(d_add(oy, d_mul(t, dy)), G.origin[1], G.cell[1], G.dims[1]);
+            const int hz = rm_cell(d_add(oz, d_mul(t, dz)), G.origin[2], G.cell[2], G.dims[2]);
+            const float fax = (float)T.ax, fbx = (float)T.bx, fcx = (float)T.cx;       // (exact: the corners came from fp32)
+            const float fay = (float)T.ay, fby = (float)T.by, fcy = (float)T.cy;
+            const float faz = (float)T.az, fbz = (float)T.bz, fcz = (float)T.cz;
+            const int lx = ds_cell(fminf(fax, fminf(fbx, fcx)), G.origin[0], G.cell[0], G.dims[0]);
+            const int ux = ds_cell(fmaxf(fax, fmaxf(fbx, fcx)), G.origin[0], G.cell[0], G.dims[0]);
+            const int ly = ds_cell(fminf(fay, fminf(fby, fcy)), G.origin[1], G.cell[1], G.dims[1]);
+            const int uy = ds_cell(fmaxf(fay, fmaxf(fby, fcy)), G.origin[1], G.cell[1], G.dims[1]);
+            const int lz = ds_cell(fminf(faz, fminf(fbz, fcz)), G.origin[2], G.cell[2], G.dims[2]);
+            const int uz = ds_cell(fmaxf(faz, fmaxf(fbz, fcz)), G.origin[2], G.cell[2], G.dims[2]);
+            if (min(max(hx, lx), ux) != x || min(max(hy, ly), uy) != y || min(max(hz, lz), uz) != z) continue;
+            B.count += 1;
+            B.flags |= grazed;
+        }
+        if (t < B.t || (t == B.t && f < B.face)) {
+            B.t = t;
+            B.u = u;
+            B.v = v;
+            B.w = w;
+            B.face = f;
+            if constexpr (MODE != TIR_RAY_COUNT) {
+                B.count = 1;
+                B.flags = grazed;
+            }
+        }
+    }
+    return tested;
+}
+
+// One lane per ray.  The walk (header, "Traversal"): clip to the box of the mesh, take the axis of the largest |d| as the major
+// axis, walk its slabs of cells from the entry to the exit, and per slab visit the rectangle of cells that the two other
+// coordinates cover over the slab's t interval -- every interval and coordinate widened by the slack.  Every loop runs on an
+// integer counter whose bound (at most a grid dimension, or a cell's list length) is known before the loop starts.
+template <int MODE>
+__global__ void __launch_bounds__(DS_THREADS)
+k_ray_mesh(const float* __restrict__ origins, const float* __restrict__ dirs, const float* __restrict__ trange, int64_t n,
+           const float* __restrict__ verts, int64_t V, const int32_t* __restrict__ faces, int64_t F, DsGrid G,
+           const int32_t* __restrict__ cursor, const int32_t* __restrict__ pairs, int64_t n_pairs, const float* __restrict__ bounds,
+           float* __restrict__ out_t, int32_t* __restrict__ out_face, float* __restrict__ out_bary, int32_t* __restrict__ out_count,
+           int32_t* __restrict__ out_flags, int32_t* __restrict__ out_tested) {
+    const int64_t i = (int64_t)blockIdx.x * DS_THREADS + threadIdx.x;
+    if (i >= n) return;
+    const float fox = origins[3 * i], foy = origins[3 * i + 1], foz = origins[3 * i + 2];
+    const float fdx = dirs[3 * i], fdy = dirs[3 * i + 1], fdz = dirs[3 * i + 2];
+    const float ft0 = trange ? trange[2 * i] : 0.0f, ft1 = trange ? trange[2 * i + 1] : (float)DS_INF;
+    const float nan = __builtin_nanf("");
+    const bool finite = fabsf(fox) < DS_INF && fabsf(foy) < DS_INF && fabsf(foz) < DS_INF && fabsf(fdx) < DS_INF && fabsf(fdy) < DS_INF &&
+                        fabsf(fdz) < DS_INF;               // (false for a NaN)
+    if (!(finite && (fdx != 0.0f || fdy != 0.0f || fdz != 0.0f) && ft0 <= ft1)) {
+        if (out_t) out_t[i] = nan;
+        if (out_face) out_face[i] = -1;
+        if (out_bary) out_bary[2 * i] = out_bary[2 * i + 1] = nan;
+        if (out_count) out_count[i] = 0;
+        if (out_flags) out_flags[i] = TIR_RAY_FLAG_INVALID;
+        if (out_tested) out_tested[i] = 0;
+        return;
+    }
+    const double ox = fox, oy = foy, oz = foz, dx = fdx, dy = fdy, dz = fdz, t0 = ft0, t1 = ft1;
+    const double lx = bounds[0], ly = bounds[1], lz = bounds[2], hx = bounds[3], hy = bounds[4], hz = bounds[5];
+    // 1. the part of [t0, t1] inside the box of the mesh
+    double T0 = t0, T1 = t1;
+    bool live = true;
+    if (dx == 0.0) {
+        live = live && !(ox < lx || ox > hx);
+    } else {
+        const double a = d_div(d_sub(lx, ox), dx), b = d_div(d_sub(hx, ox), dx);
+        T0 = fmax(T0, fmin(a, b));
+        T1 = fmin(T1, fmax(a, b));
+    }
+    if (dy == 0.0) {
+        live = live && !(oy < ly || oy > hy);
+    } else {
+        const double a = d_div(d_sub(ly, oy), dy), b = d_div(d_sub(hy, oy), dy);
+        T0 = fmax(T0, fmin(a, b));
+        T1 = fmin(T1, fmax(a, b));
+    }
+    if (dz == 0.0) {
+        live = live && !(oz < lz || oz > hz);
+    } else {
+        const double a = d_div(d_sub(lz, oz), dz), b = d_div(d_sub(hz, oz), dz);
+        T0 = fmax(T0, fmin(a, b));
+        T1 = fmin(T1, fmax(a, b));
+    }
+    live = live && T0 <= T1;
+    RmBest B{DS_INF, 0.0, 0.0, 0.0, 0x7fffffff, 0, 0};
+    int nt = 0;
+    if (live) {
+        // 2. the major axis m and the two others p = m + 1, q = m + 2 (mod 3), every per-axis value chosen by conditional moves
+        const double adx = fabs(dx), ady = fabs(dy), adz = fabs(dz);
+        int m = ady > adx ? 1 : 0;
+        m = adz > fmax(adx, ady) ? 2 : m;
+        const double ex = d_add(d_mul(TIR_DISTANCE_SLACK, (double)G.cell[0]), d_mul(TIR_RAY_COORD_SLACK, fmax(fabs(lx), fabs(hx))));
+        const double ey = d_add(d_mul(TIR_DISTANCE_SLACK, (double)G.cell[1]), d_mul(TIR_RAY_COORD_SLACK, fmax(fabs(ly), fabs(hy))));
+        const double ez = d_add(d_mul(TIR_DISTANCE_SLACK, (double)G.cell[2]), d_mul(TIR_RAY_COORD_SLACK, fmax(fabs(lz), fabs(hz))));
+        const double om = rm_sel(m, ox, oy, oz), op = rm_sel(m, oy, oz, ox), oq = rm_sel(m, oz, ox, oy);
+        const double dm = rm_sel(m, dx, dy, dz), dp = rm_sel(m, dy, dz, dx), dq = rm_sel(m, dz, dx, dy);
+        const double em = rm_sel(m, ex, ey, ez), ep = rm_sel(m, ey, ez, ex), eq = rm_sel(m, ez, ex, ey);
+        const float gom = rm_sel(m, G.origin[0], G.origin[1], G.origin[2]), gop = rm_sel(m, G.origin[1], G.origin[2], G.origin[0]),
+                    goq = rm_sel(m, G.origin[2], G.origin[0], G.origin[1]);
+        const float gcm = rm_sel(m, G.cell[0], G.cell[1], G.cell[2]), gcp = rm_sel(m, G.cell[1], G.cell[2], G.cell[0]),
+                    gcq = rm_sel(m, G.cell[2], G.cell[0], G.cell[1]);
+        const int gdm = rm_sel(m, G.dims[0], G.dims[1], G.dims[2]), gdp = rm_sel(m, G.dims[1], G.dims[2], G.dims[0]),
+                  gdq = rm_sel(m, G.dims[2], G.dims[0], G.dims[1]);
+        const double tw = d_div(fmax(ex, fmax(ey, ez)), fabs(dm));
+        const double T0w = d_sub(T0, tw), T1w = d_add(T1, tw);
+        const double x0 = d_add(om, d_mul(T0, dm)), x1 = d_add(om, d_mul(T1, dm));
+        const int sa = rm_cell(d_sub(fmin(x0, x1), em), gom, gcm, gdm), sb = rm_cell(d_add(fmax(x0, x1), em), gom, gcm, gdm);
+        const bool fwd = dm > 0.0;
+        const int n_slabs = sb - sa + 1;                   // <= the grid's dimension along the major axis
+        bool done = false;
+        for (int k = 0; k < n_slabs && !done; ++k) {
+            // 3. the slab's t interval: its two planes moved outward by the slack; the first and the last slab are open-ended
+            const int s = fwd ? sa + k : sb - k;
+            const double L = d_add((double)gom, d_mul((double)s, (double)gcm)), H = d_add((double)gom, d_mul((double)(s + 1), (double)gcm));
+            double tl = d_div(d_sub(d_sub(L, em), om), dm), th = d_div(d_sub(d_add(H, em), om), dm);
+            if (s == 0) tl = fwd ? -DS_INF : DS_INF;
+            if (s == gdm - 1) th = fwd ? DS_INF : -DS_INF;
+            double ta = fwd ? tl : th, tb = fwd ? th : tl;
+            // 5. no slab from here on holds a hit below its widened entry (strictly: a tie at B.t could still go to a smaller face)
+            if (MODE == TIR_RAY_CLOSEST && B.t < ta) break;
+            ta = fmax(ta, T0w);
+            tb = fmin(tb, T1w);
+            if (!(ta <= tb)) continue;
+            // 4. the rectangle of cells the two other coordinates cover over [ta, tb]
+            const double pa = d_add(op, d_mul(ta, dp)), pb = d_add(op, d_mul(tb, dp));
+            const double qa = d_add(oq, d_mul(ta, dq)), qb = d_add(oq, d_mul(tb, dq));
+            const int p0 = rm_cell(d_sub(fmin(pa, pb), ep), gop, gcp, gdp), p1 = rm_cell(d_add(fmax(pa, pb), ep), gop, gcp, gdp);
+            const int q0 = rm_cell(d_sub(fmin(qa, qb), eq), goq, gcq, gdq), q1 = rm_cell(d_add(fmax(qa, qb), eq), goq, gcq, gdq);
+            const int np = p1 - p0 + 1, nq = q1 - q0 + 1;  // <= the two other dimensions
+            for (int jp = 0; jp < np && !done; ++jp) {
+                for (int jq = 0; jq < nq && !done; ++jq) {
+                    const int cp = p0 + jp, cq = q0 + jq;
+                    const int x = rm_sel(m, s, cq, cp), y = rm_sel(m, cp, s, cq), z = rm_sel(m, cq, cp, s);
+                    nt += rm_visit<MODE>(verts, V, faces, F, G, cursor, pairs, n_pairs, x, y, z, ox, oy, oz, dx, dy, dz, t0, t1, B);
+                    if (MODE == TIR_RAY_ANY && B.count) done = true;
+                }
+            }
+        }
+    }
+    const bool found = B.face != 0x7fffffff;
+    if (out_t) out_t[i] = found ? (float)B.t : (float)DS_INF;
+    if (out_face) out_face[i] = found ? B.face : -1;
+    if (out_bary) {
+        const double sum = d_add(d_add(B.u, B.v), B.w);
+        out_bary[2 * i] = found ? (float)d_div(B.v, sum) : nan;
+        out_bary[2 * i + 1] = found ? (float)d_div(B.w, sum) : nan;
+    }
+    if (out_count) out_count[i] = B.count;
+    if (out_flags) out_flags[i] = MODE == TIR_RAY_ANY ? 0 : B.flags;
+    if (out_tested) out_tested[i] = nt;
+}
+
 // host-side validation shared by the grid entries and the query: 0, or a negative TIR_ERR_*; fills the grid and the cell count
 int ds_validate_grid(int64_t V, int64_t F, const float* cell, const float* origin, const int32_t* dims, DsGrid* G, int64_t* cells) {
     if (!cell || !origin || !dims || V < 0 || F < 0) return TIR_ERR_ARG;
@@ -625,6 +849,35 @@ extern "C" int tir_point_mesh_distance(const float* points, int64_t n, const flo
     if (n_pairs > 0 && (!pairs || !faces || !verts)) return TIR_ERR_ARG;
     hipLaunchKernelGGL(k_point_mesh_distance, dim3((unsigned)ds_blocks(n, DS_THREADS)), dim3(DS_THREADS), 0, tir_stream(stream), points,
                        n, verts, n_verts, faces, n_faces, G, cursor, pairs, n_pairs, dist, face, closest, tested);
+    TIR_CHECK_LAUNCH();
+    return TIR_OK;
+}
+
+extern "C" int tir_ray_mesh(const float* origins, const float* dirs, const float* trange, int64_t n, const float* verts, int64_t n_verts,
+                            const int32_t* faces, int64_t n_faces, const float* cell, const float* origin, const int32_t* dims,
+                            const int32_t* cursor, const int32_t* pairs, int64_t n_pairs, const float* bounds, int mode, float* t,
+                            int32_t* face, float* bary, int32_t* count, int32_t* flags, int32_t* tested, void* stream) {
+    DsGrid G;
+    int64_t n_cells = 0;
+    const int rc = ds_validate_grid(n_verts, n_faces, cell, origin, dims, &G, &n_cells);
+    if (rc) return rc;
+    if (n < 0 || n_pairs < 0) return TIR_ERR_ARG;
+    if (mode != TIR_RAY_CLOSEST && mode != TIR_RAY_COUNT && mode != TIR_RAY_ANY) return TIR_ERR_ARG;
+    if (mode == TIR_RAY_ANY && (t || face || bary)) return TIR_ERR_ARG;      // which face is met first depends on the grid
+    if (n > INT32_MAX || n_pairs > INT32_MAX) return TIR_ERR_UNSUPPORTED;
+    if (n == 0) return TIR_OK;
+    if (!origins || !dirs || !cursor || !bounds) return TIR_ERR_ARG;
+    if (mode == TIR_RAY_ANY ? !count : (!t || !face)) return TIR_ERR_ARG;
+    if (n_pairs > 0 && (!pairs || !faces || !verts)) return TIR_ERR_ARG;
+    const dim3 grid((unsigned)ds_blocks(n, DS_THREADS)), block(DS_THREADS);
+    hipStream_t st = tir_stream(stream);
+#define TIR_RAY_LAUNCH(M)                                                                                                         \
+    hipLaunchKernelGGL(k_ray_mesh<M>, grid, block, 0, st, origins, dirs, trange, n, verts, n_verts, faces, n_faces, G, cursor, pairs, \
+                       n_pairs, bounds, t, face, bary, count, flags, tested)
+    if (mode == TIR_RAY_CLOSEST) TIR_RAY_LAUNCH(TIR_RAY_CLOSEST);
+    else if (mode == TIR_RAY_COUNT) TIR_RAY_LAUNCH(TIR_RAY_COUNT);
+    else TIR_RAY_LAUNCH(TIR_RAY_ANY);
+#undef TIR_RAY_LAUNCH
     TIR_CHECK_LAUNCH();
     return TIR_OK;
 }

@@ -8,6 +8,8 @@
     export_textured(model, "scene.glb", simplify=3)      # + a texture atlas baked at every texel, as a binary glTF (tir_atlas_*)
     export_mesh(model, "scene.ply", simplify_tolerance=0.5)   # the smallest mesh within half a cell of the full one
     distance((va, fa), (vb, fb))                         # how far two surfaces lie apart: Chamfer, Hausdorff (tir_distance.hip)
+    distance(a, b, signed=True, thresholds=(0.5,), normals=True)   # + inflated or shrunk, F-score, normal consistency
+    raycast((v, f), origins, dirs)                       # what a ray hits on the mesh, exactly (tir_ray_mesh)
 
 Coordinates follow the reference, quirk included (Appendix B policy: parity first): convert_sdf_samples_to_ply takes the voxel
 size as (aabb[1] - aabb[0]) / shape -- `shape`, not `shape - 1` (utils.py:186) -- although getDenseAlpha's lattice spans the
@@ -297,32 +299,163 @@ def distance_summary(d_vertices, d_samples):
             "max": float(both.max()) if both.numel() else nan, "p95": p95, "n": n}
 
 
-def _one_way(src, dst, grid, samples, seed):
-    v, f = src
-    used = torch.unique(f.reshape(-1).long())                 # the vertices a face refers to, ascending
-    query = v[used]
-    if samples > 0:
-        query = torch.cat([query, ops.sample_surface(v, f, samples, seed)[0]])
-    d = ops.point_mesh_distance(query, dst[0], dst[1], grid)[0]
-    return distance_summary(d[:used.numel()], d[used.numel():])
+def topology(verts, faces):
+    """Whether the parity of ray crossings means inside (plain torch, on the device of the inputs).  Vertices are welded by
+    position first (-0.0 as 0.0), so a mesh with three vertices of its own per face (what write_glb stores) is judged by its
+    surface.  A face with a repeated welded vertex counts as "degenerate"; its self-edges are dropped.  -> {"closed": every
+    directed edge (a, b) occurs as often as its reverse (b, a) -- the exact condition under which an odd number of crossings
+    means inside; "boundary_edges": the directed edges without a partner, sum over edges of max(0, count(a, b) - count(b, a));
+    "degenerate"}.  A face index outside [0, V) raises ValueError."""
+    v = torch.as_tensor(verts).reshape(-1, 3)
+    f = torch.as_tensor(faces).reshape(-1, 3).long().to(v.device)
+    if f.numel() == 0:
+        return {"closed": True, "boundary_edges": 0, "degenerate": 0}
+    if int(f.min()) < 0 or int(f.max()) >= v.shape[0]:
+        raise ValueError("topology: a face index lies outside [0, V)")
+    uniq, inverse = torch.unique(v + 0.0, dim=0, return_inverse=True)
+    w = inverse[f]                                            # [F, 3] welded indices
+    a, b = w.reshape(-1), w.roll(-1, 1).reshape(-1)           # the directed edges (0, 1), (1, 2), (2, 0) of every face
+    degenerate = int(((w[:, 0] == w[:, 1]) | (w[:, 1] == w[:, 2]) | (w[:, 2] == w[:, 0])).sum())
+    keep = a != b
+    a, b = a[keep], b[keep]
+    n = uniq.shape[0]
+    key, cnt = torch.unique(a * n + b, return_counts=True)
+    rkey, rcnt = torch.unique(b * n + a, return_counts=True)  # (b, a) for every edge: how often the reverse of `rkey` occurs
+    pos = torch.searchsorted(rkey, key).clamp(max=max(rkey.numel() - 1, 0))
+    partner = torch.where(rkey[pos] == key, rcnt[pos], torch.zeros_like(cnt)) if key.numel() else cnt
+    boundary = int((cnt - partner).clamp(min=0).sum())
+    return {"closed": boundary == 0, "boundary_edges": boundary, "degenerate": degenerate}
+
+
+def face_normals(verts, faces, index):
+    """Unit fp64 normals (v1 - v0) x (v2 - v0) of faces `index` ([n] integer tensor); NaN for an index of -1 or a face without
+    area."""
+    idx = index.long()
+    tri = verts.to(torch.float64)[faces.long()[idx.clamp(min=0)]]
+    n = torch.linalg.cross(tri[:, 1] - tri[:, 0], tri[:, 2] - tri[:, 0])
+    n = n / n.norm(dim=1, keepdim=True)
+    return torch.where((idx >= 0)[:, None], n, torch.full_like(n, float("nan")))
 
 
 @torch.no_grad()
-def distance(a, b, samples=262144, seed=0):
+def raycast(mesh, origins, dirs, grid=None, trange=None, mode="closest"):
+    """Rays against a mesh: (verts [V, 3] f32, faces [F, 3] i32), origins and dirs [n, 3] f32 on the GPU (ops.ray_mesh: exact
+    fp64 ray-triangle rule over ops.face_grid, bit-identical for every grid).  mode "closest" or "count".  -> {"t" [n] f32 (+inf
+    on a miss, in units of |dir|), "face" [n] i32 (-1), "bary" [n, 2] f32 (weights of the face's second and third corner),
+    "point" [n, 3] f32 = origin + t dir, "normal" [n, 3] f32 = the unit face normal (v1 - v0) x (v2 - v0), "count" [n] i32,
+    "flags" [n] i32 (ops.RAY_GRAZED, ops.RAY_INVALID)}; bary, point and normal are NaN on a miss."""
+    if mode not in ("closest", "count"):
+        raise ValueError('raycast: mode "closest" or "count"')
+    verts, faces = mesh
+    t, face, bary, count, flags = ops.ray_mesh(origins, dirs, verts, faces, grid, mode=mode, trange=trange, bary=True, count=True,
+                                               flags=True)
+    hit = face >= 0
+    nan = torch.full_like(origins.reshape(-1, 3), float("nan"))
+    point = torch.where(hit[:, None], origins.reshape(-1, 3) + t[:, None] * dirs.reshape(-1, 3), nan)
+    return {"t": t, "face": face, "bary": bary, "point": point, "normal": face_normals(verts, faces, face).float(), "count": count,
+            "flags": flags}
+
+
+def signed_summary(d_samples, inside, votes, grazed):
+    """The signed figures of one direction from its samples' unsigned distances, and ops.mesh_inside's three outputs for them:
+    signed_mean = the mean of -d for a sample inside the other mesh and +d outside (float64), inside_share, undecided = the
+    samples whose three votes are not unanimous, grazed = the samples one of whose rays passed through an edge or a vertex."""
+    ds = torch.as_tensor(d_samples).reshape(-1).to(torch.float64)
+    inside, votes, grazed = (torch.as_tensor(x).reshape(-1) for x in (inside, votes, grazed))
+    n = ds.numel()
+    nan = float("nan")
+    sd = torch.where(inside.bool(), -ds, ds)
+    return {"signed_mean": float(sd.sum() / n) if n else nan, "inside_share": float(inside.bool().sum()) / n if n else nan,
+            "undecided": int(((votes == 1) | (votes == 2)).sum()), "grazed": int(grazed.bool().sum())}
+
+
+def normal_summary(n_own, n_near):
+    """normal_consistency = the mean |n . n'| over the samples (Occupancy Networks), flipped_share = the share with n . n' < 0;
+    n, n' [k, 3] unit normals, sums in float64."""
+    dot = (torch.as_tensor(n_own).to(torch.float64) * torch.as_tensor(n_near).to(torch.float64)).sum(1)
+    k = dot.numel()
+    nan = float("nan")
+    return {"normal_consistency": float(dot.abs().sum() / k) if k else nan, "flipped_share": float((dot < 0).sum()) / k if k else nan}
+
+
+def fscore_summary(d_a, d_b, thresholds):
+    """Per threshold: precision = the share of a's sample distances <= it, recall = the share of b's, fscore = 2 P R / (P + R)
+    (0 when both are 0); a is the prediction, b the ground truth."""
+    da, db = torch.as_tensor(d_a).reshape(-1), torch.as_tensor(d_b).reshape(-1)
+    out = []
+    for tau in thresholds:
+        p = float((da <= tau).sum()) / da.numel() if da.numel() else 0.0
+        r = float((db <= tau).sum()) / db.numel() if db.numel() else 0.0
+        out.append({"threshold": float(tau), "precision": p, "recall": r, "fscore": 2.0 * p * r / (p + r) if p + r > 0 else 0.0})
+    return out
+
+
+def _one_way(src, dst, grid, samples, seed, signed=False, normals=False):
+    v, f = src
+    used = torch.unique(f.reshape(-1).long())                 # the vertices a face refers to, ascending
+    query = v[used]
+    pts = own = None
+    if samples > 0:
+        pts, own = ops.sample_surface(v, f, samples, seed)
+        query = torch.cat([query, pts])
+    d, near = ops.point_mesh_distance(query, dst[0], dst[1], grid)
+    ds = d[used.numel():]
+    out = distance_summary(d[:used.numel()], ds)
+    if signed:
+        empty = v.new_zeros((0, 3))
+        out.update(signed_summary(ds, *ops.mesh_inside(empty if pts is None else pts, dst[0], dst[1], grid)))
+    if normals:
+        none = near[:0]
+        out.update(normal_summary(face_normals(v, f, none if own is None else own), face_normals(dst[0], dst[1], near[used.numel():])))
+    return out, ds
+
+
+def _check_distance_options(samples, signed, thresholds, normals, allow_open):
+    samples = int(samples)
+    if samples < 0:
+        raise ValueError("distance: samples >= 0")
+    if thresholds is not None:
+        thresholds = tuple(float(t) for t in ([thresholds] if isinstance(thresholds, (int, float)) else thresholds))
+        if not thresholds or any(not t >= 0.0 for t in thresholds):
+            raise ValueError("distance: thresholds is a non-empty sequence of distances >= 0")
+    for name, flag in (("signed", signed), ("normals", normals), ("allow_open", allow_open)):
+        if not isinstance(flag, bool):
+            raise ValueError(f"distance: {name} is True or False")
+    if allow_open and not signed:
+        raise ValueError("distance: allow_open belongs to signed=True")
+    return samples, thresholds
+
+
+@torch.no_grad()
+def distance(a, b, samples=262144, seed=0, *, signed=False, thresholds=None, normals=False, allow_open=False):
     """How far two surfaces lie apart.  a, b: (verts [V, 3] f32, faces [F, 3] i32) on the GPU -> {"a_to_b", "b_to_a": {mean, rms,
     max, p95, n}, "chamfer": a_to_b.mean + b_to_a.mean, "hausdorff": max(a_to_b.max, b_to_a.max)}, in the coordinates of the
     inputs.  A direction's queries are the vertices its mesh's faces refer to, followed by `samples` area-weighted stratified
     samples of its surface (ops.sample_surface with `seed`, the same for both directions); each is measured exactly against the
     other mesh (ops.point_mesh_distance over ops.face_grid).  mean, rms and p95 are taken over the samples, max over both
-    (distance_summary).  The same inputs give the same bits on every run."""
-    samples = int(samples)
-    if samples < 0:
-        raise ValueError("distance: samples >= 0")
+    (distance_summary).  The same inputs give the same bits on every run.
+    signed=True: each direction gains signed_mean, inside_share, undecided and grazed (signed_summary): a sample inside the other
+    mesh (ops.mesh_inside: the parity of three exact rays) counts with -distance; the magnitudes are the same bits.  Parity needs
+    a closed surface: a destination mesh that topology() does not find closed raises ValueError with its boundary-edge count,
+    unless allow_open=True.  thresholds=(tau, ...): "fscore" = fscore_summary over the samples' distances (a = prediction, b =
+    ground truth).  normals=True: each direction gains normal_consistency and flipped_share (normal_summary) between the fp64
+    normal of each sample's own face and that of its nearest face on the other mesh.  With none of the three the result and
+    its bits are what they were and no ray is cast."""
+    samples, thresholds = _check_distance_options(samples, signed, thresholds, normals, allow_open)
     (va, fa), (vb, fb) = a, b
+    if signed and not allow_open:
+        for name, (v, f) in (("a", a), ("b", b)):
+            topo = topology(v, f)
+            if not topo["closed"]:
+                raise ValueError(f"distance: signed=True needs closed surfaces, mesh {name} has {topo['boundary_edges']} boundary edges "
+                                 "(allow_open=True takes the parity as it comes)")
     ga, gb = ops.face_grid(va, fa), ops.face_grid(vb, fb)
-    ab = _one_way((va, fa), (vb, fb), gb, samples, seed)
-    ba = _one_way((vb, fb), (va, fa), ga, samples, seed)
-    return {"a_to_b": ab, "b_to_a": ba, "chamfer": ab["mean"] + ba["mean"], "hausdorff": max(ab["max"], ba["max"])}
+    ab, da = _one_way((va, fa), (vb, fb), gb, samples, seed, signed, normals)
+    ba, db = _one_way((vb, fb), (va, fa), ga, samples, seed, signed, normals)
+    out = {"a_to_b": ab, "b_to_a": ba, "chamfer": ab["mean"] + ba["mean"], "hausdorff": max(ab["max"], ba["max"])}
+    if thresholds is not None:
+        out["fscore"] = fscore_summary(da, db, thresholds)
+    return out
 
 
 def _model_grid(model, gridSize):

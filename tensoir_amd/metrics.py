@@ -153,7 +153,8 @@ def _mesh_on_device(m, dev):
 def chamfer(a, b, **kw):
     """mesh.distance under the name of the geometry figure of inverse-rendering papers: the Chamfer distance of a recovered
     mesh to a ground-truth one is result["chamfer"] (the sum of the two mean surface distances, in the meshes' coordinates).
-    a, b: (verts, faces) tensors or arrays, or paths to .ply / .glb files; kw: mesh.distance's samples and seed.  Host inputs
+    a, b: (verts, faces) tensors or arrays, or paths to .ply / .glb files; kw: mesh.distance's samples and seed, and its
+    options signed, thresholds, normals and allow_open (the signed distance, F-score and normal consistency).  Host inputs
     are uploaded; there is no CPU path."""
     from . import mesh
     dev = _device_of(*[x for m in (a, b) if isinstance(m, (tuple, list)) for x in m])

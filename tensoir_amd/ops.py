@@ -1768,8 +1768,9 @@ def face_grid(verts, faces, cell=None, max_pairs=None, *, dims=None, origin=None
     lists every face in its one cell: the brute-force path.
     -> {"cell", "origin", "dims": host lists, "cursor" [cells] i32 (the end of every cell's list), "pairs" [P] i32 (face
     indices; the order inside a cell may differ between runs, no result of point_mesh_distance depends on it), "n_pairs",
-    "degenerate", "listed", "n_faces", "n_verts"}.  One small read-back for the bounding box (and the mean edge), then one
-    32-byte read-back (pair total, error word, statistics) per cell edge tried; a face index outside [0, V) raises
+    "degenerate", "listed", "n_faces", "n_verts", "bounds" [6] f32 on the device (the box of the finite vertices, padded by
+    2^-16 max(max |coordinate|, largest extent): what ray_mesh clips its rays to)}.  One small read-back for the bounding box
+    (and the mean edge), then one 32-byte read-back (pair total, error word, statistics) per cell edge tried; a face index outside [0, V) raises
     TensoirHipError ("face index")."""
     verts, faces = _mesh_args(verts, faces)
     V, F = verts.shape[0], faces.shape[0]
@@ -1779,11 +1780,14 @@ def face_grid(verts, faces, cell=None, max_pairs=None, *, dims=None, origin=None
     if not 0 <= max_pairs <= limit:
         raise ValueError(f"face_grid: max_pairs in 0 .. {limit}")
     lo = hi = None
+    bounds = torch.zeros((6,), dtype=torch.float32, device=dev)
     if V:
         fin = torch.isfinite(verts)
         big = torch.finfo(torch.float32).max
         lo_t = torch.where(fin, verts, torch.full_like(verts, big)).amin(0)
         hi_t = torch.where(fin, verts, torch.full_like(verts, -big)).amax(0)
+        pad = torch.maximum(torch.maximum(lo_t.abs(), hi_t.abs()).amax(), (hi_t - lo_t).amax()) * (2.0 ** -16)
+        bounds = torch.cat([lo_t - pad, hi_t + pad])                  # (stays on the device: ray_mesh clips its rays to it)
         mean_edge = None
         if cell is None and dims is None and F:
             idx = faces.long().clamp(0, V - 1)
@@ -1832,7 +1836,7 @@ def face_grid(verts, faces, cell=None, max_pairs=None, *, dims=None, origin=None
     _call("tir_face_grid_fill", _ptr(verts if V else None), V, _ptr(faces if F else None), F, *cargs, pairs, _ptr(cursor), _ptr(counts),
           _ptr(offsets), _ptr(plist if pairs else None), _stream())
     return {"cell": [float(c) for c in cargs[0]], "origin": [float(o) for o in cargs[1]], "dims": dm, "cursor": cursor, "pairs": plist,
-            "n_pairs": pairs, "degenerate": degenerate, "listed": listed, "n_faces": F, "n_verts": V}
+            "n_pairs": pairs, "degenerate": degenerate, "listed": listed, "n_faces": F, "n_verts": V, "bounds": bounds}
 
 
 def point_mesh_distance(points, verts, faces, grid=None, closest=False, tested=False):
@@ -1863,6 +1867,89 @@ def point_mesh_distance(points, verts, faces, grid=None, closest=False, tested=F
           _ptr(grid["pairs"] if P else None), P, _ptr(dist if n else None), _ptr(face if n else None),
           _ptr(cl if closest and n else None), _ptr(nt if tested and n else None), _stream())
     return (dist, face) + ((cl,) if closest else ()) + ((nt,) if tested else ())
+
+
+RAY_MODES = {"closest": 0, "count": 1, "any": 2}                       # TIR_RAY_CLOSEST / COUNT / ANY
+RAY_GRAZED, RAY_INVALID = 1, 2                                        # TIR_RAY_FLAG_*
+# TIR_RAY_INSIDE_DIRECTIONS: the three fixed directions of mesh_inside (fp32)
+MESH_INSIDE_DIRECTIONS = ((0.5345225, 0.2672612, 0.8017837), (-0.6882472, 0.6246950, -0.3692745), (0.1825742, -0.9128709, -0.3651484))
+
+
+def _ray_grid(verts, faces, grid, what):
+    if grid is None:
+        grid = face_grid(verts, faces)
+    if grid["n_faces"] != faces.shape[0] or grid["n_verts"] != verts.shape[0] or grid["cursor"].device != verts.device \
+            or "bounds" not in grid:
+        raise ValueError(f"{what}: grid is not a face_grid of this mesh")
+    return grid
+
+
+def ray_mesh(origins, dirs, verts, faces, grid=None, mode="closest", trange=None, bary=False, count=False, flags=False, tested=False):
+    """Rays against a mesh (tir_ray_mesh; the ray-triangle rule, the traversal and the modes: include/tensoir_hip.h).
+    origins, dirs [n, 3] f32 (a direction need not be unit: t is in units of |d|), trange [n, 2] f32 or None ([0, +inf]), verts
+    [V, 3] f32, faces [F, 3] i32, all on one GPU; grid: face_grid(verts, faces) of THIS mesh (None builds the default one).
+    mode "closest" / "count" -> (t [n] f32, face [n] i32) followed, in this order, by bary [n, 2] f32 (weights of the face's
+    second and third corner), count [n] i32, flags [n] i32 (RAY_GRAZED, RAY_INVALID) and tested [n] i32 for the options that are
+    set.  A miss: t = +inf, face = -1, bary = NaN.  "count" counts every accepted hit exactly and walks the whole ray; "closest"
+    may stop early, its count is 0 or 1 and its grazed flag speaks of the reported hit only.  mode "any" -> (hit [n] bool),
+    followed by flags and tested if set; bary and count are refused.  Everything but `tested` is bit-identical for every grid
+    over the same faces and on every run.  An invalid ray (non-finite, d == 0, NaN range or t0 > t1): t = NaN, face = -1,
+    count = 0, flags = RAY_INVALID.  No read-back when a grid is handed in."""
+    if mode not in RAY_MODES:
+        raise ValueError(f"ray_mesh: mode is one of {sorted(RAY_MODES)}")
+    any_mode = mode == "any"
+    if any_mode and (bary or count):
+        raise ValueError('ray_mesh: mode "any" reports no bary and no count (which face is met first depends on the grid)')
+    verts, faces = _mesh_args(verts, faces)
+    origins = f32(origins, "origins", 3).view(-1, 3)
+    dirs = f32(dirs, "dirs", 3).view(-1, 3)
+    dev = verts.device
+    n = origins.shape[0]
+    if dirs.shape[0] != n:
+        raise ValueError("dirs: one direction per origin")
+    if trange is not None:
+        trange = f32(trange, "trange", 2).view(-1, 2)
+        if trange.shape[0] != n:
+            raise ValueError("trange: one [t0, t1] per ray")
+    if any(x.device != dev for x in (origins, dirs) + (() if trange is None else (trange,))):
+        raise ValueError("origins, dirs, trange: expected the device of verts")
+    grid = _ray_grid(verts, faces, grid, "ray_mesh")
+    V, F, P = verts.shape[0], faces.shape[0], grid["n_pairs"]
+
+    def buf(want, dtype, *shape):
+        return torch.empty(shape, dtype=dtype, device=dev) if want else None
+    t, face = buf(not any_mode, torch.float32, n), buf(not any_mode, torch.int32, n)
+    bc, fl, nt = buf(bary, torch.float32, n, 2), buf(flags, torch.int32, n), buf(tested, torch.int32, n)
+    cnt = buf(count or any_mode, torch.int32, n)
+    _call("tir_ray_mesh", _ptr(origins if n else None), _ptr(dirs if n else None), _ptr(trange if n and trange is not None else None), n,
+          _ptr(verts if V else None), V, _ptr(faces if F else None), F, (C.c_float * 3)(*grid["cell"]), (C.c_float * 3)(*grid["origin"]),
+          (C.c_int32 * 3)(*grid["dims"]), _ptr(grid["cursor"]), _ptr(grid["pairs"] if P else None), P, _ptr(grid["bounds"]),
+          RAY_MODES[mode], *[_ptr(x if x is not None and n else None) for x in (t, face, bc, cnt, fl, nt)], _stream())
+    if any_mode:
+        return (cnt != 0,) + ((fl,) if flags else ()) + ((nt,) if tested else ())
+    return (t, face) + ((bc,) if bary else ()) + ((cnt,) if count else ()) + ((fl,) if flags else ()) + ((nt,) if tested else ())
+
+
+def mesh_inside(points, verts, faces, grid=None):
+    """Which points lie inside a closed mesh: the parity of the hits of three "count" rays of ray_mesh from each point along
+    MESH_INSIDE_DIRECTIONS over [0, +inf].  -> (inside [n] bool = at least two odd counts, votes [n] uint8 = the odd counts, 0 .. 3,
+    grazed [n] bool = a ray passed exactly through an edge or a vertex, whose crossing may have been counted twice).  Parity
+    means inside only for a mesh whose every directed edge occurs as often as its reverse (mesh.topology's "closed").  A
+    non-finite point gets no vote.  Bit-identical for every grid and run; no read-back when a grid is handed in."""
+    verts, faces = _mesh_args(verts, faces)
+    points = f32(points, "points", 3).view(-1, 3)
+    if points.device != verts.device:
+        raise ValueError("points: expected the device of verts")
+    grid = _ray_grid(verts, faces, grid, "mesh_inside")
+    n = points.shape[0]
+    votes = torch.zeros((n,), dtype=torch.uint8, device=verts.device)
+    grazed = torch.zeros((n,), dtype=torch.bool, device=verts.device)
+    for d in MESH_INSIDE_DIRECTIONS:
+        dirs = torch.tensor(d, dtype=torch.float32, device=verts.device).expand(n, 3).contiguous()
+        _, _, cnt, fl = ray_mesh(points, dirs, verts, faces, grid, mode="count", count=True, flags=True)
+        votes += (cnt & 1).to(torch.uint8)
+        grazed |= (fl & RAY_GRAZED) != 0
+    return votes >= 2, votes, grazed
 
 
 # ---- per-point bake (tensoir_amd/bake.py) ---------------------------------------------------------
