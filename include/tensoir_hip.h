@@ -1118,6 +1118,28 @@ int tir_ray_mesh(const float* origins, const float* dirs, const float* trange, i
                  const int32_t* cursor, const int32_t* pairs, int64_t n_pairs, const float* bounds, int mode, float* t,
                  int32_t* face, float* bary, int32_t* count, int32_t* flags, int32_t* tested, void* stream);
 
+/* ---- Traced shadows of the light cells: one any-hit ray per (surface point, light cell) pair over the same grid
+ *      (tensoir_amd/csrc/tir_distance.hip; ops.shadow_trace, raster.relight_mesh(shadows="traced"); restated in numpy
+ *      by tests/shadowtrace_reference.py).  No maps, no bias in texels, no memory that grows with D S^2.
+ *   pts, nrm [M][3] fp32: the surface point and the stored, unflipped normal of each row; cells [D][8]: tir_env_cells' records;
+ *   the mesh and grid arguments are those of tir_ray_mesh; t0 fp32 >= 0: where the ray starts to count, in units of |L|.
+ *   occl [D][ceil(M / 64)] uint64: bit m & 63 of word [d][m >> 6] is 1 iff pair (m, d) is OCCLUDED.  Every word is written (no
+ *   clear is needed); the bits of rows beyond M are 0.
+ *   The rule for pair (m, d), L = cells[d].dir as stored (not renormalised):
+ *     it contributes iff c = n.L > 1e-6, c formed as tir_light_gbuffer and tir_shadow_lookup form it (sums of products may be
+ *     fused); a contributing pair is occluded iff the ray with origin pts[m], direction L and range [t0, +inf] has an accepted hit
+ *     under tir_ray_mesh's rule in TIR_RAY_ANY mode (the fp64 ray-triangle rule, the conservative walk: the same device function).
+ *     A pair that does not contribute and an invalid ray (a non-finite point, a non-finite or zero L) give bit 0.
+ *   The bits are identical for every grid over the same faces, for every fill order and on every run.
+ *   One wave covers 64 consecutive rows and walks the cells in chunks of 16; a wave's 64 answers for a cell are one ballot.
+ * Host validation before any device work: a negative count, D < 1, a t0 that is negative or not finite, the grid conditions of
+ *   tir_ray_mesh, and with M > 0 a null pointer, cells not 16-byte or occl not 8-byte aligned -> TIR_ERR_ARG; D > 2^20, M or
+ *   n_pairs > 2^31-1 -> TIR_ERR_UNSUPPORTED; M == 0 -> TIR_OK, nothing done.  The entry takes a stream and allocates nothing. */
+int tir_shadow_trace(const float* pts, const float* nrm, const float* cells, int64_t M, int32_t D, const float* verts,
+                     int64_t n_verts, const int32_t* faces, int64_t n_faces, const float* cell, const float* origin, const int32_t* dims,
+                     const int32_t* cursor, const int32_t* pairs, int64_t n_pairs, const float* bounds, float t0, uint64_t* occl,
+                     void* stream);
+
 /* ---- per-point bake of materials and direct lighting (tensoir_amd/bake.py).  Point p is marched inward from
  * origins[p] along dirs[p] by tir_march_secondary_fwd with records; the caller decodes every record (BRDF decoder output
  * rec_brdf [A][4] = albedo rgb + raw roughness, shading normal rec_normal [A][3]).
@@ -1346,6 +1368,16 @@ int tir_shadow_lookup(const float* pts, const float* nrm, const float* cells, co
 int tir_light_gbuffer_shadowed(const float* gbuf, const float* view, const float* cells, const float* pts, const float* frames,
                                const uint32_t* maps, int64_t M, int32_t D, int32_t S, float bias_const, float bias_slope, float fresnel,
                                int32_t flags, float* out, void* stream);
+
+/* tir_light_gbuffer_occluded: tir_light_gbuffer with occl [D][occl_stride] uint64, the packed answers of
+ *   tir_shadow_trace for the same rows and cells (occl_stride >= ceil(M / 64) words per cell): the same thread layout, arithmetic,
+ *   order, flags and validation; a pair with c > 1e-6 is added only when bit m & 63 of word [d][m >> 6] is 0, tested where
+ *   tir_light_gbuffer_shadowed tests its map, before the specular term.  With all words 0 the result equals tir_light_gbuffer's
+ *   bit for bit; with the bits of tir_shadow_lookup's code 1 it equals tir_light_gbuffer_shadowed's.  Blocks start at multiples
+ *   of 64 rows, so a wave reads one word per cell.  Validation as tir_light_gbuffer, and with M > 0 a null occl, occl not 8-byte
+ *   aligned or occl_stride < ceil(M / 64) -> TIR_ERR_ARG. */
+int tir_light_gbuffer_occluded(const float* gbuf, const float* view, const float* cells, const uint64_t* occl, int64_t occl_stride,
+                               int64_t M, int32_t D, float fresnel, int32_t flags, float* out, void* stream);
 
 /* ---- Image metrics of the evaluation loop (tensoir_amd/metrics.py; restated in numpy by tests/metrics_reference.py).
  * tir_ssim: the reference's rgb_ssim (utils.py:93-139) for N image pairs.  img0, img1 [N][H][W][C] fp32 on the device, channel

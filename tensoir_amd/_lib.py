@@ -182,6 +182,8 @@ SIGNATURES = {
                                           I64, P, P, P, P, P]),
     "tir_ray_mesh": (C.c_int, [P, P, P, I64, P, I64, P, I64, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(I32), P, P, I64, P,
                                C.c_int, P, P, P, P, P, P, P]),
+    "tir_shadow_trace": (C.c_int, [P, P, P, I64, I32, P, I64, P, I64, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(I32), P, P,
+                                   I64, P, F32, P, P]),
     "tir_bake_composite": (C.c_int, [P, P, P, P, P, P, P, P, P, C.POINTER(C.c_float), I64, I64, P, P]),
     "tir_irradiance_integrate": (C.c_int, [P, P, P, P, P, P, I64, I32, I32, P, P]),
     "tir_atlas_corners": (C.c_int, [P, I64, P, P, I64, I32, I32, I32, P, P, P, P, P, P]),
@@ -196,6 +198,7 @@ SIGNATURES = {
     "tir_shadow_maps": (C.c_int, [P, I64, P, I64, P, I32, I32, P, P, I32, P, P]),
     "tir_shadow_lookup": (C.c_int, [P, P, P, P, P, I64, I32, I32, F32, F32, P, P]),
     "tir_light_gbuffer_shadowed": (C.c_int, [P, P, P, P, P, P, I64, I32, I32, F32, F32, F32, I32, P, P]),
+    "tir_light_gbuffer_occluded": (C.c_int, [P, P, P, P, I64, I64, I32, F32, I32, P, P]),
     "tir_ssim_workspace": (I64, [I64, I32, I32, I32, I32]),
     "tir_ssim": (C.c_int, [P, P, I64, I32, I32, I32, P, I32, C.c_double, C.c_double, P, P, P, P]),
     "tir_image_error_workspace": (I64, [I64, I64]),

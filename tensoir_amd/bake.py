@@ -8,6 +8,7 @@ occlusion and direct irradiance under one of the model's lights, evaluated at su
     python -m tensoir_amd.bake CKPT OUT.glb --texture-size N --check-views V [--check-size S]   # + raster.compare_asset, one JSON line
     ... --check-views V --check-light NAME|FILE.hdr|FILE.npy [--check-light-rows R] [--write-views DIR]   # + relit_psnr
     ... --check-light ... --check-shadows [--shadow-size S]   # + shadow_agreement: the mesh's shadow maps against the field's visibility (4.10)
+    ... --check-shadows --shadow-method maps|traced|both [--shadow-eps X]   # the asset's exact traced shadows beside / instead of the maps (4.17)
     ... --environment OUT.hdr [--environment-size H W]                  # + the recovered light as a Radiance picture
 
 Per point p with unit outward direction n and s = model.stepSize:
@@ -208,6 +209,11 @@ def main(argv=None):
     ap.add_argument("--check-shadows", action="store_true", help="with --check-light: also build the asset's per-cell shadow maps and "
                     "report shadow_agreement, the share of (pixel, light cell) pairs on which they and the field's transmittance agree")
     ap.add_argument("--shadow-size", type=int, default=256, metavar="S", help="side of the S x S shadow maps (default 256)")
+    ap.add_argument("--shadow-method", choices=("maps", "traced", "both"), default="maps", help="with --check-shadows: the asset's "
+                    "visibility by its shadow maps (default), by exact any-hit rays over its face grid, or both -- then with "
+                    "shadow_agreement_traced and shadow_map_agreement (maps against traced) beside shadow_agreement")
+    ap.add_argument("--shadow-eps", type=float, default=None, metavar="X", help="traced shadows: rays start at X times the radius of "
+                    "the mesh's bounding sphere (default raster.SHADOW_EPS)")
     ap.add_argument("--environment", default=None, metavar="OUT.hdr", help="also write the model's light --light as a Radiance "
                     "picture (mesh.export_environment)")
     ap.add_argument("--environment-size", type=int, nargs=2, metavar=("H", "W"), default=(256, 512))
@@ -272,9 +278,13 @@ def main(argv=None):
         light = a.check_light
         if light in synth.HDR_NAMES:
             light = synth.make_hdr_maps(synth.HDR_NAMES, 64, 128)[light]            # as Environment_Light("synthetic:h=64,w=128")
+        shadow = {}
+        if a.check_shadows:
+            shadow = {"shadows": True if a.shadow_method == "maps" else a.shadow_method, "shadow_size": a.shadow_size}
+            if a.shadow_eps is not None:
+                shadow["shadow_eps"] = a.shadow_eps
         print(json.dumps(raster.compare_asset(model, a.out, H=a.check_size, W=a.check_size, n_views=a.check_views, grid=grid, light=light,
-                                              light_rows=a.check_light_rows, write_views=a.write_views,
-                                              **({"shadows": True, "shadow_size": a.shadow_size} if a.check_shadows else {}))))
+                                              light_rows=a.check_light_rows, write_views=a.write_views, **shadow)))
 
 
 if __name__ == "__main__":

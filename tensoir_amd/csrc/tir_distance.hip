@@ -12,6 +12,8 @@
 //              k_fg_cells<true>   per face and overlapped cell: pairs[cursor[cell]++] = face; cursor[cell] ends as the cell's end
 //   query      k_point_mesh_distance  one lane per point: shells of cells of growing Chebyshev radius, fp64 closest point
 //              k_ray_mesh<mode>   one lane per ray: slabs of cells along the major axis, fp64 ray-triangle rule (tir_ray_mesh)
+//              k_shadow_trace     one lane per surface point, the light cell as the loop counter: the same walk in any-hit mode, the
+//                                 64 answers of a wave packed by one ballot (tir_shadow_trace)
 // Every sum that crosses lanes is an integer sum, every minimum / maximum is order-independent: no output depends on the order
 // the device worked in, the order of the faces inside a cell included (ties go to the smaller face index).
 #include "tir_common.hpp"
@@ -599,35 +601,16 @@ __device__ __forceinline__ int rm_visit(const float* __restrict__ verts, int64_t
     return tested;
 }
 
-// One lane per ray.  The walk (header, "Traversal"): clip to the box of the mesh, take the axis of the largest |d| as the major
+// The walk of one valid ray (header, "Traversal"): clip to the box of the mesh, take the axis of the largest |d| as the major
 // axis, walk its slabs of cells from the entry to the exit, and per slab visit the rectangle of cells that the two other
 // coordinates cover over the slab's t interval -- every interval and coordinate widened by the slack.  Every loop runs on an
-// integer counter whose bound (at most a grid dimension, or a cell's list length) is known before the loop starts.
+// integer counter whose bound (at most a grid dimension, or a cell's list length) is known before the loop starts.  The one
+// walk of the file: k_ray_mesh and k_shadow_trace both call it.  Returns the number of faces tested.
 template <int MODE>
-__global__ void __launch_bounds__(DS_THREADS)
-k_ray_mesh(const float* __restrict__ origins, const float* __restrict__ dirs, const float* __restrict__ trange, int64_t n,
-           const float* __restrict__ verts, int64_t V, const int32_t* __restrict__ faces, int64_t F, DsGrid G,
-           const int32_t* __restrict__ cursor, const int32_t* __restrict__ pairs, int64_t n_pairs, const float* __restrict__ bounds,
-           float* __restrict__ out_t, int32_t* __restrict__ out_face, float* __restrict__ out_bary, int32_t* __restrict__ out_count,
-           int32_t* __restrict__ out_flags, int32_t* __restrict__ out_tested) {
-    const int64_t i = (int64_t)blockIdx.x * DS_THREADS + threadIdx.x;
-    if (i >= n) return;
-    const float fox = origins[3 * i], foy = origins[3 * i + 1], foz = origins[3 * i + 2];
-    const float fdx = dirs[3 * i], fdy = dirs[3 * i + 1], fdz = dirs[3 * i + 2];
-    const float ft0 = trange ? trange[2 * i] : 0.0f, ft1 = trange ? trange[2 * i + 1] : (float)DS_INF;
-    const float nan = __builtin_nanf("");
-    const bool finite = fabsf(fox) < DS_INF && fabsf(foy) < DS_INF && fabsf(foz) < DS_INF && fabsf(fdx) < DS_INF && fabsf(fdy) < DS_INF &&
-                        fabsf(fdz) < DS_INF;               // (false for a NaN)
-    if (!(finite && (fdx != 0.0f || fdy != 0.0f || fdz != 0.0f) && ft0 <= ft1)) {
-        if (out_t) out_t[i] = nan;
-        if (out_face) out_face[i] = -1;
-        if (out_bary) out_bary[2 * i] = out_bary[2 * i + 1] = nan;
-        if (out_count) out_count[i] = 0;
-        if (out_flags) out_flags[i] = TIR_RAY_FLAG_INVALID;
-        if (out_tested) out_tested[i] = 0;
-        return;
-    }
-    const double ox = fox, oy = foy, oz = foz, dx = fdx, dy = fdy, dz = fdz, t0 = ft0, t1 = ft1;
+__device__ __forceinline__ int rm_walk(const float* __restrict__ verts, int64_t V, const int32_t* __restrict__ faces, int64_t F,
+                                       const DsGrid& G, const int32_t* __restrict__ cursor, const int32_t* __restrict__ pairs,
+                                       int64_t n_pairs, const float* __restrict__ bounds, double ox, double oy, double oz, double dx,
+                                       double dy, double dz, double t0, double t1, RmBest& B) {
     const double lx = bounds[0], ly = bounds[1], lz = bounds[2], hx = bounds[3], hy = bounds[4], hz = bounds[5];
     // 1. the part of [t0, t1] inside the box of the mesh
     double T0 = t0, T1 = t1;
@@ -654,7 +637,6 @@ k_ray_mesh(const float* __restrict__ origins, const float* __restrict__ dirs, co
         T1 = fmin(T1, fmax(a, b));
     }
     live = live && T0 <= T1;
-    RmBest B{DS_INF, 0.0, 0.0, 0.0, 0x7fffffff, 0, 0};
     int nt = 0;
     if (live) {
         // 2. the major axis m and the two others p = m + 1, q = m + 2 (mod 3), every per-axis value chosen by conditional moves
@@ -709,6 +691,37 @@ k_ray_mesh(const float* __restrict__ origins, const float* __restrict__ dirs, co
             }
         }
     }
+    return nt;
+}
+
+// One lane per ray.
+template <int MODE>
+__global__ void __launch_bounds__(DS_THREADS)
+k_ray_mesh(const float* __restrict__ origins, const float* __restrict__ dirs, const float* __restrict__ trange, int64_t n,
+           const float* __restrict__ verts, int64_t V, const int32_t* __restrict__ faces, int64_t F, DsGrid G,
+           const int32_t* __restrict__ cursor, const int32_t* __restrict__ pairs, int64_t n_pairs, const float* __restrict__ bounds,
+           float* __restrict__ out_t, int32_t* __restrict__ out_face, float* __restrict__ out_bary, int32_t* __restrict__ out_count,
+           int32_t* __restrict__ out_flags, int32_t* __restrict__ out_tested) {
+    const int64_t i = (int64_t)blockIdx.x * DS_THREADS + threadIdx.x;
+    if (i >= n) return;
+    const float fox = origins[3 * i], foy = origins[3 * i + 1], foz = origins[3 * i + 2];
+    const float fdx = dirs[3 * i], fdy = dirs[3 * i + 1], fdz = dirs[3 * i + 2];
+    const float ft0 = trange ? trange[2 * i] : 0.0f, ft1 = trange ? trange[2 * i + 1] : (float)DS_INF;
+    const float nan = __builtin_nanf("");
+    const bool finite = fabsf(fox) < DS_INF && fabsf(foy) < DS_INF && fabsf(foz) < DS_INF && fabsf(fdx) < DS_INF && fabsf(fdy) < DS_INF &&
+                        fabsf(fdz) < DS_INF;               // (false for a NaN)
+    if (!(finite && (fdx != 0.0f || fdy != 0.0f || fdz != 0.0f) && ft0 <= ft1)) {
+        if (out_t) out_t[i] = nan;
+        if (out_face) out_face[i] = -1;
+        if (out_bary) out_bary[2 * i] = out_bary[2 * i + 1] = nan;
+        if (out_count) out_count[i] = 0;
+        if (out_flags) out_flags[i] = TIR_RAY_FLAG_INVALID;
+        if (out_tested) out_tested[i] = 0;
+        return;
+    }
+    const double ox = fox, oy = foy, oz = foz, dx = fdx, dy = fdy, dz = fdz, t0 = ft0, t1 = ft1;
+    RmBest B{DS_INF, 0.0, 0.0, 0.0, 0x7fffffff, 0, 0};
+    const int nt = rm_walk<MODE>(verts, V, faces, F, G, cursor, pairs, n_pairs, bounds, ox, oy, oz, dx, dy, dz, t0, t1, B);
     const bool found = B.face != 0x7fffffff;
     if (out_t) out_t[i] = found ? (float)B.t : (float)DS_INF;
     if (out_face) out_face[i] = found ? B.face : -1;
@@ -720,6 +733,48 @@ k_ray_mesh(const float* __restrict__ origins, const float* __restrict__ dirs, co
     if (out_count) out_count[i] = B.count;
     if (out_flags) out_flags[i] = MODE == TIR_RAY_ANY ? 0 : B.flags;
     if (out_tested) out_tested[i] = nt;
+}
+
+// ---- traced shadows of the light cells (tir_shadow_trace) -------------------------------------------------------------
+// One lane per row, one wave per 64 consecutive rows; the cell is the loop counter of a chunk of ST_CELLS cells, the same in
+// every lane, so its record arrives by scalar loads while the row's point and normal stay in registers.  A contributing pair
+// (c > 1e-6, tir::light_cosine) walks the grid with rm_walk<TIR_RAY_ANY> over [t0, +inf]; the 64 answers are one ballot that the
+// wave's first lane stores.  A wave without a contributing lane skips the walk (the branch is empty for it) and stores 0.
+constexpr int ST_CELLS = 16;
+
+__global__ void __launch_bounds__(DS_THREADS)
+k_shadow_trace(const float* __restrict__ pts, const float* __restrict__ nrm, const float4* __restrict__ cells, int64_t M, int D,
+               const float* __restrict__ verts, int64_t V, const int32_t* __restrict__ faces, int64_t F, DsGrid G,
+               const int32_t* __restrict__ cursor, const int32_t* __restrict__ pairs, int64_t n_pairs, const float* __restrict__ bounds,
+               float ft0, unsigned long long* __restrict__ occl, int64_t words) {
+    const int64_t m = (int64_t)blockIdx.x * DS_THREADS + threadIdx.x;
+    const int64_t word = m >> 6;                           // the same in every lane of the wave: blocks start at multiples of 64
+    const bool row = m < M;
+    float p0 = 0.0f, p1 = 0.0f, p2 = 0.0f, n0 = 0.0f, n1 = 0.0f, n2 = 0.0f;
+    if (row) {
+        p0 = pts[3 * m]; p1 = pts[3 * m + 1]; p2 = pts[3 * m + 2];
+        n0 = nrm[3 * m]; n1 = nrm[3 * m + 1]; n2 = nrm[3 * m + 2];
+    }
+    const bool valid = row && fabsf(p0) < DS_INF && fabsf(p1) < DS_INF && fabsf(p2) < DS_INF;      // (false for a NaN)
+    const double ox = p0, oy = p1, oz = p2, t0 = ft0;
+    for (int d0 = (int)blockIdx.y * ST_CELLS; d0 < D; d0 += (int)gridDim.y * ST_CELLS) {
+        const int d1 = min(d0 + ST_CELLS, D);
+        for (int d = d0; d < d1; ++d) {
+            const float4 ca = cells[2 * (size_t)d];
+            const float c = tir::light_cosine(n0, n1, n2, ca.x, ca.y, ca.z);
+            const bool ray = fabsf(ca.x) < DS_INF && fabsf(ca.y) < DS_INF && fabsf(ca.z) < DS_INF &&
+                             (ca.x != 0.0f || ca.y != 0.0f || ca.z != 0.0f);
+            bool hit = false;
+            if (valid && ray && c > 1e-6f) {
+                RmBest B{DS_INF, 0.0, 0.0, 0.0, 0x7fffffff, 0, 0};
+                rm_walk<TIR_RAY_ANY>(verts, V, faces, F, G, cursor, pairs, n_pairs, bounds, ox, oy, oz, (double)ca.x, (double)ca.y,
+                                     (double)ca.z, t0, DS_INF, B);
+                hit = B.count != 0;
+            }
+            const unsigned long long bits = __ballot(hit);
+            if ((threadIdx.x & 63) == 0 && word < words) occl[(size_t)d * (size_t)words + (size_t)word] = bits;
+        }
+    }
 }
 
 // host-side validation shared by the grid entries and the query: 0, or a negative TIR_ERR_*; fills the grid and the cell count
@@ -878,6 +933,28 @@ extern "C" int tir_ray_mesh(const float* origins, const float* dirs, const float
     else if (mode == TIR_RAY_COUNT) TIR_RAY_LAUNCH(TIR_RAY_COUNT);
     else TIR_RAY_LAUNCH(TIR_RAY_ANY);
 #undef TIR_RAY_LAUNCH
+    TIR_CHECK_LAUNCH();
+    return TIR_OK;
+}
+
+extern "C" int tir_shadow_trace(const float* pts, const float* nrm, const float* cells, int64_t M, int32_t D, const float* verts,
+                                int64_t n_verts, const int32_t* faces, int64_t n_faces, const float* cell, const float* origin,
+                                const int32_t* dims, const int32_t* cursor, const int32_t* pairs, int64_t n_pairs, const float* bounds,
+                                float t0, uint64_t* occl, void* stream) {
+    DsGrid G;
+    int64_t n_cells = 0;
+    const int rc = ds_validate_grid(n_verts, n_faces, cell, origin, dims, &G, &n_cells);
+    if (rc) return rc;
+    if (M < 0 || n_pairs < 0 || D < 1 || !(t0 >= 0.0f && t0 < (float)DS_INF)) return TIR_ERR_ARG;
+    if (D > (1 << 20) || M > INT32_MAX || n_pairs > INT32_MAX) return TIR_ERR_UNSUPPORTED;
+    if (M == 0) return TIR_OK;
+    if (!pts || !nrm || !cells || !cursor || !bounds || !occl) return TIR_ERR_ARG;
+    if (reinterpret_cast<uintptr_t>(cells) % 16 != 0 || reinterpret_cast<uintptr_t>(occl) % 8 != 0) return TIR_ERR_ARG;
+    if (n_pairs > 0 && (!pairs || !faces || !verts)) return TIR_ERR_ARG;
+    const unsigned chunks = (unsigned)((D + ST_CELLS - 1) / ST_CELLS);
+    hipLaunchKernelGGL(k_shadow_trace, dim3((unsigned)ds_blocks(M, DS_THREADS), chunks < 65535u ? chunks : 65535u), dim3(DS_THREADS), 0,
+                       tir_stream(stream), pts, nrm, reinterpret_cast<const float4*>(cells), M, (int)D, verts, n_verts, faces, n_faces, G,
+                       cursor, pairs, n_pairs, bounds, t0, reinterpret_cast<unsigned long long*>(occl), (M + 63) / 64);
     TIR_CHECK_LAUNCH();
     return TIR_OK;
 }

@@ -863,6 +863,10 @@ k_env_cells(const float* __restrict__ hdr, int H, int W, const float* __restrict
 // pixel: two calls give identical bits, whatever the order of the pixels.
 // SHADOW: a contributing pair is added only when tir::shadow_lit says so, tested before the specular term; without
 // it the instantiation is the unshadowed kernel, instruction for instruction.
+// LIGHT_TRACED: the pair is added only when its bit of occl (tir_shadow_trace) is 0, tested at the same place.  A
+// block starts at a multiple of 64 rows, so the word of (cell, wave) is the same in every lane: one scalar load.
+constexpr int LIGHT_PLAIN = 0, LIGHT_MAPS = 1, LIGHT_TRACED = 2;
+
 struct LightShadow {
     const float* pts;                                    // [M][3]
     const float* frames;                                 // [D][12]
@@ -871,9 +875,15 @@ struct LightShadow {
     tir::ShadowBias bias;
 };
 
-template <bool SHADOW>
+struct LightOccluded {
+    const unsigned long long* occl;                      // [D][stride]: bit m & 63 of word m >> 6 = pair (m, d) is occluded
+    int64_t stride;                                      // words per cell, >= ceil(M / 64)
+};
+
+template <int SHADOW>
 __device__ __forceinline__ void light_rows(const float4* __restrict__ gbuf, const float* __restrict__ view, const float4* __restrict__ cells,
-                                           int64_t M, int D, float fresnel, int flags, float4* __restrict__ out, const LightShadow& sh) {
+                                           int64_t M, int D, float fresnel, int flags, float4* __restrict__ out, const LightShadow& sh,
+                                           const LightOccluded& oc) {
     const int64_t m = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (m >= M) return;
     const float4 g0 = gbuf[3 * m], g1 = gbuf[3 * m + 1], g2 = gbuf[3 * m + 2];      // TIR_RASTER_ROW = 12 floats
@@ -888,16 +898,21 @@ __device__ __forceinline__ void light_rows(const float4* __restrict__ gbuf, cons
     const float four_pi = 4.0f * 3.14159265358979323846f;
     float acc[3] = {0.f, 0.f, 0.f};
     float pt[3] = {0.f, 0.f, 0.f};
-    if constexpr (SHADOW) { pt[0] = sh.pts[3 * m]; pt[1] = sh.pts[3 * m + 1]; pt[2] = sh.pts[3 * m + 2]; }
+    if constexpr (SHADOW == LIGHT_MAPS) { pt[0] = sh.pts[3 * m]; pt[1] = sh.pts[3 * m + 1]; pt[2] = sh.pts[3 * m + 2]; }
+    int word = 0;
+    if constexpr (SHADOW == LIGHT_TRACED) word = __builtin_amdgcn_readfirstlane((int)(m >> 6));    // M <= 2^36: below 2^30
     for (int d = 0; d < D; ++d) {
         const float4 ca = cells[2 * (size_t)d], cb = cells[2 * (size_t)d + 1];
         const float lx = ca.x, ly = ca.y, lz = ca.z;
         const float c = ns[0] * lx + ns[1] * ly + ns[2] * lz;                        // tir::light_cosine's expression
         if (c > 1e-6f) {
-            if constexpr (SHADOW) {
+            if constexpr (SHADOW == LIGHT_MAPS) {
                 if (!tir::shadow_lit(sh.frames + 12 * (size_t)d, sh.maps + (size_t)d * (size_t)sh.S * (size_t)sh.S, sh.S, pt[0], pt[1],
                                      pt[2], c, sh.bias))
                     continue;
+            }
+            if constexpr (SHADOW == LIGHT_TRACED) {
+                if ((oc.occl[(size_t)d * (size_t)oc.stride + (size_t)word] >> (threadIdx.x & 63)) & 1ull) continue;
             }
             float hx = (lx + s.V[0]) * 0.5f, hy = (ly + s.V[1]) * 0.5f, hz = (lz + s.V[2]) * 0.5f;
             const float inv = __builtin_amdgcn_rsqf(fmaxf(hx * hx + hy * hy + hz * hz, 1e-24f));    // x / max(|x|, 1e-12)
@@ -927,13 +942,19 @@ __device__ __forceinline__ void light_rows(const float4* __restrict__ gbuf, cons
 __global__ void __launch_bounds__(256)
 k_light_gbuffer(const float4* __restrict__ gbuf, const float* __restrict__ view, const float4* __restrict__ cells, int64_t M, int D,
                 float fresnel, int flags, float4* __restrict__ out) {
-    light_rows<false>(gbuf, view, cells, M, D, fresnel, flags, out, LightShadow{});
+    light_rows<LIGHT_PLAIN>(gbuf, view, cells, M, D, fresnel, flags, out, LightShadow{}, LightOccluded{});
 }
 
 __global__ void __launch_bounds__(256)
 k_light_gbuffer_shadowed(const float4* __restrict__ gbuf, const float* __restrict__ view, const float4* __restrict__ cells, int64_t M,
                          int D, float fresnel, int flags, float4* __restrict__ out, LightShadow sh) {
-    light_rows<true>(gbuf, view, cells, M, D, fresnel, flags, out, sh);
+    light_rows<LIGHT_MAPS>(gbuf, view, cells, M, D, fresnel, flags, out, sh, LightOccluded{});
+}
+
+__global__ void __launch_bounds__(256)
+k_light_gbuffer_occluded(const float4* __restrict__ gbuf, const float* __restrict__ view, const float4* __restrict__ cells, int64_t M,
+                         int D, float fresnel, int flags, float4* __restrict__ out, LightOccluded oc) {
+    light_rows<LIGHT_TRACED>(gbuf, view, cells, M, D, fresnel, flags, out, LightShadow{}, oc);
 }
 
 }  // namespace
@@ -982,6 +1003,24 @@ extern "C" int tir_light_gbuffer_shadowed(const float* gbuf, const float* view, 
     hipLaunchKernelGGL(k_light_gbuffer_shadowed, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, tir_stream(stream),
                        reinterpret_cast<const float4*>(gbuf), view, reinterpret_cast<const float4*>(cells), M, (int)D, fresnel,
                        (int)flags, reinterpret_cast<float4*>(out), sh);
+    TIR_CHECK_LAUNCH();
+    return TIR_OK;
+}
+
+extern "C" int tir_light_gbuffer_occluded(const float* gbuf, const float* view, const float* cells, const uint64_t* occl,
+                                          int64_t occl_stride, int64_t M, int32_t D, float fresnel, int32_t flags, float* out,
+                                          void* stream) {
+    if (M < 0 || D < 1 || (flags & ~(TIR_LIGHT_OCCLUSION | TIR_LIGHT_SRGB))) return TIR_ERR_ARG;
+    if (D > (1 << 20) || M > ((int64_t)1 << 36)) return TIR_ERR_UNSUPPORTED;
+    if (M == 0) return TIR_OK;
+    if (!gbuf || !view || !cells || !out || !occl || occl_stride < (M + 63) / 64) return TIR_ERR_ARG;
+    if (reinterpret_cast<uintptr_t>(gbuf) % 16 != 0 || reinterpret_cast<uintptr_t>(cells) % 16 != 0 ||
+        reinterpret_cast<uintptr_t>(out) % 16 != 0 || reinterpret_cast<uintptr_t>(occl) % 8 != 0)
+        return TIR_ERR_ARG;
+    const LightOccluded oc{reinterpret_cast<const unsigned long long*>(occl), occl_stride};
+    hipLaunchKernelGGL(k_light_gbuffer_occluded, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, tir_stream(stream),
+                       reinterpret_cast<const float4*>(gbuf), view, reinterpret_cast<const float4*>(cells), M, (int)D, fresnel,
+                       (int)flags, reinterpret_cast<float4*>(out), oc);
     TIR_CHECK_LAUNCH();
     return TIR_OK;
 }

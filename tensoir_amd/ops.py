@@ -2333,6 +2333,81 @@ def light_gbuffer_shadowed(gbuf, view, cells, pts, frames, maps, bias, fresnel=0
     return out
 
 
+# ---- traced shadows of the exported asset: one any-hit ray per (point, light cell) pair (tensoir_amd/raster.py) ----
+def _occl_words(M):
+    return (int(M) + 63) // 64
+
+
+def shadow_trace(pts, nrm, cells, verts, faces, grid=None, t0=0.0):
+    """tir_shadow_trace: pts, nrm [M, 3] (surface points and their stored normals), cells [D, 8] (env_cells), verts [V, 3] f32 and
+    faces [F, 3] i32 on one GPU; grid: face_grid(verts, faces) of THIS mesh (None builds the default one) -> occl [D, ceil(M / 64)]
+    int64: bit m & 63 of word [d, m >> 6] is 1 iff pair (m, d) contributes (n.L > 1e-6, as light_gbuffer forms it) and the ray from
+    pts[m] along cells[d]'s direction over [t0, +inf] meets the mesh by ray_mesh's rule (mode "any").  Every other bit is 0.
+    The bits are identical for every grid over the same faces.  No read-back when a grid is handed in."""
+    pts, nrm, cells = f32(pts, "pts", 3).view(-1, 3), f32(nrm, "nrm", 3).view(-1, 3), f32(cells, "cells", 8).view(-1, 8)
+    verts, faces = _mesh_args(verts, faces)
+    dev = verts.device
+    if pts.shape != nrm.shape:
+        raise ValueError("shadow_trace: one normal per point")
+    if cells.shape[0] < 1:
+        raise ValueError("shadow_trace: at least one light cell")
+    if any(x.device != dev for x in (pts, nrm, cells)):
+        raise ValueError("pts, nrm, cells: expected the device of verts")
+    t0 = float(t0)
+    if not (t0 >= 0.0 and math.isfinite(t0)):
+        raise ValueError("shadow_trace: t0 is finite and >= 0")
+    grid = _ray_grid(verts, faces, grid, "shadow_trace")
+    M, D, V, F, P = pts.shape[0], cells.shape[0], verts.shape[0], faces.shape[0], grid["n_pairs"]
+    occl = torch.empty((D, _occl_words(M)), dtype=torch.int64, device=dev)
+    _call("tir_shadow_trace", _ptr(pts if M else None), _ptr(nrm if M else None), _ptr(cells), M, D, _ptr(verts if V else None), V,
+          _ptr(faces if F else None), F, (C.c_float * 3)(*grid["cell"]), (C.c_float * 3)(*grid["origin"]), (C.c_int32 * 3)(*grid["dims"]),
+          _ptr(grid["cursor"]), _ptr(grid["pairs"] if P else None), P, _ptr(grid["bounds"]), t0, _ptr(occl if M else None), _stream())
+    return occl
+
+
+def occlusion_bits(occl, M):
+    """occl [D, ceil(M / 64)] int64 (shadow_trace) -> bool [M, D]: pair (m, d) is occluded.  Plain torch, for tests and diagnostics."""
+    occl = torch.as_tensor(occl)
+    M = int(M)
+    if occl.dtype != torch.int64 or occl.dim() != 2 or occl.shape[1] != _occl_words(M):
+        raise ValueError("occlusion_bits: occl is [D, ceil(M / 64)]")
+    shifts = torch.arange(64, dtype=torch.int64, device=occl.device)
+    bits = ((occl[:, :, None] >> shifts) & 1) != 0                        # (an arithmetic shift: the mask keeps the one bit)
+    return bits.reshape(occl.shape[0], -1)[:, :M].t().contiguous()
+
+
+def pack_occlusion(mask):
+    """bool [M, D] -> occl [D, ceil(M / 64)] int64, the layout of shadow_trace (rows beyond M: 0).  Plain torch."""
+    mask = torch.as_tensor(mask)
+    if mask.dim() != 2:
+        raise ValueError("pack_occlusion: mask is [M, D]")
+    M, D = mask.shape
+    W = _occl_words(M)
+    b = torch.zeros((D, W * 64), dtype=torch.int64, device=mask.device)
+    b[:, :M] = (mask != 0).t().to(torch.int64)
+    shifts = torch.arange(64, dtype=torch.int64, device=mask.device)
+    return (b.view(D, W, 64) << shifts).sum(-1).contiguous()              # (bit 63 wraps into the sign: the sum is exact mod 2^64)
+
+
+def light_gbuffer_occluded(gbuf, view, cells, occl, fresnel=0.04, occlusion=True, srgb=False):
+    """tir_light_gbuffer_occluded: light_gbuffer with occl [D, >= ceil(M / 64)] int64 (shadow_trace of the same rows and cells): a
+    cell lights a row only where the pair's bit is 0.  -> [..., 4] = {r, g, b, coverage}."""
+    gbuf, view, cells = f32(gbuf, "gbuf", RASTER_ROW), f32(view, "view", 3), f32(cells, "cells", 8).view(-1, 8)
+    occl = _req(occl, torch.int64, "occl")
+    if gbuf.shape[:-1] != view.shape[:-1]:
+        raise ValueError("light_gbuffer_occluded: gbuf and view take one row per pixel")
+    M, D = gbuf.numel() // RASTER_ROW, cells.shape[0]
+    if D < 1:
+        raise ValueError("light_gbuffer_occluded: at least one light cell")
+    if occl.dim() != 2 or occl.shape[0] != D or occl.shape[1] < _occl_words(M) or occl.device != gbuf.device:
+        raise ValueError("light_gbuffer_occluded: occl is [D, ceil(M / 64)] int64 on gbuf's device (shadow_trace)")
+    out = torch.empty(gbuf.shape[:-1] + (4,), dtype=torch.float32, device=gbuf.device)
+    flags = (LIGHT_OCCLUSION if occlusion else 0) | (LIGHT_SRGB if srgb else 0)
+    _call("tir_light_gbuffer_occluded", _ptr(gbuf), _ptr(view), _ptr(cells), _ptr(occl if M else None), occl.shape[1], M, D,
+          float(fresnel), flags, _ptr(out), _stream())
+    return out
+
+
 # ---- image metrics (tensoir_amd/metrics.py; DESIGN 4.11) -----------------------------------------------------------------------
 SSIM_TILE = 16                   # TIR_SSIM_TILE: the side of the output tile one workgroup of tir_ssim computes
 SSIM_MAX_TAPS = 31               # TIR_SSIM_MAX_TAPS

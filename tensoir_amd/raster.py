@@ -8,6 +8,8 @@ include/tensoir_hip.h, tir_raster_*), and the comparison of a textured GLB with 
     report = compare_asset(model, "scene.glb", light="city.hdr")          # + relit_psnr: the same light on field and asset
     out = relight_glb("scene.glb", "city.hdr", c2w, focal, H, W, shadows=True)   # the mesh shadows itself: a shadow map per cell (4.10)
     report = compare_asset(model, "scene.glb", light="city.hdr", shadows=True)   # + shadow_agreement: the maps against the field's visibility
+    out = relight_glb("scene.glb", "city.hdr", c2w, focal, H, W, shadows="traced")       # exact shadows: one any-hit ray per pair (4.17)
+    report = compare_asset(model, "scene.glb", light="city.hdr", shadows="both")         # maps vs. field, traced vs. field, maps vs. traced
 
 Camera: the datasets' convention.  Pixel (i, j) has its centre at (i + 0.5, j + 0.5) and the camera-space direction
 ((i + 0.5 - W/2) / f, (j + 0.5 - H/2) / f, 1); c2w [3, 4] has the columns x right, y down, z forward and the eye.  All per-corner
@@ -191,9 +193,47 @@ def shadow_maps_for(pos, cells, S=256):
     return frames, ops.shadow_maps(pos, frames, S)[0]
 
 
+SHADOW_EPS = 1e-2                # traced shadows start at t0 = SHADOW_EPS x the radius of mesh_bounds: the rule of DESIGN 4.17
+SHADOW_METHODS = {None: None, False: None, True: "maps", "maps": "maps", "traced": "traced"}
+
+
+def _shadow_method(shadows, extra=()):
+    """shadows -> None (no shadows), "maps" (True), "traced", or one of `extra` as it is."""
+    if isinstance(shadows, str) and shadows in extra:
+        return shadows
+    try:
+        return SHADOW_METHODS[shadows]
+    except (KeyError, TypeError):
+        raise ValueError(f"shadows is one of False, True, {', '.join(repr(k) for k in ('maps', 'traced') + tuple(extra))}") from None
+
+
+def shadow_grid_for(pos, faces=None):
+    """The mesh and its face grid as traced shadows take them: pos [3F, 3] (unwelded: faces = arange) or verts [V, 3] with faces
+    [F, 3] int32 -> (verts, faces, grid = ops.face_grid(verts, faces)), what relight_mesh(shadows="traced", shadow_grid=...) takes.
+    It depends on the mesh only: build it once for all views and lights."""
+    pos = ops.f32(pos, "pos", 3).view(-1, 3)
+    if faces is None:
+        if pos.shape[0] % 3:
+            raise ValueError("an unwelded mesh takes three rows of pos per face")
+        faces = torch.arange(pos.shape[0], dtype=torch.int32, device=pos.device).view(-1, 3)
+    faces = ops.i32(faces, "faces").view(-1, 3)
+    return pos, faces, ops.face_grid(pos, faces)
+
+
+def traced_occlusion(pts, nrm, cells, shadow_grid, radius, shadow_eps=SHADOW_EPS):
+    """ops.shadow_trace of the rows pts, nrm [M, 3] against shadow_grid = (verts, faces, grid), rays starting at t0 = shadow_eps x
+    radius (of mesh_bounds) -> occl [D, ceil(M / 64)].  The rows are not compacted: an empty pixel's normal is zero, its pairs do
+    not contribute, and a wave of such rows skips the walk."""
+    shadow_eps = float(shadow_eps)
+    if not (shadow_eps >= 0.0 and math.isfinite(shadow_eps)):
+        raise ValueError("shadow_eps is finite and >= 0")
+    verts, faces, grid = shadow_grid
+    return ops.shadow_trace(pts, nrm, cells, verts, faces, grid, shadow_eps * float(radius))
+
+
 @torch.no_grad()
 def relight_mesh(pos, nrm, tan, uv, images, cells, c2w, focal, H, W, hdr=None, occlusion=True, srgb=True, fresnel=0.04, shadows=False,
-                 shadow_size=256, shadow_bias=SHADOW_BIAS, shadow_maps=None, **render_kw):
+                 shadow_size=256, shadow_bias=SHADOW_BIAS, shadow_maps=None, shadow_eps=SHADOW_EPS, shadow_grid=None, **render_kw):
     """render_mesh, then what a glTF viewer does after the texture lookups: every covered pixel's albedo, roughness and normal
     lit by the light cells (environment_cells) through albedo / pi + GGX_specular, the pixel's ray reversed as the view vector
     (ops.light_gbuffer: one pass over the G-buffer, no indirect light) -> render_mesh's dict plus "rgb" [H, W, 3].
@@ -203,14 +243,24 @@ def relight_mesh(pos, nrm, tan, uv, images, cells, c2w, focal, H, W, hdr=None, o
     shadows (default False: no shadows, every number as before): a cell lights a pixel only where the mesh does not stand between
     them, by one shadow_size x shadow_size shadow map per cell (hard shadows, nearest texel, shadow_bias = (constant,
     slope) in texels).  The pixel's surface point is the ray's origin + depth x its unit direction.  shadow_maps: the (frames,
-    maps) of shadow_maps_for(pos, cells, shadow_size), for a caller who renders many views; by default they are built here."""
+    maps) of shadow_maps_for(pos, cells, shadow_size), for a caller who renders many views; by default they are built here.
+    shadows="maps" is shadows=True.  shadows="traced" (DESIGN 4.17): no maps; one exact any-hit ray per (pixel, cell) pair from the
+    pixel's surface point towards the cell over the mesh's face grid (ops.shadow_trace), starting at t0 = shadow_eps x the radius
+    of mesh_bounds(pos); no bias in texels, no memory that grows with the cells.  shadow_grid: shadow_grid_for(pos), for a caller
+    who renders many views; by default it is built here."""
+    method = _shadow_method(shadows)
     out, gbuf = _render(pos, nrm, tan, uv, images, c2w, focal, H, W, **render_kw)
     rays = camera_rays(c2w, focal, H, W, gbuf.device)
-    if shadows:
+    if method == "maps":
         frames, maps = shadow_maps_for(pos, cells, shadow_size) if shadow_maps is None else shadow_maps
         pts = rays[:, 0:3] + out["depth"].reshape(-1, 1) * rays[:, 3:6]
         lit = ops.light_gbuffer_shadowed(gbuf.view(-1, ops.RASTER_ROW), -rays[:, 3:6], cells, pts, frames, maps, shadow_bias, fresnel,
                                          occlusion, srgb)
+    elif method == "traced":
+        sgrid = shadow_grid_for(pos) if shadow_grid is None else shadow_grid
+        pts = rays[:, 0:3] + out["depth"].reshape(-1, 1) * rays[:, 3:6]
+        occl = traced_occlusion(pts, out["normal"].reshape(-1, 3), cells, sgrid, mesh_bounds(pos)[1], shadow_eps)
+        lit = ops.light_gbuffer_occluded(gbuf.view(-1, ops.RASTER_ROW), -rays[:, 3:6], cells, occl, fresnel, occlusion, srgb)
     else:
         lit = ops.light_gbuffer(gbuf.view(-1, ops.RASTER_ROW), -rays[:, 3:6], cells, fresnel, occlusion, srgb)
     rgb = lit[:, 0:3]
@@ -223,8 +273,8 @@ def relight_mesh(pos, nrm, tan, uv, images, cells, c2w, focal, H, W, hdr=None, o
 
 def relight_glb(path, hdr, c2w, focal, H, W, rows=32, aabb=None, grid=None, device="cuda", background=True, **kw):
     """relight_mesh of a file written by mesh.export_textured under the environment hdr (array, tensor or .hdr path) reduced to
-    rows x 2 rows cells; background=False leaves the empty pixels black.  aabb, grid: as render_glb.  shadows, shadow_size,
-    shadow_bias (and everything else of relight_mesh) pass through."""
+    rows x 2 rows cells; background=False leaves the empty pixels black.  aabb, grid: as render_glb.  shadows (False, True /
+    "maps", "traced"), shadow_size, shadow_bias, shadow_eps, shadow_grid (and everything else of relight_mesh) pass through."""
     env = _environment(hdr, device)
     return relight_mesh(*load_glb(path, aabb, grid, device), environment_cells(env, rows), c2w, focal, H, W,
                         hdr=env if background else None, **kw)
@@ -256,22 +306,45 @@ def relit_psnr(gbuf_a, gbuf_b, view, cells, fresnel=0.04, images=None):
     return -10.0 * math.log10(mse) if mse > 0 else float("inf")
 
 
-def _shadow_agreement(model, relight, args, rays, field_depth, asset, both, cells, smaps, max_pixels):
-    """compare_asset's shadow_agreement of one view: rays [n, 6], field_depth [n], the asset's render dict, both [n] bool."""
+def _contributing_codes(pts, nrm, cells):
+    """ops.shadow_lookup against empty 1 x 1 maps -> codes [M, D] uint8: 2 where the pair contributes (n.L > 1e-6 exactly as the
+    lighting kernels form it), 0 elsewhere."""
+    D = cells.shape[0]
+    frames = torch.zeros((D, 12), dtype=torch.float32, device=cells.device)
+    return ops.shadow_lookup(pts, nrm, cells, frames, torch.zeros((D, 1, 1), dtype=torch.int32, device=cells.device))
+
+
+def _shadow_agreement(model, relight, args, rays, field_depth, asset, both, cells, smaps, max_pixels, traced=None):
+    """compare_asset's shadow agreements of one view: rays [n, 6], field_depth [n], the asset's render dict, both [n] bool; smaps
+    = (frames, maps) or None; traced = (shadow_grid, radius, shadow_eps) or None -> {"maps": maps vs. field, "traced": traced vs.
+    field, "maps_traced": maps vs. traced} for what was asked, each over the pairs that contribute on the asset side."""
+    names = (("maps",) if smaps is not None else ()) + (("traced",) if traced is not None else ()) + \
+            (("maps_traced",) if smaps is not None and traced is not None else ())
     idx = torch.nonzero(both).reshape(-1)
     if idx.numel() == 0:
-        return float("nan")
+        return {k: float("nan") for k in names}
     idx = idx[::max(1, -(-idx.numel() // max(max_pixels, 1)))]                  # a fixed stride: no random numbers
     o, d = rays[idx, 0:3], rays[idx, 3:6]
     D = cells.shape[0]
-    codes = ops.shadow_lookup(o + asset["depth"].reshape(-1, 1)[idx] * d, asset["normal"].reshape(-1, 3)[idx], cells, *smaps, SHADOW_BIAS)
+    apts, anrm = o + asset["depth"].reshape(-1, 1)[idx] * d, asset["normal"].reshape(-1, 3)[idx]
+    codes = ops.shadow_lookup(apts, anrm, cells, *smaps, SHADOW_BIAS) if smaps is not None else _contributing_codes(apts, anrm, cells)
     pts = (o + field_depth.reshape(-1, 1)[idx] * d).repeat_interleave(D, dim=0)
     L = torch.nn.functional.normalize(cells[:, 0:3], dim=-1).repeat(idx.numel(), 1)
     vis = relight.compute_transmittance(model, pts, L, nSample=args.second_nSample, vis_near=args.second_near, vis_far=args.second_far)[0]
     field_lit = vis.reshape(idx.numel(), D) > 0.5
     on = codes != 0
     n = int(on.sum())
-    return float(((codes == 2) == field_lit)[on].sum()) / n if n else float("nan")
+    share = lambda a, b: float((a == b)[on].sum()) / n if n else float("nan")
+    out = {}
+    if smaps is not None:
+        out["maps"] = share(codes == 2, field_lit)
+    if traced is not None:
+        sgrid, radius, eps = traced
+        traced_lit = ~ops.occlusion_bits(traced_occlusion(apts, anrm, cells, sgrid, radius, eps), idx.numel())
+        out["traced"] = share(traced_lit, field_lit)
+        if smaps is not None:
+            out["maps_traced"] = share(codes == 2, traced_lit)
+    return out
 
 
 def _write_view(path, rgb):
@@ -287,7 +360,7 @@ def _mean(values):
 
 @torch.no_grad()
 def compare_asset(model, path, cameras=None, H=200, W=200, focal=None, n_views=8, grid=None, args=None, chunk=16384, light=None,
-                  light_rows=16, write_views=None, shadows=False, shadow_size=256, shadow_pixels=4096, ssim=False):
+                  light_rows=16, write_views=None, shadows=False, shadow_size=256, shadow_pixels=4096, ssim=False, shadow_eps=SHADOW_EPS):
     """Render the field (Renderer_TensoIR_train under its own first light -- no novel illumination --, no white background,
     `chunk` rays per call) and the asset at `path` (render_glb, mapped to field coordinates with the lattice `grid`, default the
     model's gridSize) from the same cameras.  The renderer decodes albedo, roughness and normals only with is_relight=True, which
@@ -316,11 +389,18 @@ def compare_asset(model, path, cameras=None, H=200, W=200, focal=None, n_views=8
                       second_near, second_far) > 0.5 means lit.  Counted over the pairs that contribute on the asset side (n.L >
                       1e-6); nan when there are none.  Every other number is what it is without shadows: relit_psnr stays the
                       unshadowed comparison.
+    shadows="maps" is shadows=True.  shadows="traced"  makes shadow_agreement the TRACED visibility of the asset
+    (ops.shadow_trace over its face grid, rays from t0 = shadow_eps x the radius of mesh_bounds) against the same march of the
+    field: the same pixels, the same field side, the same definition.  shadows="both" reports
+      shadow_agreement         the maps against the field: the number of shadows=True, bit for bit
+      shadow_agreement_traced  the traced visibility against the field
+      shadow_map_agreement     the maps against the traced visibility, over the pairs that contribute on the asset side: what the
+                      shadow map's bias and aliasing cost, free of the field
     ssim (default False: the report is exactly the one above) adds
       albedo_ssim     metrics.ssim (the reference's rgb_ssim, max_val 1) of the field's albedo_map against the asset's albedo over
                       the whole frame, both set to 0 outside the pixels in both silhouettes: the one structural number of the report
     write_views (a directory, with light): every view's two images as view_KK_field.png / view_KK_asset.png, and with shadows
-    the asset under its own shadows as view_KK_asset_shadowed.png.
+    the asset under its own shadows as view_KK_asset_shadowed.png (maps) and view_KK_asset_traced.png (traced).
     cameras: [n, 3, 4]; default orbit_cameras(model.aabb, n_views) at the middle of the model's near / far range, with a focal
     length that fits the box into 90 % of the image."""
     import types
@@ -345,12 +425,18 @@ def compare_asset(model, path, cameras=None, H=200, W=200, focal=None, n_views=8
         if light is None:
             raise ValueError("write_views writes the lit images: it needs light")
         os.makedirs(write_views, exist_ok=True)
-    smaps = None
-    if shadows:
+    smaps = traced = None
+    method = _shadow_method(shadows, ("both",))
+    if method is not None:
         if cells is None:
             raise ValueError("shadows compares the shadows of a light: it needs light")
         from . import relight
-        smaps = shadow_maps_for(asset[0], cells, shadow_size)
+        if method in ("maps", "both"):
+            smaps = shadow_maps_for(asset[0], cells, shadow_size)
+        if method in ("traced", "both"):
+            traced = (shadow_grid_for(asset[0]), mesh_bounds(asset[0])[1], shadow_eps)
+    skeys = {"maps": (("shadow_agreement", "maps"),), "traced": (("shadow_agreement", "traced"),),
+             "both": (("shadow_agreement", "maps"), ("shadow_agreement_traced", "traced"), ("shadow_map_agreement", "maps_traced"))}.get(method, ())
     views = []
     for k, c2w in enumerate(cameras):
         rays = camera_rays(c2w, focal, H, W, dev)
@@ -388,16 +474,23 @@ def compare_asset(model, path, cameras=None, H=200, W=200, focal=None, n_views=8
             if write_views is not None:
                 for name, img in zip(("field", "asset"), lit):
                     _write_view(os.path.join(write_views, f"view_{k:02d}_{name}.png"), img.reshape(H, W, 3))
-        if smaps is not None:
-            v["shadow_agreement"] = _shadow_agreement(model, relight, args, rays, ret["depth_map"].reshape(-1), a, both.reshape(-1), cells,
-                                                      smaps, int(shadow_pixels))
+        if method is not None:
+            agree = _shadow_agreement(model, relight, args, rays, ret["depth_map"].reshape(-1), a, both.reshape(-1), cells, smaps,
+                                      int(shadow_pixels), traced)
+            v.update({name: agree[which] for name, which in skeys})
             if write_views is not None:
                 pts = rays[:, 0:3] + a["depth"].reshape(-1, 1) * rays[:, 3:6]
-                img = ops.light_gbuffer_shadowed(gbuf.view(-1, ops.RASTER_ROW), (-rays[:, 3:6]).contiguous(), cells, pts, *smaps, SHADOW_BIAS,
-                                                 float(model.fixed_fresnel), False, True)
-                _write_view(os.path.join(write_views, f"view_{k:02d}_asset_shadowed.png"), img[:, 0:3].reshape(H, W, 3))
+                view = (-rays[:, 3:6]).contiguous()
+                if smaps is not None:
+                    img = ops.light_gbuffer_shadowed(gbuf.view(-1, ops.RASTER_ROW), view, cells, pts, *smaps, SHADOW_BIAS,
+                                                     float(model.fixed_fresnel), False, True)
+                    _write_view(os.path.join(write_views, f"view_{k:02d}_asset_shadowed.png"), img[:, 0:3].reshape(H, W, 3))
+                if traced is not None:
+                    occl = traced_occlusion(pts, a["normal"].reshape(-1, 3), cells, *traced)
+                    img = ops.light_gbuffer_occluded(gbuf.view(-1, ops.RASTER_ROW), view, cells, occl, float(model.fixed_fresnel), False, True)
+                    _write_view(os.path.join(write_views, f"view_{k:02d}_asset_traced.png"), img[:, 0:3].reshape(H, W, 3))
         views.append(v)
     keys = ("iou", "pixels", "albedo_psnr", "roughness_rmse", "normal_deg", "depth_rmse") + (() if cells is None else ("relit_psnr",)) + \
-           (() if smaps is None else ("shadow_agreement",)) + (("albedo_ssim",) if ssim else ())
+           tuple(name for name, _ in skeys) + (("albedo_ssim",) if ssim else ())
     mean = {k: _mean([v[k] for v in views if math.isfinite(v[k])]) for k in keys}
     return {"views": views, "mean": mean, "H": int(H), "W": int(W), "focal": float(focal), "n_views": len(views)}
