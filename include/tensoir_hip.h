@@ -15,6 +15,12 @@
  *   - fp32 I/O, int32 indices, int64 sizes.  Return 0 on success, a negative TIR_ERR_* /
  *     -(hipError_t) on failure; nothing throws across the ABI.
  *   - re-entrant; no internal threads.
+ *
+ * The Python binding (tensoir_amd/_lib.py) is generated from this file at import: the `typedef struct X { ... } X;` blocks, the
+ * prototypes and the `#define TIR_NAME value` lines (an integer, a floating literal without suffix or a parenthesised quotient of
+ * two; other macros are not published).  Its parser reads plain declarations only and refuses the rest, so keep to these type
+ * names: int, int32_t, int64_t, uint64_t, float, double and the structs by value; void, char, unsigned, unsigned long long, uint8_t,
+ * uint16_t, uint32_t behind a pointer.  Parameters are named, no function pointers, no #if beyond the guard and __cplusplus.
  */
 #ifndef TENSOIR_HIP_H
 #define TENSOIR_HIP_H

@@ -1,4 +1,4 @@
-"""ctypes binding of libtensoir_hip.so (the C ABI declared in include/tensoir_hip.h).
+"""ctypes binding of libtensoir_hip.so, derived at import from include/tensoir_hip.h (the one statement of the C ABI).
 
 There is NO fallback: if the shared library is missing or cannot be loaded the import of any
 product entry point raises.  Built in-tree by ``tensoir_amd/csrc/build.sh`` (``__graft_entry__.build``).
@@ -7,214 +7,116 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TENSOIR_HIP_LIB", os.path.join(_HERE, "libtensoir_hip.so"))
-
-c_float_p = C.c_void_p   # device pointers are passed as integers
-c_int_p = C.c_void_p
-
-
-class TirField(C.Structure):
-    _fields_ = [
-        ("aabb_min", C.c_float * 3), ("aabb_max", C.c_float * 3), ("inv_aabb", C.c_float * 3),
-        ("grid", C.c_int32 * 3),
-        ("step_size", C.c_float), ("distance_scale", C.c_float), ("density_shift", C.c_float),
-        ("weight_thres", C.c_float), ("near_", C.c_float), ("far_", C.c_float),
-        ("act", C.c_int32), ("n_dcomp", C.c_int32), ("n_acomp", C.c_int32), ("app_dim", C.c_int32),
-        ("n_lights", C.c_int32),
-        ("dplane", C.c_void_p * 3), ("dline", C.c_void_p * 3),
-        ("aplane", C.c_void_p * 3), ("aline", C.c_void_p * 3),
-        ("basis_t", C.c_void_p), ("light_line", C.c_void_p), ("light_mean", C.c_void_p),
-        ("occ_nbr", C.c_void_p),
-        ("occ_dim", C.c_int32 * 3), ("occ_aabb_min", C.c_float * 3), ("occ_inv", C.c_float * 3),
-        ("occ_lo", C.c_float * 3), ("occ_hi", C.c_float * 3),
-        ("tune_lds_lines", C.c_int32), ("tune_xcd_order", C.c_int32),
-        ("dense_sigma", C.c_void_p), ("dense_pitch", C.c_int32),
-        ("dense_app_pitch", C.c_int32), ("dense_app", C.c_void_p),
-    ]
-
-
-class TirFieldHalf(C.Structure):
-    _fields_ = [("aplane", C.c_void_p * 3), ("aline", C.c_void_p * 3)]
-
-
-class TirFieldGrad(C.Structure):
-    _fields_ = [("dplane", C.c_void_p * 3), ("dline", C.c_void_p * 3), ("aplane", C.c_void_p * 3),
-                ("aline", C.c_void_p * 3), ("light_line", C.c_void_p), ("light_mean", C.c_void_p)]
-
-
-class TirMlp(C.Structure):
-    _fields_ = [("packed", C.c_void_p), ("feat_dim", C.c_int32), ("pe", C.c_int32),
-                ("hidden", C.c_int32), ("out_dim", C.c_int32), ("act", C.c_int32), ("tune_grid", C.c_int32)]
-
-
-class TirEnvSG(C.Structure):
-    _fields_ = [("sgs", C.c_void_p), ("rot", C.c_void_p), ("n_sg", C.c_int32), ("n_lights", C.c_int32)]
-
-
-P = C.c_void_p
-I32 = C.c_int32
-I64 = C.c_int64
-F32 = C.c_float
-
-# name -> (restype, argtypes); mirrors include/tensoir_hip.h one to one
-SIGNATURES = {
-    "tir_version": (C.c_int, []),
-    "tir_error_string": (C.c_char_p, [C.c_int]),
-    "tir_device_check": (C.c_int, []),
-    "tir_pack_plane": (C.c_int, [P, P, I32, I32, I32, P]),
-    "tir_pack_occupancy": (C.c_int, [P, P, I32, I32, I32, P]),
-    "tir_pack_basis": (C.c_int, [P, P, I32, I32, P]),
-    "tir_light_mean": (C.c_int, [P, P, I32, I32, P]),
-    "tir_mlp_packed_floats": (I64, [I32, I32, I32, I32]),
-    "tir_pack_mlp": (C.c_int, [P, P, P, P, P, P, I32, I32, I32, I32, P, P]),
-    "tir_vm_density_fwd": (C.c_int, [C.POINTER(TirField), P, P, P, I64, P]),
-    "tir_occupancy_query": (C.c_int, [C.POINTER(TirField), P, P, I64, P]),
-    "tir_dense_alpha": (C.c_int, [C.POINTER(TirField), P, P, P, I32, I32, I32, F32, P, P]),
-    "tir_alpha_pool": (C.c_int, [P, I32, I32, I32, F32, P, P, P]),
-    "tir_filter_rays": (C.c_int, [C.POINTER(TirField), P, I64, I32, I32, P, P]),
-    "tir_dense_sigma_build": (C.c_int, [C.POINTER(TirField), P, I32, P]),
-    "tir_dense_sigma_fwd": (C.c_int, [C.POINTER(TirField), P, P, P, I64, P]),
-    "tir_dense_app_build": (C.c_int, [C.POINTER(TirField), P, I32, P]),
-    "tir_density_grad_fwd": (C.c_int, [C.POINTER(TirField), P, P, P, P, I64, P, P]),
-    "tir_density_feat_grad_fwd": (C.c_int, [C.POINTER(TirField), P, P, P, I64, P]),
-    "tir_vm_app_fwd": (C.c_int, [C.POINTER(TirField), P, P, P, P, P, I32, I32, I64, P, P]),
-    "tir_vm_app_fwd_bf16x3": (C.c_int, [C.POINTER(TirField), P, P, P, P, P, I32, I32, I64, P, P]),
-    "tir_vm_app_fwd_x3": (C.c_int, [C.POINTER(TirField), P, P, P, P, P, I32, I32, I64, P, P]),
-    "tir_pack_half": (C.c_int, [P, P, P, I32, P]),
-    "tir_pack_half_checked": (C.c_int, [P, P, P, I32, P, P]),
-    "tir_vm_app_fwd_h16": (C.c_int, [C.POINTER(TirField), C.POINTER(TirFieldHalf), P, P, P, P, I32, I32, I64, P, P]),
-    "tir_indirect_fused_fwd": (C.c_int, [C.POINTER(TirField), C.POINTER(TirFieldHalf), C.POINTER(TirMlp), P, P, P, I32, I32, P, P, I64, P, P]),
-    "tir_indirect_fused_hp_fwd": (C.c_int, [C.POINTER(TirField), C.POINTER(TirMlp), P, P, P, I32, I32, P, P, I64, P, P]),
-    "tir_vm_app_fwd_valu": (C.c_int, [C.POINTER(TirField), P, P, P, P, P, I32, I32, I64, P, P]),
-    "tir_mlp_fwd": (C.c_int, [C.POINTER(TirMlp), P, I32, P, P, I32, P, I64, P, P]),
-    "tir_mlp_fwd_bf16x3": (C.c_int, [C.POINTER(TirMlp), P, I32, P, P, I32, P, I64, P, P]),
-    "tir_mlp_fwd_multi_bf16x3": (C.c_int, [P, P, I32, P, P, P, I32, I64, P, P]),
-    "tir_mlp_fwd_multi_auxtab_bf16x3": (C.c_int, [P, P, I32, P, P, P, P, I32, I64, P, P]),
-    "tir_mlp_aux_table": (C.c_int, [C.POINTER(TirMlp), P, I64, P, P]),
-    "tir_mlp_fwd_auxtab_bf16x3": (C.c_int, [C.POINTER(TirMlp), P, I32, P, P, I32, P, I64, P, P]),
-    "tir_mlp_fwd_auxtab_f16": (C.c_int, [C.POINTER(TirMlp), P, I32, P, P, I32, P, I64, P, P]),
-    "tir_mlp_train_fwd_auxtab_bf16x3": (C.c_int, [C.POINTER(TirMlp), P, I32, P, P, I32, P, P, P, I64, P, P]),
-    "tir_mlp_train_fwd_multi_bf16x3": (C.c_int, [P, P, I32, P, P, P, P, P, I32, I64, P, P]),
-    "tir_mlp_fwd_bf16": (C.c_int, [C.POINTER(TirMlp), P, I32, P, P, I32, P, I64, P, P]),
-    "tir_mlp_fwd_valu": (C.c_int, [C.POINTER(TirMlp), P, I32, P, P, I32, P, I64, P, P]),
-    "tir_march_primary_fwd": (C.c_int, [C.POINTER(TirField), P, P, I32, I32, F32, P, P, P, P, P, P, P]),
-    "tir_exclusive_scan": (C.c_int, [P, P, I32, P]),
-    "tir_exclusive_scan_capped": (C.c_int, [P, P, I32, I32, P, P]),
-    "tir_march_primary_fused_fwd": (C.c_int, [C.POINTER(TirField), P, P, I32, I32, F32, P, P, P, P, P, P,
-                                              P, P, I32, P, P, I32, P, P]),
-    "tir_composite_primary_fused": (C.c_int, [P, P, P, P, P, P, P, P, P, P, I32, I32, I32, F32, P, P, P, P, I64, P]),
-    "tir_vm_app_jitter_fwd": (C.c_int, [C.POINTER(TirField), P, I64, P, F32, C.c_uint64, C.c_uint64, P, P, P, I32, P]),
-    "tir_vm_app_primary_fwd": (C.c_int, [C.POINTER(TirField), P, P, P, P, P, I32, I64, P, F32, C.c_uint64, C.c_uint64, P, P, P, P]),
-    "tir_vm_app_primary_x3_fwd": (C.c_int, [C.POINTER(TirField), P, P, P, P, P, I32, I64, P, F32, C.c_uint64, C.c_uint64, P, P, P, P]),
-    "tir_compact_primary": (C.c_int, [C.POINTER(TirField), P, P, P, P, I32, I32, P, P, P, P, P]),
-    "tir_composite_primary": (C.c_int, [P, P, P, P, P, P, P, P, P, P, I32, I32, I32, F32, P, P]),
-    "tir_march_secondary_fwd": (C.c_int, [C.POINTER(TirField), P, P, P, P, P, I64, I32, I32, P, F32, P, P,
-                                          P, I64, P, P, P, P, P, P, P]),
-    "tir_accumulate_records": (C.c_int, [P, P, P, P, I64, P, P]),
-    "tir_env_sg_fwd": (C.c_int, [C.POINTER(TirEnvSG), P, I32, P, P]),
-    "tir_env_pixel_fwd": (C.c_int, [P, I32, I32, P, P, I32, I64, I32, P, P]),
-    "tir_env_pixel_bwd": (C.c_int, [P, I32, I32, P, P, I32, I64, P, P, P]),
-    "tir_shade_setup": (C.c_int, [P, P, P, I32, I32, F32, P, P, P]),
-    "tir_shade_integrate": (C.c_int, [P, P, P, P, P, P, P, P, I32, I32, I32, I32, I32, F32, P, P]),
-    "tir_shade_integrate_records": (C.c_int, [P, P, P, P, P, P, P, P, P, P, P, I32, I32, I32, I32, I32, F32, P, P, P]),
-    "tir_shade_setup_compact": (C.c_int, [P, P, P, I32, I32, F32, P, P, P, P, P, P, I32, P]),
-    "tir_march_secondary_ids_fwd": (C.c_int, [C.POINTER(TirField), P, P, P, P, P, I64, I32, I32, P, F32, P, P,
-                                              P, I64, P, P, P, P, P, P, P, P, P]),
-    "tir_relight_importance": (C.c_int, [P, P, P, P, P, P, P, P, P, I32, I32, P, P]),
-    "tir_env_sample_setup": (C.c_int, [P, P, I32, I32, P, P, I32, I32, C.c_uint64, C.c_uint64, P, P, P]),
-    "tir_env_sample_setup_list": (C.c_int, [P, P, I32, I32, P, I32, P, I32, I32, C.c_uint64, C.c_uint64, I32, I32, I32, P, P, I32, I32, P, P, P, P, P]),
-    "tir_relight_importance_cells": (C.c_int, [P, P, P, P, P, P, P, P, P, P, I32, I32, P, P]),
-    "tir_relight_importance_cells_packed": (C.c_int, [P, P, P, P, P, P, P, P, I32, I32, P, P]),
-    "tir_env_lookup": (C.c_int, [P, I32, I32, P, I64, P, P]),
-    "tir_surface_compact": (C.c_int, [P, P, I32, C.c_float, P, P, P, P, P, P, P, P, P]),
-    "tir_env_sample_setup_list_n": (C.c_int, [P, P, I32, I32, P, I32, P, I32, I32, C.c_uint64, C.c_uint64, I32, I32, I32, P, P, I32, I32, P, P, P, P, P, P]),
-    "tir_relight_importance_cells_packed_n": (C.c_int, [P, P, P, P, P, P, P, P, I32, I32, P, P, P]),
-    "tir_env_compose": (C.c_int, [P, I32, I32, P, I32, I64, P, P, P, I32, P]),
-    "tir_env_mis_setup": (C.c_int, [P, P, I32, I32, P, I32, P, P, P, P, P, I32, I32, I32, F32, C.c_uint64, C.c_uint64, I32, P, P, I32, I32,
-                                    P, P, P, P, P, P, P, P]),
-    "tir_relight_mis": (C.c_int, [P, P, P, P, P, P, P, P, P, P, I32, I32, I32, P, P, P]),
-    "tir_ggx_specular": (C.c_int, [P, P, P, P, P, I32, I32, P, P]),
-    # ---- training (backward) entry points ----
-    "tir_march_primary_train_fwd": (C.c_int, [C.POINTER(TirField), P, P, I32, I32, F32, P, P, P, P, P, P, P]),
-    "tir_composite_primary_bwd": (C.c_int, [P] * 11 + [I32, I32, I32, I32, F32] + [P] * 9 + [P]),
-    "tir_march_primary_bwd": (C.c_int, [C.POINTER(TirField), C.POINTER(TirFieldGrad), P, P, I32, I32, P, P, P, P, P, P, P]),
-    "tir_density_grad_bwd": (C.c_int, [C.POINTER(TirField), C.POINTER(TirFieldGrad), P, P, I64, P]),
-    # per-point density backward (tensoir_amd/pointwise.py)
-    "tir_vm_density_bwd": (C.c_int, [C.POINTER(TirField), C.POINTER(TirFieldGrad), P, P, I64, P]),
-    "tir_density_feat_bwd": (C.c_int, [C.POINTER(TirField), C.POINTER(TirFieldGrad), P, P, P, I64, P]),
-    "tir_density_feat_grad_bwd": (C.c_int, [C.POINTER(TirField), C.POINTER(TirFieldGrad), P, P, P, I64, P]),
-    "tir_vm_app_bwd": (C.c_int, [C.POINTER(TirField), C.POINTER(TirFieldGrad), P, P, P, P, P, I32, I64, P, P, P]),
-    "tir_mlp_train_fwd": (C.c_int, [C.POINTER(TirMlp), P, I32, P, P, I32, P, P, P, I64, P, P]),
-    "tir_mlp_train_fwd_bf16x3": (C.c_int, [C.POINTER(TirMlp), P, I32, P, P, I32, P, P, P, I64, P, P]),
-    "tir_mlp_inputs": (C.c_int, [C.POINTER(TirMlp), P, I32, P, P, I32, P, I64, P]),
-    "tir_mlp_bwd_packed_floats": (I64, [I32, I32, I32, I32]),
-    "tir_pack_mlp_bwd": (C.c_int, [P, P, P, I32, I32, I32, I32, P, P]),
-    "tir_mlp_bwd": (C.c_int, [C.POINTER(TirMlp), P, P, I32, P, P, P, P, I64, P, P, P, P, P]),
-    "tir_mlp_bwd_bf16x3": (C.c_int, [C.POINTER(TirMlp), P, P, I32, P, P, P, P, I64, P, P, P, P, P]),
-    "tir_mlp_bwd_multi_bf16x3": (C.c_int, [P, P, P, I32, P, P, P, P, I32, I64, P, P, P, P, P]),
-    "tir_gemm_tn_small_bf16x3": (C.c_int, [P, I32, I32, P, I32, I32, I32, I64, P, I32, P]),
-    "tir_mlp_wgrad_multi": (C.c_int, [P, P, P, P, P, P, I32, P, P, P, P, P, P, P, P, I32, I64, I32, P]),
-    "tir_record_check": (C.c_int, [P, P, I32, P, P, P]),
-    "tir_adam_step": (C.c_int, [I32, P, P, P, P, P, P, P, P, F32, F32, F32, P]),
-    "tir_gemm_tn": (C.c_int, [P, I32, I32, P, I32, I32, I32, I64, P, I32, P, P]),
-    "tir_gemm_tn_bf16x3": (C.c_int, [P, I32, I32, P, I32, I32, I32, I64, P, I32, P, P]),
-    "tir_shade_integrate_bwd": (C.c_int, [P, P, P, P, P, P, P, P, I32, I32, I32, I32, I32, F32, P, P, P, P]),
-    "tir_env_sg_bwd": (C.c_int, [C.POINTER(TirEnvSG), P, I32, P, P, P]),
-    "tir_mc_blocks": (I64, [I32, I32, I32]),
-    "tir_mc_count": (C.c_int, [P, I32, I32, I32, F32, P, P, P]),
-    "tir_mc_emit": (C.c_int, [P, I32, I32, I32, F32, F32, F32, F32, F32, F32, F32, P, I32, I32, P, P, P, P, P]),
-    "tir_ccl_blocks": (I64, [I32, I32, I32]),
-    "tir_ccl_label": (C.c_int, [P, I32, I32, I32, F32, I32, P, P, P, P]),
-    "tir_ccl_table": (C.c_int, [P, I32, I32, I32, P, I32, P, P, P, P]),
-    "tir_ccl_filter": (C.c_int, [P, P, I32, I32, I32, F32, P, P, I32, F32, P, P]),
-    "tir_simplify_blocks": (I64, [I64]),
-    "tir_simplify_count": (C.c_int, [P, I64, P, I64, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(I32), P, P, P, P, P, P]),
-    "tir_simplify_emit": (C.c_int, [P, I64, P, I64, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(I32), C.c_double, P, P,
-                                    I32, I32, P, P, P, P, P, P]),
-    "tir_distance_blocks": (I64, [I64]),
-    "tir_mesh_sample_cdf": (C.c_int, [P, I64, P, I64, P, P, P, P]),
-    "tir_mesh_sample": (C.c_int, [P, I64, P, I64, P, I64, C.c_uint64, P, P, P]),
-    "tir_face_grid_count": (C.c_int, [P, I64, P, I64, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(I32), P, P]),
-    "tir_face_grid_fill": (C.c_int, [P, I64, P, I64, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(I32), I64, P, P, P, P, P]),
-    "tir_point_mesh_distance": (C.c_int, [P, I64, P, I64, P, I64, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(I32), P, P,
-                                          I64, P, P, P, P, P]),
-    "tir_ray_mesh": (C.c_int, [P, P, P, I64, P, I64, P, I64, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(I32), P, P, I64, P,
-                               C.c_int, P, P, P, P, P, P, P]),
-    "tir_shadow_trace": (C.c_int, [P, P, P, I64, I32, P, I64, P, I64, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(I32), P, P,
-                                   I64, P, F32, P, P]),
-    "tir_bake_composite": (C.c_int, [P, P, P, P, P, P, P, P, P, C.POINTER(C.c_float), I64, I64, P, P]),
-    "tir_irradiance_integrate": (C.c_int, [P, P, P, P, P, P, I64, I32, I32, P, P]),
-    "tir_atlas_corners": (C.c_int, [P, I64, P, P, I64, I32, I32, I32, P, P, P, P, P, P]),
-    "tir_atlas_texels": (C.c_int, [P, I64, P, P, I64, I32, I32, I32, P, P, P, P, P]),
-    "tir_atlas_pack": (C.c_int, [P, I64, P, P, I64, I32, I32, I32, P, P, P, P, P, P, P, P, P, P, P]),
-    "tir_raster_project": (C.c_int, [P, I64, P, I64, C.POINTER(C.c_float), F32, I32, I32, F32, P, P, P]),
-    "tir_raster_cover": (C.c_int, [P, I64, I32, I32, I32, P, P, P]),
-    "tir_raster_resolve": (C.c_int, [P, I64, P, I32, I32, P, P]),
-    "tir_raster_shade": (C.c_int, [P, I64, P, P, P, P, P, P, I32, I32, I32, I32, P, P]),
-    "tir_env_cells": (C.c_int, [P, I32, I32, P, I32, I32, P, P]),
-    "tir_light_gbuffer": (C.c_int, [P, P, P, I64, I32, F32, I32, P, P]),
-    "tir_shadow_maps": (C.c_int, [P, I64, P, I64, P, I32, I32, P, P, I32, P, P]),
-    "tir_shadow_lookup": (C.c_int, [P, P, P, P, P, I64, I32, I32, F32, F32, P, P]),
-    "tir_light_gbuffer_shadowed": (C.c_int, [P, P, P, P, P, P, I64, I32, I32, F32, F32, F32, I32, P, P]),
-    "tir_light_gbuffer_occluded": (C.c_int, [P, P, P, P, I64, I64, I32, F32, I32, P, P]),
-    "tir_ssim_workspace": (I64, [I64, I32, I32, I32, I32]),
-    "tir_ssim": (C.c_int, [P, P, I64, I32, I32, I32, P, I32, C.c_double, C.c_double, P, P, P, P]),
-    "tir_image_error_workspace": (I64, [I64, I64]),
-    "tir_image_error": (C.c_int, [P, P, P, I64, I64, I32, I32, P, P, P]),
-    "tir_tv_workspace": (I64, [I32, P, P, P]),
-    "tir_tv_fwd": (C.c_int, [P, P, P, P, P, I32, P, P, P, P]),
-    "tir_tv_bwd": (C.c_int, [P, P, P, P, P, I32, P, P, P]),
-    "tir_denoise_guide": (C.c_int, [P, P, I64, F32, P, I64, P]),
-    "tir_atrous_level": (C.c_int, [P, P, P, I32, I32, I32, I32, F32, F32, F32, F32, F32, P]),
-}
-
-_lib = None
+HEADER_PATH = os.environ.get("TENSOIR_HIP_HEADER", os.path.join(os.path.dirname(_HERE), "include", "tensoir_hip.h"))
 
 
 class TensoirHipError(RuntimeError):
     pass
+
+
+# ---- the header parser: exactly the C subset include/tensoir_hip.h uses (its top comment lists it); anything else raises ----
+_SCALARS = {"int": C.c_int, "int32_t": C.c_int32, "int64_t": C.c_int64, "uint64_t": C.c_uint64, "float": C.c_float,
+            "double": C.c_double}
+_POINTEES = {"void", "char", "unsigned", "unsigned long long", "uint8_t", "uint16_t", "uint32_t", *_SCALARS}   # + the structs
+_INT, _FLT = r"-?(?:0[xX][0-9a-fA-F]+|[1-9]\d*|0)", r"-?(?:\d+\.\d*|\.\d+)(?:[eE][+-]?\d+)?"
+_DEFINE = re.compile(rf"^#\s*define\s+(TIR_\w+)\s+(?:({_INT})|({_FLT})|\(\s*({_FLT})\s*/\s*({_FLT})\s*\))\s*$")
+_STRUCT = re.compile(r"typedef\s+struct\s+(\w+)\s*\{([^{}]*)\}\s*(\w+)\s*;")
+_PROTO = re.compile(r"([\w\s*]+?)\b(\w+)\s*\(([^()]*)\)")
+_DECL = re.compile(r"\s*(?:const\s+)?(unsigned\s+long\s+long\b|[A-Za-z_]\w*)\s*(.*)", re.S)            # base type, declarators
+_DECLARATOR = re.compile(r"\s*((?:\*\s*(?:const\s*)?)*)([A-Za-z_]\w*)\s*(?:\[\s*(\w+)\s*\])?\s*")   # stars, name, [length]
+
+
+def _declarators(text, structs, const):
+    """`const float* a[3], b` -> [("a", "float", 1, 3), ("b", "float", 0, None)]: name, base type, pointer depth, array length."""
+    m = _DECL.fullmatch(text)
+    base = " ".join(m.group(1).split()) if m else ""
+    if base not in _POINTEES and base not in structs:
+        raise TensoirHipError(f"{HEADER_PATH}: unknown type in `{text.strip()}`")
+    out = []
+    for d in m.group(2).split(","):
+        m = _DECLARATOR.fullmatch(d)
+        if not m:
+            raise TensoirHipError(f"{HEADER_PATH}: cannot read the declarator `{d.strip()}` of `{text.strip()}`")
+        length = m.group(3)
+        if length is not None:
+            length = int(length) if length.isdigit() else const.get(length)
+            if not isinstance(length, int):
+                raise TensoirHipError(f"{HEADER_PATH}: array length of `{text.strip()}` is neither a number nor an integer macro")
+        out.append((m.group(2), base, m.group(1).count("*"), length))
+    return out
+
+
+def _value_type(base, text, structs):
+    if base in _SCALARS:
+        return _SCALARS[base]
+    if base in structs:
+        return structs[base]
+    raise TensoirHipError(f"{HEADER_PATH}: `{base}` cannot be passed or stored by value in `{text.strip()}`")
+
+
+def parse_header(src):
+    """-> (CONST, STRUCTS, SIGNATURES) of a header text.  Raises TensoirHipError on anything outside the subset; never guesses."""
+    src = re.sub(r"/\*.*?\*/", " ", src, flags=re.S).replace("\\\n", " ")
+    src = re.sub(r"^#\s*ifdef __cplusplus\n.*?^#\s*endif[^\n]*$", "", src, flags=re.S | re.M)      # we read the header as C
+    const, code = {}, []
+    for line in src.split("\n"):
+        if not line.lstrip().startswith("#"):
+            code.append(line)
+            continue
+        line = line.strip()
+        if not re.match(r"#\s*(define|include|ifndef \w+_H|endif)\b", line):
+            raise TensoirHipError(f"{HEADER_PATH}: preprocessor line `{line}` is outside the subset the binding reads")
+        m = _DEFINE.match(line)
+        if m:                                            # macros of any other shape (brace lists, the include guard) are skipped
+            name, i, f, num, den = m.groups()
+            const[name] = int(i, 0) if i else float(f) if f else float(num) / float(den)
+    code = "\n".join(code)
+    structs = {}
+    for m in _STRUCT.finditer(code):
+        if m.group(1) != m.group(3):
+            raise TensoirHipError(f"{HEADER_PATH}: struct {m.group(1)} is typedef'd as {m.group(3)}")
+        fields = []
+        for decl in filter(str.strip, m.group(2).split(";")):
+            for name, base, stars, length in _declarators(decl, structs, const):
+                t = C.c_void_p if stars else _value_type(base, decl, structs)
+                fields.append((name, t if length is None else t * length))
+        structs[m.group(1)] = type(m.group(1), (C.Structure,), {"_fields_": fields})
+    sigs = {}
+    for stmt in filter(str.strip, _STRUCT.sub("", code).split(";")):
+        m = _PROTO.fullmatch(stmt.strip())
+        if not m:
+            raise TensoirHipError(f"{HEADER_PATH}: cannot read `{' '.join(stmt.split())}` as a prototype")
+        ret, name, params = m.groups()
+        types = []
+        for text in [ret + name] + ([] if params.strip() in ("", "void") else params.split(",")):
+            (_, base, stars, length), = _declarators(text, structs, const)
+            if length is not None:
+                raise TensoirHipError(f"{HEADER_PATH}: array parameter `{text.strip()}` of {name}")
+            if stars == 1 and base in structs:
+                types.append(C.POINTER(structs[base]))   # a TirMlp cannot be passed where a TirField belongs
+            elif stars:
+                types.append(C.c_char_p if base == "char" and not types else C.c_void_p)
+            elif base == "void" and not types:
+                types.append(None)
+            else:
+                types.append(_value_type(base, text, structs))
+        sigs[name] = (types[0], types[1:])
+    return const, structs, sigs
+
+
+if not os.path.exists(HEADER_PATH):
+    raise TensoirHipError(f"{HEADER_PATH} not found: the ctypes binding is derived from the C header (TENSOIR_HIP_HEADER overrides "
+                          "the path)")
+with open(HEADER_PATH) as _f:
+    CONST, STRUCTS, SIGNATURES = parse_header(_f.read())     # name -> int | float, name -> Structure, name -> (restype, argtypes)
+TirField, TirFieldHalf, TirFieldGrad, TirMlp, TirEnvSG = (STRUCTS[n] for n in ("TirField", "TirFieldHalf", "TirFieldGrad", "TirMlp",
+                                                                               "TirEnvSG"))
+
+_lib = None
 
 
 def lib():

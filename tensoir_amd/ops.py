@@ -15,7 +15,8 @@ import torch
 from . import _lib
 from ._lib import TirEnvSG, TirField, TirFieldHalf, TirMlp, check, lib
 
-MAP_STRIDE = 20
+_K = _lib.CONST      # the #define constants of include/tensoir_hip.h
+MAP_STRIDE = _K["TIR_MAP_STRIDE"]
 
 # Optional instrumentation used by bench.py: when STATS is a dict, the march wrappers accumulate the
 # number of gathered density samples per kernel (device-side counter, read back by the caller), and
@@ -1620,10 +1621,10 @@ def keep_components(vol, labels, table, keep, fill=0.0, level=None):
     return out
 
 
-SIMPLIFY_ACC = 28
-_SIMPLIFY_ERRORS = ((1, "a face index lies outside [0, V)"),
-                    (2, "a face edge is longer than 4 cells along an axis (or not finite)"),
-                    (4, "a vertex lies more than 3.5 cells outside the lattice of cells (or is not finite)"))
+SIMPLIFY_ACC = _K["TIR_SIMPLIFY_ACC"]
+_SIMPLIFY_ERRORS = ((_K["TIR_SIMPLIFY_ERR_FACE_INDEX"], "a face index lies outside [0, V)"),
+                    (_K["TIR_SIMPLIFY_ERR_FACE_EXTENT"], "a face edge is longer than 4 cells along an axis (or not finite)"),
+                    (_K["TIR_SIMPLIFY_ERR_VERTEX"], "a vertex lies more than 3.5 cells outside the lattice of cells (or is not finite)"))
 
 
 def simplify_mesh(verts, faces, cell, origin=(0.0, 0.0, 0.0), dims=None, reg=1e-2):
@@ -1686,7 +1687,7 @@ def simplify_mesh(verts, faces, cell, origin=(0.0, 0.0, 0.0), dims=None, reg=1e-
 
 
 # ---- surface distance between meshes (tir_distance.hip) ------------------------------
-DISTANCE_MAX_DIM = 256
+DISTANCE_MAX_DIM = _K["TIR_DISTANCE_MAX_DIM"]
 DISTANCE_CELL_FACTOR = 2.0
 _DISTANCE_FACE_INDEX = "a face index lies outside [0, V)"
 
@@ -1726,7 +1727,7 @@ def sample_surface(verts, faces, n, seed=0):
     status = torch.zeros((4,), dtype=torch.int64, device=dev)
     _call("tir_mesh_sample_cdf", _ptr(verts if V else None), V, _ptr(faces), F, _ptr(cdf), _ptr(sums), _ptr(status), _stream())
     total, err, _, _ = [int(x) for x in status.cpu()]
-    if err:
+    if err & _K["TIR_DISTANCE_ERR_FACE_INDEX"]:
         raise _lib.TensoirHipError("sample_surface: " + _DISTANCE_FACE_INDEX)
     if total <= 0:
         raise _lib.TensoirHipError("sample_surface: every face is degenerate (no area to sample)")
@@ -1750,7 +1751,7 @@ def _face_grid_count(verts, faces, cell, origin, dims):
     _call("tir_face_grid_count", _ptr(verts if V else None), V, _ptr(faces if F else None), F, c_cell, c_org, c_dims, _ptr(status),
           _stream())
     pairs, err, degenerate, listed = [int(x) for x in status.cpu()]
-    if err:
+    if err & _K["TIR_DISTANCE_ERR_FACE_INDEX"]:
         raise _lib.TensoirHipError("face_grid: " + _DISTANCE_FACE_INDEX)
     return pairs, degenerate, listed, (c_cell, c_org, c_dims)
 
@@ -1869,8 +1870,8 @@ def point_mesh_distance(points, verts, faces, grid=None, closest=False, tested=F
     return (dist, face) + ((cl,) if closest else ()) + ((nt,) if tested else ())
 
 
-RAY_MODES = {"closest": 0, "count": 1, "any": 2}                       # TIR_RAY_CLOSEST / COUNT / ANY
-RAY_GRAZED, RAY_INVALID = 1, 2                                        # TIR_RAY_FLAG_*
+RAY_MODES = {"closest": _K["TIR_RAY_CLOSEST"], "count": _K["TIR_RAY_COUNT"], "any": _K["TIR_RAY_ANY"]}
+RAY_GRAZED, RAY_INVALID = _K["TIR_RAY_FLAG_GRAZED"], _K["TIR_RAY_FLAG_INVALID"]
 # TIR_RAY_INSIDE_DIRECTIONS: the three fixed directions of mesh_inside (fp32)
 MESH_INSIDE_DIRECTIONS = ((0.5345225, 0.2672612, 0.8017837), (-0.6882472, 0.6246950, -0.3692745), (0.1825742, -0.9128709, -0.3651484))
 
@@ -1953,7 +1954,7 @@ def mesh_inside(points, verts, faces, grid=None):
 
 
 # ---- per-point bake (tensoir_amd/bake.py) ---------------------------------------------------------
-BAKE_ROW = 16
+BAKE_ROW = _K["TIR_BAKE_ROW"]
 
 
 def bake_composite(off, cnt, rec_w, rec_xyz, rec_brdf, rec_normal, origins, dirs, fallback_normal, aabb):
@@ -2100,8 +2101,8 @@ def atlas_pack(verts, normals, faces, size, cols, T, albedo, roughness, normal, 
 
 
 # ---- z-buffer rasteriser of the exported mesh (tensoir_amd/raster.py) -------------------
-RASTER_MAX_SIDE = 8192
-RASTER_ROW = 12
+RASTER_MAX_SIDE = _K["TIR_RASTER_MAX_SIDE"]
+RASTER_ROW = _K["TIR_RASTER_ROW"]
 RASTER_DROPS = ("index", "near", "guard", "nonfinite")     # the order of tir_raster_project's status counts
 
 
@@ -2185,8 +2186,8 @@ def raster_shade(pix, nrm, tan=None, uv=None, images=None, raw=False):
 
 
 # ---- lighting of the exported asset (tensoir_amd/raster.py) -----------------------------
-LIGHT_OCCLUSION = 1
-LIGHT_SRGB = 2
+LIGHT_OCCLUSION = _K["TIR_LIGHT_OCCLUSION"]
+LIGHT_SRGB = _K["TIR_LIGHT_SRGB"]
 
 
 def env_row_weights(H, W):
@@ -2228,7 +2229,7 @@ def light_gbuffer(gbuf, view, cells, fresnel=0.04, occlusion=True, srgb=False):
 
 
 # ---- shadows of the exported asset: one orthographic z-buffer per light cell (tensoir_amd/raster.py) --------------
-SHADOW_MAX_SIDE = 4096
+SHADOW_MAX_SIDE = _K["TIR_SHADOW_MAX_SIDE"]
 SHADOW_WORK_CAP = 1 << 16      # listed (cell, face) pairs of shadow_maps' workgroup pass; any value gives the same maps
 
 
@@ -2409,9 +2410,9 @@ def light_gbuffer_occluded(gbuf, view, cells, occl, fresnel=0.04, occlusion=True
 
 
 # ---- image metrics (tensoir_amd/metrics.py) -----------------------------------------------------------------------
-SSIM_TILE = 16                   # TIR_SSIM_TILE: the side of the output tile one workgroup of tir_ssim computes
-SSIM_MAX_TAPS = 31               # TIR_SSIM_MAX_TAPS
-IMAGE_ERROR_SHARE = 2048         # TIR_IMAGE_ERROR_SHARE: pixels per workgroup of tir_image_error (at most 256 workgroups per image)
+SSIM_TILE = _K["TIR_SSIM_TILE"]                   # the side of the output tile one workgroup of tir_ssim computes
+SSIM_MAX_TAPS = _K["TIR_SSIM_MAX_TAPS"]
+IMAGE_ERROR_SHARE = _K["TIR_IMAGE_ERROR_SHARE"]   # pixels per workgroup of tir_image_error (at most 256 workgroups per image)
 
 
 def _workspace(doubles, dev):
@@ -2459,9 +2460,9 @@ def image_error(a, b, mask=None, angular=False):
 
 
 # ---- total-variation regulariser (tensoir_amd/regularisers.py) ----------------------------------------------------
-TV_MAX_PLANES = 8                # TIR_TV_MAX_PLANES: planes per launch
-TV_SHARE = 8192                  # TIR_TV_SHARE: floats of one plane per workgroup of tir_tv_bwd, and of tir_tv_fwd on a small plane
-TV_FWD_GROUPS = 128              # TIR_TV_FWD_GROUPS: tir_tv_fwd gives a plane at most this many workgroups (larger shares beyond)
+TV_MAX_PLANES = _K["TIR_TV_MAX_PLANES"]           # planes per launch
+TV_SHARE = _K["TIR_TV_SHARE"]                     # floats of one plane per workgroup of tir_tv_bwd, and of tir_tv_fwd on a small plane
+TV_FWD_GROUPS = _K["TIR_TV_FWD_GROUPS"]           # tir_tv_fwd gives a plane at most this many workgroups (larger shares beyond)
 
 
 def is_channel_last(t):
@@ -2554,8 +2555,8 @@ def tv_backward(planes, coefs, g, needs=None, out=None):
 
 
 # ---- guided a-trous denoiser (tensoir_amd/denoise.py) -------------------------------------------------------------
-DENOISE_GUIDE = 12               # TIR_DENOISE_GUIDE: floats of a guide row {pos.xyz, valid, n.xyz, roughness, albedo.rgb, 0}
-ATROUS_MAX_K = 24                # TIR_ATROUS_MAX_K: colour floats per pixel of one tir_atrous_level launch (eight maps)
+DENOISE_GUIDE = _K["TIR_DENOISE_GUIDE"]           # floats of a guide row {pos.xyz, valid, n.xyz, roughness, albedo.rgb, 0}
+ATROUS_MAX_K = _K["TIR_ATROUS_MAX_K"]             # colour floats per pixel of one tir_atrous_level launch (eight maps)
 
 
 def denoise_guide(maps, rays, guide, row0, acc_thres=0.5):

@@ -1,5 +1,6 @@
 """C-ABI checks that need no GPU: the library loads, exports every symbol include/tensoir_hip.h
-declares, the ctypes mirror matches the C struct layout, and argument validation works."""
+declares, the binding derived from the header (signatures, struct layouts, constants) equals what the
+host compiler makes of the same header, and argument validation works."""
 import ctypes as C
 import os
 import re
@@ -9,7 +10,7 @@ import sys
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "tensoir_hip.h")
+INCLUDE = os.path.join(ROOT, "include")
 
 
 @pytest.fixture(scope="module")
@@ -22,9 +23,8 @@ def lib():
 
 
 def declared_symbols():
-    src = open(HEADER).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"\b(tir_\w+)\s*\(", src)))
+    from tensoir_amd import _lib
+    return sorted(_lib.SIGNATURES)       # test_binding_matches_the_compiler holds this set to the compiler's
 
 
 def test_every_declared_symbol_is_exported(lib):
@@ -34,41 +34,200 @@ def test_every_declared_symbol_is_exported(lib):
         assert hasattr(lib, s), f"{s} declared in tensoir_hip.h but not exported"
 
 
-def test_binding_table_matches_header(lib):
-    from tensoir_amd import _lib
-    assert sorted(_lib.SIGNATURES) == declared_symbols()
-    # arity of every prototype
-    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    for name, (_, args) in _lib.SIGNATURES.items():
-        m = re.search(r"\b" + name + r"\s*\((.*?)\)\s*;", src, flags=re.S)
-        assert m, name
-        params = m.group(1).strip()
-        n = 0 if params in ("", "void") else params.count(",") + 1
-        assert n == len(args), f"{name}: header has {n} parameters, binding {len(args)}"
+# ---- the derived binding (tensoir_amd/_lib.py parses the header) against what the host compiler makes of the same header ----
+def _run(tmp, name, text, compiler, *flags):
+    src = tmp / name
+    src.write_text(text)
+    exe = tmp / (name + ".exe")
+    subprocess.check_call([compiler, *flags, "-I", INCLUDE, str(src), "-o", str(exe)])
+    return subprocess.check_output([str(exe)]).decode().splitlines()
 
 
-def test_struct_layout_matches_c(tmp_path, lib):
-    from tensoir_amd import _lib
-    src = tmp_path / "layout.c"
-    src.write_text(r'''
-#include <stdio.h>
-#include <stddef.h>
+_TRAITS = r"""
+#include <cstdio>
+#include <type_traits>
 #include "tensoir_hip.h"
-int main(void) {
-  printf("%zu %zu %zu %zu %zu %zu %zu %zu\n", sizeof(TirField), offsetof(TirField, grid), offsetof(TirField, dplane),
-         offsetof(TirField, basis_t), offsetof(TirField, occ_nbr), offsetof(TirField, occ_dim), offsetof(TirField, occ_inv),
-         offsetof(TirField, occ_hi));
-  printf("%zu %zu %zu\n", sizeof(TirMlp), offsetof(TirMlp, feat_dim), offsetof(TirMlp, act));
-  printf("%zu %zu\n", sizeof(TirEnvSG), offsetof(TirEnvSG, n_sg));
-  return 0; }''')
-    exe = tmp_path / "layout"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    out = subprocess.check_output([str(exe)]).decode().split("\n")
-    F, M, E = _lib.TirField, _lib.TirMlp, _lib.TirEnvSG
-    assert [int(x) for x in out[0].split()] == [C.sizeof(F), F.grid.offset, F.dplane.offset, F.basis_t.offset,
-                                                F.occ_nbr.offset, F.occ_dim.offset, F.occ_inv.offset, F.occ_hi.offset]
-    assert [int(x) for x in out[1].split()] == [C.sizeof(M), M.feat_dim.offset, M.act.offset]
-    assert [int(x) for x in out[2].split()] == [C.sizeof(E), E.n_sg.offset]
+template <class T> void kind() {
+  if constexpr (std::is_void_v<T>) std::printf(" v");
+  else if constexpr (std::is_pointer_v<T>) std::printf(" p");
+  else if constexpr (std::is_floating_point_v<T>) std::printf(" f%zu", sizeof(T));
+  else if constexpr (std::is_integral_v<T>) std::printf(" %c%zu", std::is_signed_v<T> ? 'i' : 'u', sizeof(T));
+  else static_assert(!sizeof(T), "a parameter that is neither a pointer nor a number");
+}
+template <class F> struct sig;
+template <class R, class... A> struct sig<R (*)(A...)> {
+  static void print(const char* name) { std::printf("%s", name); kind<R>(); (kind<A>(), ...); std::printf("\n"); }
+};
+int main() {
+ENTRIES  return 0; }
+"""
+
+
+@pytest.fixture(scope="module")
+def compiler_kinds(tmp_path_factory):
+    """name -> [return kind, parameter kinds ...] of every bound entry as g++ sees its prototype: p = any pointer, i4 / i8 / u8 =
+    integral by size and signedness, f4 / f8 = floating, v = void."""
+    from tensoir_amd import _lib
+    body = "".join(f'  sig<decltype(&{n})>::print("{n}");\n' for n in _lib.SIGNATURES)
+    out = _run(tmp_path_factory.mktemp("sig"), "sig.cpp", _TRAITS.replace("ENTRIES", body), "g++", "-std=c++17")
+    return {line.split()[0]: line.split()[1:] for line in out}
+
+
+def _kind(t):
+    if t is None:
+        return "v"
+    if t in (C.c_void_p, C.c_char_p) or issubclass(t, C._Pointer):
+        return "p"
+    if t in (C.c_float, C.c_double):
+        return f"f{C.sizeof(t)}"
+    assert isinstance(t(0).value, int), t
+    return f"{'i' if t(-1).value < 0 else 'u'}{C.sizeof(t)}"
+
+
+def signature_mismatches(signatures, kinds):
+    """[(entry, position, binding's kind, compiler's kind)]: position is 'ret', a parameter index or 'arity' (then the counts)."""
+    bad = []
+    for name, (res, args) in signatures.items():
+        want = kinds[name]
+        if _kind(res) != want[0]:
+            bad.append((name, "ret", _kind(res), want[0]))
+        if len(args) != len(want) - 1:
+            bad.append((name, "arity", len(args), len(want) - 1))
+        bad += [(name, i, _kind(a), w) for i, (a, w) in enumerate(zip(args, want[1:])) if _kind(a) != w]
+    return bad
+
+
+def test_binding_matches_the_compiler(tmp_path, compiler_kinds):
+    """Every entry of SIGNATURES: arity, class and width of each parameter and the return type equal the compiler's; and the bound
+    names are exactly the functions the compiler finds declared in the header (gcc -aux-info lists them)."""
+    from tensoir_amd import _lib
+    assert set(compiler_kinds) == set(_lib.SIGNATURES)
+    assert signature_mismatches(_lib.SIGNATURES, compiler_kinds) == []
+    unit = tmp_path / "unit.c"
+    unit.write_text('#include "tensoir_hip.h"\n')
+    subprocess.check_call(["gcc", "-I", INCLUDE, "-fsyntax-only", "-aux-info", str(tmp_path / "protos.txt"), str(unit)])
+    protos = [ln for ln in (tmp_path / "protos.txt").read_text().splitlines() if "tensoir_hip.h:" in ln]
+    declared = [re.search(r"(\w+) \(", ln.split("*/", 1)[1]).group(1) for ln in protos]
+    assert sorted(declared) == sorted(_lib.SIGNATURES) and len(declared) >= 138
+
+
+def test_signature_check_reports_every_kind_of_mistake(compiler_kinds):
+    """The comparison above is not vacuous: a widened integer, a double for a float, an integer for a pointer, a dropped argument
+    and a changed return type are each reported, by entry and by position."""
+    from tensoir_amd import _lib
+
+    def first(pred):
+        return next((n, i) for n, (_, args) in _lib.SIGNATURES.items() for i, a in enumerate(args) if pred(a))
+
+    def perturbed(name, res=..., args=None):
+        sigs = dict(_lib.SIGNATURES)
+        sigs[name] = (sigs[name][0] if res is ... else res, list(sigs[name][1]) if args is None else args)
+        return sigs
+
+    def swap(where, t):
+        name, i = where
+        args = list(_lib.SIGNATURES[name][1])
+        args[i] = t
+        return signature_mismatches(perturbed(name, args=args), compiler_kinds)
+
+    n, i = where = first(lambda a: a is C.c_int32)
+    assert swap(where, C.c_int64) == [(n, i, "i8", "i4")]
+    n, i = where = first(lambda a: a is C.c_float)
+    assert swap(where, C.c_double) == [(n, i, "f8", "f4")]
+    n, i = where = first(lambda a: a is C.c_void_p)
+    assert swap(where, C.c_int64) == [(n, i, "i8", "p")]
+    n, i = where = first(lambda a: issubclass(a, C._Pointer))
+    assert swap(where, C.c_int64) == [(n, i, "i8", "p")]
+    args = _lib.SIGNATURES["tir_exclusive_scan"][1]
+    assert signature_mismatches(perturbed("tir_exclusive_scan", args=args[:-1]), compiler_kinds) == [("tir_exclusive_scan", "arity", 3, 4)]
+    got = signature_mismatches(perturbed("tir_exclusive_scan", args=args[:1] + args[2:]), compiler_kinds)   # dropped in the middle
+    assert ("tir_exclusive_scan", "arity", 3, 4) in got and ("tir_exclusive_scan", 1, "i4", "p") in got
+    assert signature_mismatches(perturbed("tir_mlp_packed_floats", res=C.c_int), compiler_kinds) == [("tir_mlp_packed_floats", "ret", "i4", "i8")]
+    assert signature_mismatches(perturbed("tir_version", res=C.c_char_p), compiler_kinds) == [("tir_version", "ret", "p", "i4")]
+
+
+def test_struct_layout_matches_c(tmp_path):
+    """sizeof of every struct the binding derived, offsetof and size of every field: the C compiler's against ctypes'."""
+    from tensoir_amd import _lib
+    assert {"TirField", "TirFieldHalf", "TirFieldGrad", "TirMlp", "TirEnvSG", "TirHalfJob", "TirHalfJobs"} <= set(_lib.STRUCTS)
+    lines, want = [], []
+    for name, S in _lib.STRUCTS.items():
+        lines.append(f'  printf("{name} %zu\\n", sizeof({name}));')
+        want.append(f"{name} {C.sizeof(S)}")
+        for f, _ in S._fields_:
+            lines.append(f'  printf("{name}.{f} %zu %zu\\n", offsetof({name}, {f}), sizeof((({name}*)0)->{f}));')
+            want.append(f"{name}.{f} {getattr(S, f).offset} {getattr(S, f).size}")
+    prog = '#include <stdio.h>\n#include <stddef.h>\n#include "tensoir_hip.h"\nint main(void) {\n' + "\n".join(lines) + "\n  return 0; }\n"
+    assert _run(tmp_path, "layout.c", prog, "gcc") == want
+    assert len(_lib.TirField._fields_) == 34 and _lib.TirField._fields_[-1][0] == "dense_app"
+
+
+def test_constants_match_c(tmp_path):
+    """Every #define the binding published: the C compiler's value, exactly (integers as long long, floating values in hex), and
+    its class; and no TIR_* macro is missing but the brace list, which the parser must skip."""
+    from tensoir_amd import _lib
+    lines = []
+    for name, v in _lib.CONST.items():
+        cls = f'_Generic(({name}), float: "f", double: "f", default: "i")'
+        lines.append(f'  printf("{name} %s %lld\\n", {cls}, (long long)({name}));' if isinstance(v, int) else
+                     f'  printf("{name} %s %a\\n", {cls}, (double)({name}));')
+    prog = '#include <stdio.h>\n#include "tensoir_hip.h"\nint main(void) {\n' + "\n".join(lines) + "\n  return 0; }\n"
+    got = {}
+    for line in _run(tmp_path, "const.c", prog, "gcc", "-std=c11"):
+        name, cls, text = line.split()
+        got[name] = int(text) if cls == "i" else float.fromhex(text)
+    assert got.keys() == _lib.CONST.keys()
+    for name, v in _lib.CONST.items():
+        assert type(got[name]) is type(v) and got[name] == v, (name, v, got[name])
+    assert _lib.CONST["TIR_ERR_ARG"] == -1001 and _lib.CONST["TIR_DISTANCE_SLACK"] == 2.0 ** -13 and _lib.CONST["TIR_MAP_STRIDE"] == 20
+    macros = subprocess.check_output(["gcc", "-dM", "-E", "-I", INCLUDE, os.path.join(INCLUDE, "tensoir_hip.h")]).decode()
+    assert set(re.findall(r"^#define (TIR_\w+)", macros, flags=re.M)) == set(_lib.CONST) | {"TIR_RAY_INSIDE_DIRECTIONS"}
+
+
+@pytest.mark.parametrize("text, names", [
+    ("int tir_f(size_t n);", "size_t n"),                                                # an unknown type
+    ("typedef struct TirA { quad q; } TirA;", "quad q"),
+    ("typedef struct TirA { float v[TIR_N]; } TirA;", "float v[TIR_N]"),                 # a length that is no number and no macro
+    ("#define TIR_N 1.5\ntypedef struct TirA { float v[TIR_N]; } TirA;", "float v[TIR_N]"),
+    ("int tir_f(int32_t n, void (*)(int));", "tir_f"),                                   # an unnamed function-pointer parameter
+    ("int tir_f(int32_t);", "int32_t"),                                                  # an unnamed parameter
+    ("int tir_f(int32_t n[3]);", "int32_t n[3]"),
+    ("int tir_f(TirA a);", "TirA a"),
+    ("#if TIR_X\nint tir_f(void);\n#endif", "#if TIR_X"),                                # conditional text would be a guess
+])
+def test_parser_refuses_what_it_cannot_read(text, names):
+    from tensoir_amd import _lib
+    with pytest.raises(_lib.TensoirHipError, match=re.escape(names)):
+        _lib.parse_header(text)
+
+
+def test_parser_reads_the_subset():
+    from tensoir_amd import _lib
+    const, structs, sigs = _lib.parse_header("""/* a comment; with, punctuation ( */
+#define TIR_N 2
+#define TIR_Q (1.0 / 4.0)
+#define TIR_LIST {1, 2}
+typedef struct TirA { const float* p[TIR_N]; float near_, far_; unsigned* u; } TirA;
+typedef struct TirB { TirA a[3]; int64_t n; } TirB;
+const char* tir_name(int code);
+int64_t tir_f(const TirA* a, const TirB* const* bs, unsigned long long* stats,
+              double x, uint64_t seed, void* stream);
+void tir_g(void);
+""")
+    assert const == {"TIR_N": 2, "TIR_Q": 0.25}
+    A, B = structs["TirA"], structs["TirB"]
+    assert [(n, t) for n, t in A._fields_] == [("p", C.c_void_p * 2), ("near_", C.c_float), ("far_", C.c_float), ("u", C.c_void_p)]
+    assert B._fields_ == [("a", A * 3), ("n", C.c_int64)] and C.sizeof(B) == 3 * C.sizeof(A) + 8
+    assert sigs == {"tir_name": (C.c_char_p, [C.c_int]),
+                    "tir_f": (C.c_int64, [C.POINTER(A), C.c_void_p, C.c_void_p, C.c_double, C.c_uint64, C.c_void_p]),
+                    "tir_g": (None, [])}
+
+
+def test_missing_header_is_named():
+    """TENSOIR_HIP_HEADER overrides the path; a header that is not there raises at import, naming the path."""
+    env = dict(os.environ, TENSOIR_HIP_HEADER="/nonexistent/tensoir_hip.h")
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "tensoir_amd", "_lib.py")], env=env, capture_output=True, text=True)   # _lib alone
+    assert p.returncode != 0 and "TensoirHipError" in p.stderr and "/nonexistent/tensoir_hip.h" in p.stderr, p.stderr
 
 
 def test_version_and_errors(lib):
