@@ -1484,6 +1484,85 @@ int tir_denoise_guide(const float* maps, const float* rays, int64_t n, float acc
 int tir_atrous_level(const float* color_in, float* color_out, const float* guide, int32_t H, int32_t W, int32_t K, int32_t step,
                      float inv_sn, float inv_sp, float inv_sa2, float inv_sr2, float inv_sc2, void* stream);
 
+/* ---- Material editing (tensoir_amd/materials.py; restated in float64 by tests/materials_reference.py): albedo,
+ * roughness and Fresnel term of surface rows changed between the primary pass and the shading stage (relight.relight_chunk), or
+ * between the bake and the texture atlas (mesh.bake_atlas).
+ * An EDIT LIST is n_edits in 0..TIR_MATERIAL_MAX_EDITS records of TIR_MATERIAL_EDIT_FLOATS fp32 in DEVICE memory (every lane reads
+ * the same record: scalar loads).  Integers are stored as the floats that equal them.  Record:
+ *    [0] selectors, the sum of 1 sphere, 2 box, 4 colour, 8 roughness band, 16 palette entry      [1] strength
+ *    [2:5] sphere centre  [5] radius  [6] feather                 [7:10] box centre  [10:13] half extents  [13] feather
+ *    [14:17] colour (linear RGB)  [17] tolerance  [18] feather    [19] lo  [20] hi  [21] feather           [22] palette id
+ *    [23] albedo mode: 0 keep, 1 set, 2 multiply, 3 recolour      [24:27] target colour (linear RGB)
+ *    [27] roughness scale  [28] roughness offset                  [29] 1: metallic is a target  [30] metallic   [31] 0
+ * The PALETTE (optional) is k in 0..TIR_MATERIAL_MAX_PALETTE centroids [k][4] fp32 in device memory and the roughness weight wr.
+ * A row has the position x, albedo a0, roughness r0 and Fresnel term f0.  State: base = a0, rough = r0, metal = 0.  Per edit, in
+ * list order:
+ *    w = strength x the product of the enabled selectors, all of which read the row's ORIGINAL x, a0, r0.  With
+ *      smoothstep(t) = t t (3 - 2 t),  fall(d, r, f) = f > 0 ? 1 - smoothstep(clamp((d - r) / f, 0, 1)) : (d <= r ? 1 : 0):
+ *      sphere  fall(|x - c|, radius, feather)             box     fall(max over the axes of (|x - c| - half), 0, feather)
+ *      colour  fall(|a0 - colour|, tolerance, feather)    band    fall(max(lo - r0, r0 - hi), 0, feather)
+ *      palette label(a0, r0) == id ? 1 : 0, label = the lowest j that minimises d2_j = ((D0 D0 + D1 D1) + D2 D2) + D3 D3,
+ *              D = (a0.r, a0.g, a0.b, wr r0) - centroid j; wr r0, every difference, product and sum is ONE fp32 operation rounded
+ *              on its own (tir::material_label, the function tir_kmeans_assign labels with); without a palette it is 0.
+ *    an edit with w == 0 leaves the state as it is.  Otherwise
+ *      target albedo: keep base; set colour; multiply base o colour; recolour colour Y(base) / max(Y(colour), 1e-6) with
+ *              Y = 0.2126 r + 0.7152 g + 0.0722 b; clamped to [0, 1].   target roughness: clamp(rough scale + offset, 0.09, 0.99).
+ *      v += w (target - v) for base, for rough unless scale = 1 and offset = 0 (an edit that does not ask for another roughness
+ *      leaves rough as it is, also outside the clamp's range), and for metal where [29] is 1 (target [30]).
+ * After the last edit: albedo = base (1 - metal), fresnel = f0 (1 - metal) + base metal (glTF's metallic-roughness model with the
+ * row's own F0), roughness = rough.  fp32 throughout, every operation rounded on its own (no fused multiply-add: the two entries
+ * below give the same bits on the same rows), sums of three terms from the left, smoothstep as (t t) (3 - 2 t).  A row on which
+ * every edit has w == 0 -- an empty list included -- keeps the bits of its albedo, roughness and Fresnel term (base = a0, metal = 0).
+ * tir_material_edit: rows i < min(M, *m_dev) (m_dev [1] in device memory or NULL = M) of plain arrays, row i of an array at
+ *   i x its stride: points (stride >= 3), albedo (>= 3), rough (>= 1), fresnel (>= 3) -> out_albedo, out_rough, out_fresnel,
+ *   out_base (may be NULL), out_metal (may be NULL), which are dense: [M][3], [M], [M][3], [M][3], [M].  An output may be its
+ *   input where that is dense too.  Rows beyond the count are not written.
+ * tir_material_edit_maps: in place on the albedo (7:10), roughness (10) and Fresnel (11:14) columns of the rows of maps [B][20]
+ *   with acc (14) > acc_thres; x = o + depth d from rays [B][6], by the device function tir_surface_compact forms surf with (the
+ *   same bits).  Only rows with an edit of w != 0 are written; n_edits = 0 does nothing.
+ * Both: one lane per row, no atomics, no LDS, nothing allocated, the host does not wait.  Host validation before any device
+ *   work: n_edits outside 0..TIR_MATERIAL_MAX_EDITS, k outside 0..TIR_MATERIAL_MAX_PALETTE, a negative M or B, a stride below its
+ *   width, a non-finite wr or a NaN acc_thres, edits null with n_edits > 0, palette null with k > 0, and with M or B > 0 a null
+ *   array (out_base and out_metal excepted) -> TIR_ERR_ARG; M > 2^31 - 1 -> TIR_ERR_UNSUPPORTED.
+ * tir_atlas_metal: the B channel of tir_atlas_pack's orm image = round(255 clamp(metal, 0, 1)), half to even, on the owned
+ *   texels (metal [N] in tir_atlas_texels' cell-major order); nothing else is written.  size, cols, T, n_faces: the layout, refused
+ *   as tir_atlas_pack refuses it; a null pointer or an orm that is not 4-byte aligned -> TIR_ERR_ARG; F = 0 does nothing.
+ *
+ * Deterministic k-means (Lloyd) over rows with the feature (a.r, a.g, a.b, wr r), albedo [N][3], rough [N]; the host loops.
+ *   Distances are tir::material_label's d2 in fp32; every sum is a double sum in a fixed order; no floating-point atomics: two
+ *   calls give identical bits.  k in 1..TIR_MATERIAL_MAX_PALETTE, centroids [k][4] fp32, N >= 1.
+ * tir_kmeans_seed: one farthest-point step given the first n_have centroids.  n_have = 0: centroid 0 = the feature of row 0.
+ *   Otherwise mind[i] = min(mind[i], d2(row i, centroid n_have - 1)) (n_have = 1: mind[i] = d2, mind is not read), and centroid
+ *   n_have = the feature of the row of largest mind, the lowest index among equals: one 64-bit integer atomic max of
+ *   (bits(mind) << 32) | (0xFFFFFFFF - i) per wave into best [1] (8-byte aligned; the entry clears it first).
+ * tir_kmeans_assign: labels [N] int32 = label of each row (read first unless first != 0: then every row counts as changed).
+ *   Workgroup g owns rows [g TIR_KMEANS_ROWS, (g + 1) TIR_KMEANS_ROWS) and STORES part_sums [g][k][5] double = per cluster the
+ *   sums of the four features and of d2 over its rows in row order, part_counts [g][k] int32, part_changed [g] int32.
+ *   tir_kmeans_groups(N) = the number of workgroups.
+ * tir_kmeans_update: one workgroup adds the partials in workgroup order: counts [k] int64, centroid = fp32(sum / count) (an empty
+ *   cluster keeps its centroid), inertia [1] double = the sum of d2 in cluster order, changed [1] int32.
+ * Validation: N < 0, n_have outside [0, k), k outside 1..TIR_MATERIAL_MAX_PALETTE, a non-finite wr, a null pointer, n_groups !=
+ *   tir_kmeans_groups(N) -> TIR_ERR_ARG; N > 2^31 - 1 -> TIR_ERR_UNSUPPORTED; N = 0 -> TIR_ERR_ARG (there is nothing to seed from). */
+#define TIR_MATERIAL_MAX_EDITS 16
+#define TIR_MATERIAL_EDIT_FLOATS 32
+#define TIR_MATERIAL_MAX_PALETTE 32
+#define TIR_KMEANS_ROWS 256
+int tir_material_edit(const float* edits, int32_t n_edits, const float* palette, int32_t k, float wr, const float* points,
+                      int32_t point_stride, const float* albedo, int32_t albedo_stride, const float* rough, int32_t rough_stride,
+                      const float* fresnel, int32_t fresnel_stride, float* out_albedo, float* out_rough, float* out_fresnel,
+                      float* out_base, float* out_metal, int64_t M, const int32_t* m_dev, void* stream);
+int tir_material_edit_maps(const float* edits, int32_t n_edits, const float* palette, int32_t k, float wr, float* maps,
+                           const float* rays, int64_t B, float acc_thres, void* stream);
+int tir_atlas_metal(uint8_t* orm, int32_t size, int32_t cols, int32_t T, int64_t n_faces, const float* metal, void* stream);
+int64_t tir_kmeans_groups(int64_t N);
+int tir_kmeans_seed(const float* albedo, const float* rough, int64_t N, float wr, float* centroids, int32_t k, int32_t n_have,
+                    float* mind, uint64_t* best, void* stream);
+int tir_kmeans_assign(const float* albedo, const float* rough, int64_t N, float wr, const float* centroids, int32_t k,
+                      int32_t first, int32_t* labels, double* part_sums, int32_t* part_counts, int32_t* part_changed,
+                      int64_t n_groups, void* stream);
+int tir_kmeans_update(const double* part_sums, const int32_t* part_counts, const int32_t* part_changed, int64_t n_groups,
+                      float* centroids, int32_t k, int64_t* counts, double* inertia, int32_t* changed, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

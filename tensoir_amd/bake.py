@@ -217,7 +217,23 @@ def main(argv=None):
     ap.add_argument("--environment", default=None, metavar="OUT.hdr", help="also write the model's light --light as a Radiance "
                     "picture (mesh.export_environment)")
     ap.add_argument("--environment-size", type=int, nargs=2, metavar=("H", "W"), default=(256, 512))
+    ap.add_argument("--edits", default=None, metavar="FILE.json", help="material edits applied between the bake and the texture atlas "
+                    "(with --texture-size): a JSON file {\"edits\": [...], \"palette\": {...}} as materials.EditList.to_json writes it")
+    ap.add_argument("--palette", type=int, default=None, metavar="K", help="print the K materials of the surface (materials.palette: "
+                    "k-means over albedo and roughness, the largest first) as one JSON line; an edits file may carry it as "
+                    "\"palette\".  With - for OUT nothing is exported")
+    ap.add_argument("--palette-samples", type=int, default=65536, metavar="N", help="surface samples the palette is found on")
     a = ap.parse_args(argv)
+    if a.edits is not None and a.texture_size is None:
+        ap.error("--edits changes the texture atlas: it needs --texture-size")
+    if a.palette is not None and (not 1 <= a.palette <= ops.MATERIAL_MAX_PALETTE or a.palette_samples < a.palette):
+        ap.error(f"--palette K: 1 <= K <= {ops.MATERIAL_MAX_PALETTE} and --palette-samples >= K")
+    edits = None
+    if a.edits is not None:
+        import json
+        from . import materials
+        with open(a.edits) as h:
+            edits = materials.EditList.from_json(json.load(h))              # refused before the checkpoint is read
     if a.check_views is not None and (a.texture_size is None or a.check_views < 1 or a.check_size < 1):
         ap.error("--check-views V (V >= 1, --check-size >= 1) compares a textured export: it needs --texture-size")
     if a.check_light is not None and a.check_views is None:
@@ -239,10 +255,19 @@ def main(argv=None):
     model = load_model(a.ckpt, "cuda", **extra)
     grid = None if a.grid is None else [a.grid] * 3
     report = {}
+    if a.palette is not None:
+        import json
+        from . import materials
+        pal = materials.palette(model, a.palette, samples=a.palette_samples, level=a.level, gridSize=grid, keep_largest=a.keep_largest,
+                                min_component_voxels=a.min_component_voxels, connectivity=a.connectivity)
+        print(json.dumps({"palette": pal.to_json(), "passes": pal.passes, "inertia": pal.inertia}))
+        if a.out == "-":
+            return
     if a.texture_size is not None:
+        more = {} if edits is None else {"edits": edits}
         nv, nf = mesh.export_textured(model, a.out, a.level, grid, a.texture_size, a.color, light_idx=a.light,
                                       keep_largest=a.keep_largest, min_component_voxels=a.min_component_voxels,
-                                      connectivity=a.connectivity, report=report, **simp)
+                                      connectivity=a.connectivity, report=report, **simp, **more)
     else:
         nv, nf = mesh.export_mesh(model, a.out, a.level, grid, attributes=True, color=a.color, light_idx=a.light,
                                   keep_largest=a.keep_largest, min_component_voxels=a.min_component_voxels,

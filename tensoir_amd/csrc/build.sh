@@ -17,7 +17,7 @@ OUT="${1:-$HERE/..}"
 INC="$HERE/../../include"
 HIPCC="${HIPCC:-/opt/rocm/bin/hipcc}"
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -I$INC -I$HERE -Wall -Wno-unused-function ${TENSOIR_EXTRA_FLAGS:-}"
-SRCS="tir_field tir_dense_app tir_march tir_mlp tir_shade tir_train tir_mesh tir_raster tir_metrics tir_regularise tir_denoise tir_distance"
+SRCS="tir_field tir_dense_app tir_march tir_mlp tir_shade tir_train tir_mesh tir_raster tir_metrics tir_regularise tir_denoise tir_distance tir_materials"
 mkdir -p "$HERE/obj"
 HIPVER="$($HIPCC --version 2>/dev/null | head -3 | sha256sum | cut -c1-16)"
 # the flags enter the stamp without the absolute checkout path (a snapshot on another box must not look like other flags)

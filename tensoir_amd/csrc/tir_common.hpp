@@ -229,6 +229,34 @@ __device__ __forceinline__ float sub_rn(float a, float b) {
     return a - b;
 }
 
+// The surface point of a primary ray, o + depth d per component (scripts/relight_importance.py:104: two ATen kernels, the
+// product and the sum rounded separately) -- the one form tir_surface_compact and tir_material_edit_maps share, so that an edit
+// selects by the very position the relighting stage is handed.
+__device__ __forceinline__ float surface_point(float o, float depth, float d) { return add_rn(o, mul_rn(depth, d)); }
+
+// round(255 x) of a value clamped to [0, 1], half to even (a NaN counts as 0): the byte of an RGBA8 atlas image
+__device__ __forceinline__ unsigned unorm8(float x) { return (unsigned)rintf(255.0f * fminf(fmaxf(x, 0.f), 1.f)); }
+
+// ---- material palette (contract: include/tensoir_hip.h, material editing) -- shared by the palette selector of
+// tir_material_edit and by the k-means kernels, which must agree on every label: d2 = ((D0 D0 + D1 D1) + D2 D2) + D3 D3 with
+// every difference, product and sum rounded on its own (a fused step would move a row that lies between two centroids).
+__device__ __forceinline__ float material_dist2(const float* __restrict__ c, float f0, float f1, float f2, float f3) {
+    const float d0 = sub_rn(f0, c[0]), d1 = sub_rn(f1, c[1]), d2 = sub_rn(f2, c[2]), d3 = sub_rn(f3, c[3]);
+    return add_rn(add_rn(add_rn(mul_rn(d0, d0), mul_rn(d1, d1)), mul_rn(d2, d2)), mul_rn(d3, d3));
+}
+// label(a0, r0): the lowest index among the k centroids [k][4] of smallest d2 to (a0, wr r0); d2 of the label in `best`.  k >= 1.
+__device__ __forceinline__ int material_label(const float* __restrict__ cent, int k, float wr, float ar, float ag, float ab, float r0,
+                                              float& best) {
+    const float f3 = mul_rn(wr, r0);
+    int label = 0;
+    best = material_dist2(cent, ar, ag, ab, f3);
+    for (int j = 1; j < k; ++j) {
+        const float d = material_dist2(cent + 4 * j, ar, ag, ab, f3);
+        if (d < best) { best = d; label = j; }
+    }
+    return label;
+}
+
 // ---- shadow maps of the light cells (contract: include/tensoir_hip.h, tir_shadow_*) -- shared by tir_raster.hip
 // (the maps, tir_shadow_lookup) and tir_shade.hip (tir_light_gbuffer_shadowed).
 // A point in the orthographic frame fr [12] of one cell: map coordinates in texels and the depth w (larger = nearer the light),

@@ -1269,7 +1269,7 @@ k_atlas_texels(const float* __restrict__ verts, const float* __restrict__ normal
 }
 
 // round(255 x) of a value in [0, 1] (a NaN counts as 0)
-__device__ __forceinline__ unsigned atlas_u8(float x) { return (unsigned)rintf(255.0f * fminf(fmaxf(x, 0.f), 1.f)); }
+__device__ __forceinline__ unsigned atlas_u8(float x) { return tir::unorm8(x); }
 
 // relight.linear2srgb_torch, its + 1e-6 included
 __device__ __forceinline__ float atlas_srgb(float c) {

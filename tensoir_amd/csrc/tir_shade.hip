@@ -120,7 +120,7 @@ k_shade_setup(const float* __restrict__ maps, const float* __restrict__ rays, co
         if (d == 0) {
             const float depth = mp[3];
 #pragma unroll
-            for (int a = 0; a < 3; ++a) surf[3 * (size_t)m + a] = add_rn(r[a], mul_rn(depth, r[3 + a]));   // :422
+            for (int a = 0; a < 3; ++a) surf[3 * (size_t)m + a] = surface_point(r[a], depth, r[3 + a]);   // :422
         }
         // cosine = clamp(einsum(surf2l, normal_map), 0); mask = cosine > 1e-6   (:433-435)
         float cs = dirs[3 * d] * mp[4] + dirs[3 * d + 1] * mp[5] + dirs[3 * d + 2] * mp[6];
@@ -722,7 +722,7 @@ k_surface_compact(const float* __restrict__ maps, const float* __restrict__ rays
             const float depth = mp[3];
 #pragma unroll
             for (int a = 0; a < 3; ++a) {
-                surf[3 * (size_t)sl + a] = add_rn(r[a], mul_rn(depth, r[3 + a]));
+                surf[3 * (size_t)sl + a] = surface_point(r[a], depth, r[3 + a]);
                 nrm[3 * (size_t)sl + a] = mp[4 + a];
                 alb[3 * (size_t)sl + a] = mp[7 + a];
                 fr[3 * (size_t)sl + a] = mp[11 + a];

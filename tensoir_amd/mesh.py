@@ -752,7 +752,7 @@ def _check_texture_options(size, color, bake_kw):
 
 
 @torch.no_grad()
-def bake_atlas(model, verts, faces, normals, grid, size=2048, color="albedo", **bake_kw):
+def bake_atlas(model, verts, faces, normals, grid, size=2048, color="albedo", edits=None, **bake_kw):
     """A texture atlas of the mesh (verts, faces, normals) as extract_mesh returns it -- file coordinates, index-space normals --
     with one texel sample of the field per owned texel.  Layout (ops.atlas_layout; include/tensoir_hip.h, tir_atlas_*): no chart
     solver, faces 2c and 2c+1 share the square cell c of T x T texels, T = size // ceil(sqrt(ceil(F / 2))).
@@ -761,24 +761,36 @@ def bake_atlas(model, verts, faces, normals, grid, size=2048, color="albedo", **
     -> {"pos" [3F, 3], "nrm" [3F, 3], "tan" [3F, 4], "uv" [3F, 2]: the unwelded mesh (float32), "base", "orm", "normal":
     [size, size, 4] uint8 images, "cols", "T"}, tensors on verts' device.  base is sRGB of the albedo, or of the Lambertian
     radiance under the baked light (color="diffuse"); orm holds occlusion (255 with lighting=False), roughness, 0; normal is the
-    baked shading normal in the frame (tangent, cross(n, tangent), n) of the interpolated mesh normal n."""
-    from . import bake
+    baked shading normal in the frame (tangent, cross(n, tangent), n) of the interpolated mesh normal n.
+    edits (a materials.EditList or a list of MaterialEdit; None: no kernel is added, the images keep their bits):
+    materials.apply runs on the bake's albedo and roughness at its surface positions before the images are packed.  The base
+    colour then encodes the edited `base` (glTF: the viewer forms the diffuse part from base and metallic; color="diffuse" lights
+    base (1 - metal)), G of orm the edited roughness and B of orm the metallic value (tir_atlas_metal)."""
+    from . import bake, materials
     _check_texture_options(size, color, bake_kw)
+    edits = materials.as_edit_list(edits)
     F = faces.shape[0]
     cols, T = ops.atlas_layout(F, size)
     pos, nrm, tan, uv = ops.atlas_corners(verts, normals, faces, size, cols, T)
     point, outward, _ = ops.atlas_texels(verts, normals, faces, size, cols, T)
     p, d = field_positions(model.aabb, grid, point, outward)
     b = bake.bake_points(model, p.contiguous(), d.contiguous(), **bake_kw)
-    base, orm, normal = ops.atlas_pack(verts, normals, faces, size, cols, T, b["albedo"], b["roughness"], b["normal"], b["coverage"],
+    albedo, roughness, metal = b["albedo"], b["roughness"], None
+    if edits is not None and len(edits) > 0:
+        # the asset carries no Fresnel texture (a glTF viewer takes 0.04 for dielectrics): the row's F0 is that constant here
+        e = materials.apply(b["surface"], albedo, roughness, torch.full_like(albedo, 0.04), edits)
+        albedo, roughness, metal = e["albedo" if color == "diffuse" else "base"], e["roughness"], e["metal"]
+    base, orm, normal = ops.atlas_pack(verts, normals, faces, size, cols, T, albedo, roughness, b["normal"], b["coverage"],
                                        irradiance=b["irradiance"] if color == "diffuse" else None, ao=b.get("ao"))
+    if metal is not None and F > 0:
+        ops.atlas_metal(orm, cols, T, F, metal)
     return {"pos": pos, "nrm": nrm, "tan": tan, "uv": uv, "base": base, "orm": orm, "normal": normal, "cols": cols, "T": T}
 
 
 @torch.no_grad()
 def export_textured(model, path, level=0.005, gridSize=None, size=2048, color="albedo", *, keep_largest=None,
                     min_component_voxels=None, connectivity=6, simplify=None, report=None, compress_level=6,
-                    simplify_tolerance=None, simplify_max=SIMPLIFY_MAX, measure_simplify=False, **bake_kw):
+                    simplify_tolerance=None, simplify_max=SIMPLIFY_MAX, measure_simplify=False, edits=None, **bake_kw):
     """extract_mesh + bake_atlas + write_glb: the mesh as a single-file binary glTF 2.0 with base-colour, occlusion / roughness /
     metallic and tangent-space normal textures -> (number of triangle corners = 3 F, number of faces).
     Positions are the PLY export's coordinates, the reference's voxel-size quirk included (module docstring), and the file's
@@ -786,7 +798,11 @@ def export_textured(model, path, level=0.005, gridSize=None, size=2048, color="a
     face, no index buffer).  keep_largest / min_component_voxels / connectivity / simplify: extract_mesh's options; the texture
     keeps the field's detail at every texel whatever the face budget.  compress_level: zlib's, for the PNG images.
     simplify_tolerance / simplify_max / measure_simplify: extract_mesh's error-bounded face budget and its report.
-    The root's extras.tensoir_amd records size, cols, T, faces, level, simplify (the k taken), color and light_idx."""
+    The root's extras.tensoir_amd records size, cols, T, faces, level, simplify (the k taken), color and light_idx.
+    edits: bake_atlas's material edits; the list's JSON is recorded as extras.tensoir_amd.edits.  An asset with
+    metal is for a glTF viewer: raster.relight_glb / relight_mesh keep their scalar fresnel and do not read orm's B channel."""
+    from . import materials
+    edits = materials.as_edit_list(edits)
     _check_component_options(keep_largest, min_component_voxels, connectivity)
     _check_simplify_options(simplify, simplify_tolerance, simplify_max, measure_simplify)
     _check_texture_options(size, color, bake_kw)
@@ -800,12 +816,14 @@ def export_textured(model, path, level=0.005, gridSize=None, size=2048, color="a
                                          measure_simplify=measure_simplify)
     if simplify_tolerance is not None:
         simplify = report["simplify"]
-    a = bake_atlas(model, verts, faces, normals, grid, size, color, **bake_kw)
+    a = bake_atlas(model, verts, faces, normals, grid, size, color, edits=edits, **bake_kw)
     F = faces.shape[0]
     light = bake_kw.get("light_idx", 0)
     extras = {"size": int(size), "cols": a["cols"], "T": a["T"], "faces": F, "level": float(level),
               "simplify": None if simplify is None else int(simplify), "color": color,
               "light_idx": int(light) if not torch.is_tensor(light) else None}
+    if edits is not None:
+        extras["edits"] = edits.to_json()
     write_glb(path, a["pos"], a["nrm"], a["tan"], a["uv"], {k: a[k].cpu().numpy() for k in IMAGE_NAMES}, extras,
               occlusion=bool(bake_kw.get("lighting", True)), compress_level=int(compress_level))
     return 3 * F, F

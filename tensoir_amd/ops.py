@@ -2596,3 +2596,133 @@ def atrous_level(color_in, color_out, guide, H, W, step, inv_sn, inv_sp, inv_sa2
         _call("tir_atrous_level", _ptr(color_in), _ptr(color_out), _ptr(guide), H, W, K, int(step), float(inv_sn), float(inv_sp),
               float(inv_sa2), float(inv_sr2), float(inv_sc2), _stream())
     return color_out
+
+
+# ---- material editing (tensoir_amd/materials.py) ---------------------------------------------------------------------
+MATERIAL_MAX_EDITS = _K["TIR_MATERIAL_MAX_EDITS"]
+MATERIAL_EDIT_FLOATS = _K["TIR_MATERIAL_EDIT_FLOATS"]       # floats of one edit record (layout: include/tensoir_hip.h)
+MATERIAL_MAX_PALETTE = _K["TIR_MATERIAL_MAX_PALETTE"]
+KMEANS_ROWS = _K["TIR_KMEANS_ROWS"]                         # rows per workgroup of tir_kmeans_assign
+
+
+def _rows(t, name, width):
+    """An fp32 device matrix whose rows are `width` contiguous floats at any row stride (a column view of a wider row is taken
+    as it is, never copied) -> (tensor, row stride in floats)."""
+    _req(t, torch.float32, name)
+    if width == 1 and t.dim() == 1:
+        t = t.unsqueeze(1)
+    if t.dim() != 2 or t.shape[1] != width:
+        raise ValueError(f"{name}: expected [M, {width}], got {tuple(t.shape)}")
+    if (width > 1 and t.stride(1) != 1) or (t.shape[0] > 1 and t.stride(0) < width):
+        t = t.contiguous()
+    return t, (int(t.stride(0)) if t.shape[0] > 1 else width)
+
+
+def _edit_list(records, centroids):
+    records = f32(records, "records", MATERIAL_EDIT_FLOATS).view(-1, MATERIAL_EDIT_FLOATS)
+    k = 0
+    if centroids is not None:
+        centroids = f32(centroids, "centroids", 4).view(-1, 4)
+        k = centroids.shape[0]
+    return records, records.shape[0], centroids, k
+
+
+def material_edit(records, centroids, rough_weight, points, albedo, rough, fresnel, m_dev=None):
+    """tir_material_edit: the edit list `records` [n, 32] (palette `centroids` [k, 4] or None, roughness weight) on M rows of
+    points [M, 3], albedo [M, 3], rough [M] or [M, 1], fresnel [M, 3] -- column views of wider rows are read in place -- ->
+    dict(albedo, roughness, fresnel, base, metal), new dense tensors.  m_dev (int32 device scalar): only the first min(M, m_dev)
+    rows exist; the rows beyond are not written (they hold what torch.empty left)."""
+    records, n, centroids, k = _edit_list(records, centroids)
+    (points, ps), (albedo, as_), (rough, rs), (fresnel, fs) = (_rows(points, "points", 3), _rows(albedo, "albedo", 3),
+                                                              _rows(rough, "roughness", 1), _rows(fresnel, "fresnel", 3))
+    M, dev = albedo.shape[0], albedo.device
+    if not (points.shape[0] == rough.shape[0] == fresnel.shape[0] == M):
+        raise ValueError(f"material_edit: {points.shape[0]} points, {M} albedo, {rough.shape[0]} roughness and {fresnel.shape[0]} "
+                         "fresnel rows")
+    v3 = lambda: torch.empty((M, 3), dtype=torch.float32, device=dev)
+    v1 = lambda: torch.empty((M,), dtype=torch.float32, device=dev)
+    out = {"albedo": v3(), "roughness": v1(), "fresnel": v3(), "base": v3(), "metal": v1()}
+    with torch.cuda.device(dev):
+        _call("tir_material_edit", _ptr(records if n else None), n, _ptr(centroids), k, float(rough_weight), _ptr(points), ps,
+              _ptr(albedo), as_, _ptr(rough), rs, _ptr(fresnel), fs, _ptr(out["albedo"]), _ptr(out["roughness"]), _ptr(out["fresnel"]),
+              _ptr(out["base"]), _ptr(out["metal"]), M, _ptr(m_dev), _stream())
+    return out
+
+
+def material_edit_maps(records, centroids, rough_weight, maps, rays, acc_thres=0.5):
+    """tir_material_edit_maps: the edit list on the rows of a chunk's primary maps [B, 20] with acc > acc_thres, IN PLACE on their
+    albedo, roughness and Fresnel columns; the position is surface_compact's surf.  maps must be contiguous (it is written)."""
+    records, n, centroids, k = _edit_list(records, centroids)
+    _req(maps, torch.float32, "maps", MAP_STRIDE)
+    rays = f32(rays, "rays", 6)
+    if maps.dim() != 2 or not maps.is_contiguous() or rays.dim() != 2 or rays.shape[0] != maps.shape[0] or rays.device != maps.device:
+        raise ValueError(f"material_edit_maps: a contiguous maps [B, 20] and rays [B, 6] on its device, got {tuple(maps.shape)}, "
+                         f"{tuple(rays.shape)}")
+    with torch.cuda.device(maps.device):
+        _call("tir_material_edit_maps", _ptr(records if n else None), n, _ptr(centroids), k, float(rough_weight), _ptr(maps), _ptr(rays),
+              maps.shape[0], float(acc_thres), _stream())
+    return maps
+
+
+def atlas_metal(orm, cols, T, n_faces, metal):
+    """tir_atlas_metal: the B channel of atlas_pack's orm image [size, size, 4] uint8 = round(255 metal) on the owned texels, in
+    place (metal [N]: cell-major, as atlas_texels orders the texels)."""
+    if orm.dtype != torch.uint8 or not orm.is_cuda or orm.dim() != 3 or orm.shape[0] != orm.shape[1] or orm.shape[2] != 4 \
+            or not orm.is_contiguous():
+        raise ValueError("atlas_metal: orm is a contiguous [size, size, 4] uint8 image on the GPU")
+    metal = f32(metal, "metal").view(-1)
+    N = ((int(n_faces) + 1) // 2) * int(T) * int(T)
+    if metal.shape[0] != N:
+        raise ValueError(f"atlas_metal: metal takes {N} rows (ceil(F / 2) * T * T), got {metal.shape[0]}")
+    with torch.cuda.device(orm.device):
+        _call("tir_atlas_metal", _ptr(orm), int(orm.shape[0]), int(cols), int(T), int(n_faces), _ptr(metal if N else None), _stream())
+    return orm
+
+
+def kmeans_seed(albedo, rough, k, rough_weight=1.0):
+    """k farthest-point seeds from row 0 (tir_kmeans_seed, k launches of one step) -> centroids [k, 4]."""
+    albedo, rough = f32(albedo, "albedo", 3).view(-1, 3), f32(rough, "roughness").view(-1)
+    N, dev = albedo.shape[0], albedo.device
+    centroids = torch.zeros((int(k), 4), dtype=torch.float32, device=dev)
+    mind = torch.empty((max(N, 1),), dtype=torch.float32, device=dev)
+    best = torch.zeros((1,), dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        for have in range(int(k)):
+            _call("tir_kmeans_seed", _ptr(albedo), _ptr(rough), N, float(rough_weight), _ptr(centroids), int(k), have, _ptr(mind),
+                  _ptr(best), _stream())
+    return centroids
+
+
+def kmeans_workspace(N, k, dev):
+    """The buffers a Lloyd pass leaves its partials in: (part_sums [G, k, 5] f64, part_counts [G, k] i32, part_changed [G] i32)."""
+    G = int(lib().tir_kmeans_groups(int(N)))
+    if G < 0:
+        check(G, "tir_kmeans_groups")
+    return (torch.empty((G, k, 5), dtype=torch.float64, device=dev), torch.empty((G, k), dtype=torch.int32, device=dev),
+            torch.empty((G,), dtype=torch.int32, device=dev))
+
+
+def kmeans_assign(albedo, rough, centroids, labels, workspace, first, rough_weight=1.0):
+    """tir_kmeans_assign: labels [N] int32 (in place) = the nearest centroid of every row, the lowest index among equals, and the
+    per-workgroup partial sums / counts / changed-label counts in `workspace` (kmeans_workspace)."""
+    albedo, rough = f32(albedo, "albedo", 3).view(-1, 3), f32(rough, "roughness").view(-1)
+    centroids = f32(centroids, "centroids", 4)
+    i32(labels, "labels")
+    sums, counts, changed = workspace
+    if not labels.is_contiguous() or labels.shape[0] != albedo.shape[0]:
+        raise ValueError("kmeans_assign: labels is a contiguous [N] int32 tensor")
+    with torch.cuda.device(albedo.device):
+        _call("tir_kmeans_assign", _ptr(albedo), _ptr(rough), albedo.shape[0], float(rough_weight), _ptr(centroids), centroids.shape[0],
+              int(bool(first)), _ptr(labels), _ptr(sums), _ptr(counts), _ptr(changed), sums.shape[0], _stream())
+    return labels
+
+
+def kmeans_update(workspace, centroids, counts, inertia, changed):
+    """tir_kmeans_update: the partials of one assignment, added in workgroup order -> centroids [k, 4] (in place; an empty cluster
+    keeps its centroid), counts [k] int64, inertia [1] float64, changed [1] int32."""
+    sums, pc, pch = workspace
+    if not centroids.is_contiguous() or centroids.dtype != torch.float32 or centroids.shape[0] != sums.shape[1]:
+        raise ValueError("kmeans_update: centroids is the contiguous fp32 [k, 4] tensor the assignment read")
+    with torch.cuda.device(centroids.device):
+        _call("tir_kmeans_update", _ptr(sums), _ptr(pc), _ptr(pch), sums.shape[0], _ptr(centroids), centroids.shape[0], _ptr(counts),
+              _ptr(inertia), _ptr(changed), _stream())

@@ -267,7 +267,11 @@ def finish_pending(tensoIR):
 def shade_from_maps(tensoIR, maps, rays, light_idx, sample_method="fixed_envirmap", args=None,
                     use_linear2srgb=True, acc_thres=-1e30, return_aux=False, _defer_check=False):
     """The body of render_with_BRDF (models/relight_utils.py:417-480) on packed [M,20] map rows.
-    Rows with acc <= acc_thres are background: no secondary rays, white output (renderer.py:86-106)."""
+    Rows with acc <= acc_thres are background: no secondary rays, white output (renderer.py:86-106).
+    Material edits need no argument here -- a caller edits the rows first:
+        out, maps = model(rays, light_idx, _return_maps=True)
+        materials.apply_to_maps(maps, rays, edits, acc_thres=0.5)
+        rgb = shade_from_maps(model, maps, rays, light_idx, "fixed_envirmap", args, acc_thres=0.5)"""
     dev = maps.device
     M = maps.shape[0]
     rays = ops.to_device(rays, dev, torch.float32).contiguous()
@@ -618,7 +622,7 @@ def relight_importance_sampled(tensoIR, env, light_name, surface_xyz, normal, al
 
 @torch.no_grad()
 def relight_chunk(tensoIR, env, light_names, rays, light_idx, num_samples=512, nSample=96, vis_near=0.05, vis_far=1.5,
-                  N_samples=-1, out=None, mis=None):
+                  N_samples=-1, out=None, mis=None, edits=None):
     """One chunk of scripts/relight_importance.py:93-185 for ALL environment maps without a host round trip: primary pass ->
     the acc > 0.5 rows compacted ON THE DEVICE (the script's boolean-mask indexing, :99-113, is a synchronisation per chunk
     plus ~12 indexing launches) -> per map: importance sampling, visibility march and BRDF integration bounded by the
@@ -629,12 +633,23 @@ def relight_chunk(tensoIR, env, light_names, rays, light_idx, num_samples=512, n
     relit colour already clamped and sRGB-encoded by the integration kernel; BACKGROUND rows hold the raw environment lookup
     (Environment_Light.get_light) -- the script's clamp, tone mapping of the background and its `acc > 0.9` blend of the two
     (`:172-176`) are the caller's (prim[6] is acc_map).
-    mis: relight_importance_sampled's (a MisConfig: map and BRDF sampling under the balance heuristic; None: as above)."""
+    mis: relight_importance_sampled's (a MisConfig: map and BRDF sampling under the balance heuristic; None: as above).
+    edits (a materials.EditList or a list of MaterialEdit; None: no kernel is added and every result keeps its bits):
+    materials.apply_to_maps runs once on the chunk's map rows before they are compacted, so the relit colours, the compacted
+    arrays and the albedo, roughness and Fresnel maps handed back in `prim` (views of the edited rows, made so explicitly) are the
+    edited ones.  What the primary pass composited from the unedited materials -- rgb_map, rgb_with_brdf_map -- is NOT
+    re-rendered."""
+    from . import materials
+    edits = materials.as_edit_list(edits)                  # refused before the chunk is rendered
     dev = rays.device
     rays = rays.to(torch.float32).contiguous()
     B = rays.shape[0]
     names = list(light_names)
     prim, maps = tensoIR(rays, light_idx, N_samples=N_samples, _return_maps=True)
+    if edits is not None and len(edits) > 0:
+        materials.apply_to_maps(maps, rays, edits, 0.5)
+        # unpack_maps hands out column views of `maps`; a forward that returned copies would still show the unedited materials
+        prim = tuple(prim[:3]) + (maps[:, 7:10], maps[:, 10:11], maps[:, 11:14]) + tuple(prim[6:])
     c = ops.surface_compact(maps, rays, 0.5)
     if out is None:
         out = torch.empty((B, 3 * max(len(names), 1)), dtype=torch.float32, device=dev)
@@ -669,7 +684,7 @@ def _map_rows(prim, B):
 
 @torch.no_grad()
 def relight_view(tensoIR, env, light_names, rays, H, W, light_idx=None, num_samples=512, chunk=4096, nSample=96, vis_near=0.05,
-                 vis_far=1.5, denoise=None, mis=None):
+                 vis_far=1.5, denoise=None, mis=None, edits=None):
     """A whole H x W view relit under every map of `light_names`: relight_chunk over chunks of `chunk` rays (rays [H * W, 6],
     row-major; light_idx [H * W] or [H * W, 1], default zeros) into one [H * W, 3 n_maps] buffer, the denoiser's guide rows packed
     next to it (tir_denoise_guide, one launch per chunk), and with denoise = a tensoir_amd.denoise.AtrousConfig the guided
@@ -679,6 +694,9 @@ def relight_view(tensoIR, env, light_names, rays, H, W, light_idx=None, num_samp
     (acc <= 0.5: not valid in the guide) the raw environment lookup, which the filter neither changes nor reads.
     num_samples: importance samples per surface point and map -- with the filter, 16 to 64 instead of 512.
     mis: relight_importance_sampled's (a MisConfig: map and BRDF sampling under the balance heuristic; None: map only).
+    edits: relight_chunk's (material edits; None: nothing is added).  The guide rows are built from the EDITED maps
+    -- a guide of unedited albedo would let the filter blur across an edit's border; nothing the primary pass composited is
+    re-rendered.
     Single process: the multi-rank gather of the benchmark keeps its own loop."""
     from . import denoise as dn
     H, W, chunk = int(H), int(W), int(chunk)
@@ -691,6 +709,8 @@ def relight_view(tensoIR, env, light_names, rays, H, W, light_idx=None, num_samp
         raise TypeError(f"relight_view: mis is None or a MisConfig, got {type(mis).__name__}")
     if denoise is not None and not isinstance(denoise, dn.AtrousConfig):
         raise TypeError(f"relight_view: denoise is None or an AtrousConfig, got {type(denoise).__name__}")
+    from . import materials
+    edits = materials.as_edit_list(edits)
     if not rays.is_cuda:
         raise ops._lib.TensoirHipError("relight_view: rays must live on the GPU; tensoir_amd has no CPU path")
     dev, n = rays.device, H * W
@@ -704,7 +724,7 @@ def relight_view(tensoIR, env, light_names, rays, H, W, light_idx=None, num_samp
     for r0 in range(0, n, chunk):
         r1 = min(r0 + chunk, n)
         _, prim, _ = relight_chunk(tensoIR, env, names, rays[r0:r1], lidx[r0:r1], num_samples, nSample, vis_near, vis_far, out=rows[r0:r1],
-                                   mis=mis)
+                                   mis=mis, edits=edits)
         ops.denoise_guide(_map_rows(prim, r1 - r0), rays[r0:r1], guide, r0, 0.5)      # valid = relight_chunk's own acc > 0.5
         acc[r0:r1] = prim[6]
     image = lambda t: t.view(H, W, len(names), 3).permute(2, 0, 1, 3).contiguous()
