@@ -461,7 +461,7 @@ __device__ __forceinline__ void composite_one_ray(const float* __restrict__ rays
 }
 
 
-__global__ void __launch_bounds__(256)
+__global__ void __launch_bounds__(1024)
 k_composite_primary(const float* __restrict__ rays, const int32_t* __restrict__ offsets,
                     const float* __restrict__ rec_w, const float* __restrict__ rgb,
                     const float* __restrict__ brdf, const float* __restrict__ brdf_jit,
@@ -477,7 +477,11 @@ k_composite_primary(const float* __restrict__ rays, const int32_t* __restrict__ 
                                  is_relight, fixed_fresnel, out, ex.ticket != nullptr, r, lane);
     if (!ex.ticket || !is_relight) return;
     // the two smoothness losses = means over ALL rays of map columns 17 / 18 (models/tensorBase_rotated_lights.py:999-1000):
-    // the block that finishes last sums the columns in a fixed order (deterministic; no extra reduction launch)
+    // the block that finishes last sums the columns in a fixed order (deterministic; no extra reduction launch).
+    // This launch has 1024-thread workgroups (16 rays each): one ticket per 16 rays, 256 returning atomics on the one address at
+    // 4096 rays instead of the 1024 that four-ray workgroups issued within a few microseconds of each other.  The sum itself keeps
+    // its shape whatever the workgroup size: threads 0..255 take rows t, t + 256, ..., then the wave butterfly, then the four
+    // partials in order.
     __shared__ int s_last;
     __shared__ float s_part[2][4];
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // this wave's write-through stores have landed
@@ -489,13 +493,15 @@ k_composite_primary(const float* __restrict__ rays, const int32_t* __restrict__ 
     }
     __syncthreads();
     if (!s_last) return;
-    float a = 0.0f, g = 0.0f;
-    for (int i = threadIdx.x; i < B; i += 256) {
-        a += __hip_atomic_load(out + (size_t)i * TIR_MAP_STRIDE + 17, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        g += __hip_atomic_load(out + (size_t)i * TIR_MAP_STRIDE + 18, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (threadIdx.x < 256) {
+        float a = 0.0f, g = 0.0f;
+        for (int i = threadIdx.x; i < B; i += 256) {
+            a += __hip_atomic_load(out + (size_t)i * TIR_MAP_STRIDE + 17, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            g += __hip_atomic_load(out + (size_t)i * TIR_MAP_STRIDE + 18, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        a = group_sum<64>(a); g = group_sum<64>(g);
+        if (lane == 0) { s_part[0][threadIdx.x >> 6] = a; s_part[1][threadIdx.x >> 6] = g; }
     }
-    a = group_sum<64>(a); g = group_sum<64>(g);
-    if (lane == 0) { s_part[0][threadIdx.x >> 6] = a; s_part[1][threadIdx.x >> 6] = g; }
     __syncthreads();
     if (threadIdx.x == 0) {
         ex.smooth_out[0] = ((s_part[0][0] + s_part[0][1]) + (s_part[0][2] + s_part[0][3])) / (float)B;
@@ -530,7 +536,9 @@ extern "C" int tir_composite_primary_fused(const float* rays, const int32_t* off
     if (B == 0) return TIR_OK;
     if (!rays || !offsets || !acc || !depth || !out_maps) return TIR_ERR_ARG;
     TirCompositeExtras ex{ticket, smooth_out, reinterpret_cast<long long*>(rng_state), (long long)rng_step};
-    hipLaunchKernelGGL(k_composite_primary, dim3((B + 3) / 4), dim3(256), 0, tir_stream(stream), rays, offsets,
+    // with the tail: 16 rays per workgroup (see the kernel), at most one workgroup per CU at 4096 rays
+    const bool tail = ticket != nullptr;
+    hipLaunchKernelGGL(k_composite_primary, dim3(tail ? (B + 15) / 16 : (B + 3) / 4), dim3(tail ? 1024 : 256), 0, tir_stream(stream), rays, offsets,
                        rec_w, rgb, brdf, brdf_jit, pred_normal, derived_normal, acc, depth, B, white_bg,
                        is_relight, fixed_fresnel, out_maps, ex);
     TIR_CHECK_LAUNCH();

@@ -209,7 +209,7 @@ __global__ void k_pack_mlp(const float* __restrict__ w0, const float* __restrict
             else if (j < BH_W2) { int q = j - BH_B1; v = b1[unit_of(q % 64, q / 64)]; }
             else if (j < BH_B2) {
                 int q = j - BH_W2, h = q / (4 * W2A_STRIDE), o = (q / W2A_STRIDE) % 4, u = q % W2A_STRIDE;
-                v = (o < out_dim && u < 64) ? 0.5f * w2[o * HID + unit_of(u, h)] : 0.0f;     // x 1/2: B operand is 2 relu(h)
+                v = (o < out_dim && u < 64) ? w2[o * HID + unit_of(u, h)] : 0.0f;            // B operand is relu(h) itself
             }
             else { int o = j - BH_B2; v = (o < out_dim) ? b2[o] : 0.0f; }
         } else {                                // two bf16 per float slot
@@ -504,6 +504,45 @@ __device__ __forceinline__ float relu(float x) {
     return __builtin_bit_cast(float, __builtin_elementwise_max(__builtin_bit_cast(int, x), 0));
 }
 
+// ---- layer 3 (128 -> out <= 4) on the matrix pipe, exact fp32, shared by every decoder kernel of this file.
+// v_mfma_f32_4x4x1_16b_f32 computes 16 independent 4x4 outer products per issue.  Block = 4 consecutive lanes (same half);
+// lane 4b+j supplies B = its own sample's hidden value (column j) and A = W2[row j][that unit]; D register i of lane 4b+j =
+// out_i of the lane's sample.  64 issues of 8 cycles replace 256 FMAs + 64 LDS reads per lane; four accumulator chains
+// (unit q goes to chain q % 4, in ascending q) break the dependency chain.
+// (register layout probed on gfx950: D reg i of lane 4b+j = A(lane 4b+i) * B(lane 4b+j).)
+// The ReLU of the 64 layer-2 accumulators is taken IN PLACE, on the integer pipe (relu above: one v_max_i32 each, which issues
+// under other waves' matrix instructions), and all of it ahead of the first matrix instruction: the accumulators are dead
+// afterwards, and no VALU write then lands on a register that a matrix instruction in flight still reads.  (The earlier form,
+// B = x + |x| against a W2a image scaled by 1/2, wrote one temporary per issue: a v_add_f32 and a wait state in front of every
+// matrix instruction.)  The products are the same bits for every finite activation.  Non-finite ones differ, on purpose: x = -inf
+// gives 0 as the reference's ReLU does (x + |x| gave NaN), and a NaN with the sign bit set becomes 0.
+// Returns this lane half's partial sums of the four outputs; the caller adds the other half's (lane ^ 32) and the bias.
+__device__ __forceinline__ void layer3_relu_mfma(const float* __restrict__ lds, int h, int lane, f32x16 (&acc2)[4], float (&o)[4]) {
+#pragma unroll
+    for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc2[mt][r] = relu(acc2[mt][r]);
+    // left to itself the scheduler sinks each v_max_i32 in front of its matrix instruction again, into ONE temporary (the wait
+    // states are back); nothing crosses this line
+    __builtin_amdgcn_sched_barrier(0);
+    f32x4 o4[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) o4[c] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const float* wp = lds + BH_W2 + (h * 4 + (lane & 3)) * W2A_STRIDE;
+#pragma unroll
+    for (int g = 0; g < 16; ++g) {
+        const float4 w = *reinterpret_cast<const float4*>(wp + 4 * g);
+        const float wv[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int q = 4 * g + e;
+            o4[e] = __builtin_amdgcn_mfma_f32_4x4x1f32(wv[e], acc2[q >> 4][q & 15], o4[e], 0, 0, 0);
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) o[i] = (o4[0][i] + o4[1][i]) + (o4[2][i] + o4[3][i]);
+}
+
 // LDS operand tiles are read through four per-lane byte bases (W0hi / W0lo / W1hi / W1lo section start + this lane's
 // offset) that the compiler cannot see through, plus compile-time offsets < 64 KB that fit the 16-bit ds offset field.
 // Left to itself (150 KB image, absolute addresses above the 64 KB offset range) the compiler hoists one address VGPR
@@ -735,34 +774,9 @@ mlp_bf16_body(const float* __restrict__ packed, const float* __restrict__ feat, 
                     *reinterpret_cast<float4*>(h2o + s_raw * HID + mt * 32 + 8 * i + 4 * h) =
                         make_float4(relu(acc2[mt][4 * i]), relu(acc2[mt][4 * i + 1]), relu(acc2[mt][4 * i + 2]), relu(acc2[mt][4 * i + 3]));
         }
-        // ---- layer 3 (128 -> out <= 4) on the matrix pipe, exact fp32: v_mfma_f32_4x4x1_16b_f32 computes 16 independent
-        // 4x4 outer products per issue.  Block = 4 consecutive lanes (same half); lane 4b+j supplies B = its own sample's
-        // hidden value (column j) and A = W2[row j][that unit]; D register i of lane 4b+j = out_i of lane's sample.
-        // 64 issues of 8 cycles replace 256 FMAs + 64 LDS reads per lane; four accumulators break the dependency chain.
-        // (register layout probed on gfx950: D reg i of lane 4b+j = A(lane 4b+i) * B(lane 4b+j).)
-        f32x4 o4[4];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) o4[c] = f32x4{0.f, 0.f, 0.f, 0.f};
-        {
-            const float* wp = lds + BH_W2 + (h * 4 + (lane & 3)) * W2A_STRIDE;
-#pragma unroll
-            for (int g = 0; g < 16; ++g) {
-                const float4 w = *reinterpret_cast<const float4*>(wp + 4 * g);
-                const float wv[4] = {w.x, w.y, w.z, w.w};
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const int q = 4 * g + e;
-                    const float x = acc2[q >> 4][q & 15];
-                    // 2 relu(x) = x + |x| (one VALU op the compiler can schedule and pad: an inline-asm v_max feeding an
-                    // MFMA operand would need its VALU->MFMA wait states by hand); W2a carries the exact factor 1/2
-                    o4[e] = __builtin_amdgcn_mfma_f32_4x4x1f32(wv[e], x + __builtin_fabsf(x), o4[e], 0, 0, 0);
-                }
-            }
-        }
-        float o0 = (o4[0][0] + o4[1][0]) + (o4[2][0] + o4[3][0]);
-        float o1 = (o4[0][1] + o4[1][1]) + (o4[2][1] + o4[3][1]);
-        float o2 = (o4[0][2] + o4[1][2]) + (o4[2][2] + o4[3][2]);
-        float o3 = (o4[0][3] + o4[1][3]) + (o4[2][3] + o4[3][3]);
+        float o3v[4];
+        layer3_relu_mfma(lds, h, lane, acc2, o3v);
+        float o0 = o3v[0], o1 = o3v[1], o2 = o3v[2], o3 = o3v[3];
         o0 += __shfl_xor(o0, 32, 64); o1 += __shfl_xor(o1, 32, 64);
         o2 += __shfl_xor(o2, 32, 64); o3 += __shfl_xor(o3, 32, 64);
         if (h == 0 && s_raw < n) {
@@ -971,27 +985,9 @@ __device__ __forceinline__ void fus_decode(const float* lds, unsigned w0hi, unsi
         }
         layer2_interleaved<1, 0, true>(w1hi, w1hi, acc, acc2);
     }
-    f32x4 o4[4];
-#pragma unroll
-    for (int c = 0; c < 4; ++c) o4[c] = f32x4{0.f, 0.f, 0.f, 0.f};
-    {
-        const float* wp = lds + BH_W2 + (h * 4 + (lane & 3)) * W2A_STRIDE;
-#pragma unroll
-        for (int g = 0; g < 16; ++g) {
-            const float4 w = *reinterpret_cast<const float4*>(wp + 4 * g);
-            const float wv[4] = {w.x, w.y, w.z, w.w};
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int q = 4 * g + e;
-                const float x = acc2[q >> 4][q & 15];
-                o4[e] = __builtin_amdgcn_mfma_f32_4x4x1f32(wv[e], x + __builtin_fabsf(x), o4[e], 0, 0, 0);
-            }
-        }
-    }
-    float o0 = (o4[0][0] + o4[1][0]) + (o4[2][0] + o4[3][0]);
-    float o1 = (o4[0][1] + o4[1][1]) + (o4[2][1] + o4[3][1]);
-    float o2 = (o4[0][2] + o4[1][2]) + (o4[2][2] + o4[3][2]);
-    float o3 = (o4[0][3] + o4[1][3]) + (o4[2][3] + o4[3][3]);
+    float o3v[4];
+    layer3_relu_mfma(lds, h, lane, acc2, o3v);
+    float o0 = o3v[0], o1 = o3v[1], o2 = o3v[2], o3 = o3v[3];
     o0 += __shfl_xor(o0, 32, 64); o1 += __shfl_xor(o1, 32, 64);
     o2 += __shfl_xor(o2, 32, 64); o3 += __shfl_xor(o3, 32, 64);
     __builtin_amdgcn_s_setprio(0);
@@ -1483,27 +1479,9 @@ k_indirect_fused_hp(TirField f, const float* __restrict__ packed, const float* _
             for (int r = 0; r < 16; ++r) acc2[mt][r] = bp[r];
         }
         hp_layer2<0>(w1hi, w1f8, hp, h8, acc2);
-        f32x4 o4[4];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) o4[c] = f32x4{0.f, 0.f, 0.f, 0.f};
-        {
-            const float* wp = lds + BH_W2 + (h * 4 + (lane & 3)) * W2A_STRIDE;
-#pragma unroll
-            for (int g = 0; g < 16; ++g) {
-                const float4 w = *reinterpret_cast<const float4*>(wp + 4 * g);
-                const float wv[4] = {w.x, w.y, w.z, w.w};
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const int q = 4 * g + e;
-                    const float x = acc2[q >> 4][q & 15];
-                    o4[e] = __builtin_amdgcn_mfma_f32_4x4x1f32(wv[e], x + __builtin_fabsf(x), o4[e], 0, 0, 0);
-                }
-            }
-        }
-        float o0 = (o4[0][0] + o4[1][0]) + (o4[2][0] + o4[3][0]);
-        float o1 = (o4[0][1] + o4[1][1]) + (o4[2][1] + o4[3][1]);
-        float o2 = (o4[0][2] + o4[1][2]) + (o4[2][2] + o4[3][2]);
-        float o3 = (o4[0][3] + o4[1][3]) + (o4[2][3] + o4[3][3]);
+        float o3v[4];
+        layer3_relu_mfma(lds, h, lane, acc2, o3v);
+        float o0 = o3v[0], o1 = o3v[1], o2 = o3v[2], o3 = o3v[3];
         o0 += __shfl_xor(o0, 32, 64); o1 += __shfl_xor(o1, 32, 64);
         o2 += __shfl_xor(o2, 32, 64); o3 += __shfl_xor(o3, 32, 64);
         if (h == 0 && sd < n) {

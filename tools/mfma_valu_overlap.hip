@@ -15,10 +15,12 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 h2 __attribute__((ext_vector_type(2)));
 
 // MK: 0 = v_mfma_f32_32x32x16_f16 (32 cycles), 1 = v_mfma_f32_16x16x32_f16 (16 cycles, issued twice as often), 2 = v_mfma_f32_32x32x16_bf16,
-//     3 = v_mfma_f32_32x32x2_f32 (exact fp32, 64 cycles per 16 passes ... issued half as often)
+//     3 = v_mfma_f32_32x32x2_f32 (exact fp32, 64 cycles per 16 passes ... issued half as often),
+//     4 = v_mfma_f32_4x4x1_16b_f32 (the decoders' layer 3: 8 cycles, issued four times as often)
 // VK: 0 = v_fma_f32, 1 = v_pk_fma_f16, 2 = v_pk_fma_f32, 3 = v_sin_f32 (transcendental unit), 4 = v_cvt_pkrtz_f16_f32,
 //     5 = v_pk_fma_f16 with SIXTEEN independent chains (is VK 1's overlap only the matrix pipe filling dependency stalls?), 6 = v_fma_f32 x 16,
-//     7 = v_mad_u32_u24 (integer), 8 = v_fma_mix_f32 (fp16 operand read in place, fp32 arithmetic)
+//     7 = v_mad_u32_u24 (integer), 8 = v_fma_mix_f32 (fp16 operand read in place, fp32 arithmetic),
+//     9 = v_max_i32 (the ReLU in front of layer 3)
 template <int MK, int VK>
 __global__ void __launch_bounds__(512) k(float* out, int mode, int n_mfma, int n_valu) {
     const int wave = threadIdx.x >> 6;
@@ -46,6 +48,13 @@ __global__ void __launch_bounds__(512) k(float* out, int mode, int n_mfma, int n
             for (int i = 0; i < 16; ++i) s += c0[i] + c1[i] + c2[i] + c3[i];
         } else {
             f32x4 c0 = {}, c1 = {}, c2 = {}, c3 = {};
+            if constexpr (MK == 4) {
+                const float x = (float)a[0], y = (float)b[0];
+                for (int i = 0; i < 4 * n_mfma; ++i) {
+                    c0 = __builtin_amdgcn_mfma_f32_4x4x1f32(x, y, c0, 0, 0, 0); c1 = __builtin_amdgcn_mfma_f32_4x4x1f32(x, y, c1, 0, 0, 0);
+                    c2 = __builtin_amdgcn_mfma_f32_4x4x1f32(x, y, c2, 0, 0, 0); c3 = __builtin_amdgcn_mfma_f32_4x4x1f32(x, y, c3, 0, 0, 0);
+                }
+            } else
             for (int i = 0; i < 2 * n_mfma; ++i) {
                 c0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c0, 0, 0, 0); c1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c1, 0, 0, 0);
                 c2 = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c2, 0, 0, 0); c3 = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c3, 0, 0, 0);
@@ -90,6 +99,13 @@ __global__ void __launch_bounds__(512) k(float* out, int mode, int n_mfma, int n
             for (int i = 0; i < n_valu; ++i)
 #pragma unroll
                 for (int j = 0; j < 8; ++j) asm volatile("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(v[j]) : "v"(v[j]), "v"(3u), "v"(7u));
+            for (int j = 0; j < 8; ++j) s += (float)v[j];
+        } else if constexpr (VK == 9) {
+            int v[8];
+            for (int j = 0; j < 8; ++j) v[j] = (int)threadIdx.x - 256 + j;
+            for (int i = 0; i < n_valu; ++i)
+#pragma unroll
+                for (int j = 0; j < 8; ++j) asm volatile("v_max_i32 %0, %1, %2" : "=v"(v[j]) : "v"(v[j]), "v"(-3));
             for (int j = 0; j < 8; ++j) s += (float)v[j];
         } else if constexpr (VK == 8) {
             float v[8];
@@ -159,5 +175,9 @@ int main() {
     run<0, 5>(out, "v_mfma_f32_32x32x16_f16", "v_pk_fma_f16 (16 chains)", nm, nv);
     run<0, 6>(out, "v_mfma_f32_32x32x16_f16", "v_fma_f32 (16 chains)", nm, nv);
     run<1, 5>(out, "v_mfma_f32_16x16x32_f16", "v_pk_fma_f16 (16 chains)", nm, nv);
+    run<4, 0>(out, "v_mfma_f32_4x4x1_16b_f32", "v_fma_f32", nm, nv);
+    run<4, 7>(out, "v_mfma_f32_4x4x1_16b_f32", "v_mad_u32_u24", nm, nv);
+    run<4, 9>(out, "v_mfma_f32_4x4x1_16b_f32", "v_max_i32", nm, nv);
+    run<0, 9>(out, "v_mfma_f32_32x32x16_f16", "v_max_i32", nm, nv);
     return 0;
 }
